@@ -18,9 +18,15 @@ Poisson matrix (n = 16 777 216, nnz = 83 869 696, Int32 indices).  N > 1: weak s
 GPU); the sub-record `strong_scaling` is BASELINE configs[2], the fixed 8192^2 problem over the N GPUs, with
 the same problem on rank 0 alone beside it (speed-up measured inside one run).
 
+A plain run does what the headline needs and nothing else: it builds and verifies the problem, warms up (untimed,
+the launches a full run makes before its headline window), times exactly K steps and prints the line.  `--full` adds everything
+else the line can carry: the cold window and the per-launch cross-check, the opt-in packed copy, `cpu_baseline` (the
+oracle's restatement of the reference kernel, timed on this host's cores), the strong-scaling and other-config
+sub-records and, at N > 1, the transport comparison; the `--no-*` options leave single stages out of a full run.
+`--dump-outputs DIR` writes what the last timed step computed (see dump_outputs).
+
 Output: ONE JSON line on rank 0 (contract in the task statement) with `roofline` (HBM, algorithmic
-bytes / per-launch time measured with HIP events on the launch stream) and `cpu_baseline` (the
-oracle's restatement of the reference kernel, timed on this host's cores).
+bytes / the time of one timed step).
 """
 import argparse
 import json
@@ -53,7 +59,45 @@ def parse():
     ap.add_argument("--strong-size", type=int, default=8192, help="grid edge of the strong-scaling sub-record (BASELINE configs[2])")
     ap.add_argument("--no-strong", action="store_true", help="skip the strong-scaling sub-record")
     ap.add_argument("--no-extras", action="store_true", help="skip the CG / SpMM sub-records (BASELINE configs[3], [4])")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: cold window, per-launch cross-check, packed copy, CPU "
+                         "baseline, strong-scaling and other-config sub-records, the N > 1 transport comparison")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write y of the last step (a fixed sample of its rows) as .npy files to DIR")
+    args = ap.parse_args()
+    if args.dump_outputs is not None:
+        if args.workload not in ("poisson2d", "poisson2d_strong"):
+            ap.error("--dump-outputs is implemented for the poisson2d workloads")
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+    return args
+
+
+DUMP_SAMPLE_ROWS = 1 << 21            # per job: values + row numbers in float64 are 32 MiB at most
+DUMP_SEED = 20240611
+
+
+def dump_rows(nrows, world):
+    """The rows of y that --dump-outputs writes: all of them up to DUMP_SAMPLE_ROWS / world, else the first and last 4096
+    (the halo-adjacent grid lines; fewer at many ranks) and a seeded uniform draw -- the same rows in every run with the same arguments."""
+    cap = DUMP_SAMPLE_ROWS // world
+    if nrows <= cap:
+        return np.arange(nrows, dtype=np.int64)
+    w = min(4096, cap // 4)
+    edge = np.concatenate([np.arange(w), np.arange(nrows - w, nrows)])
+    draw = np.random.default_rng(DUMP_SEED).integers(0, nrows, cap - edge.size)
+    return np.unique(np.concatenate([edge, draw]))[:cap]
+
+
+def dump_outputs(dirname, torch, y, nrows, world, rank):
+    """--dump-outputs: y = A*x as the last timed step left it -- what a caller of mul! receives -- on this rank's rows, in
+    float64: DIR/y.npy (DIR/y_rank<r>.npy at N > 1) and the local row numbers of those entries in DIR/y_rows.npy
+    (y_rank<r>_rows.npy)."""
+    rows = dump_rows(nrows, world)
+    vals = y.v[torch.from_numpy(rows).to(y.v.device)].cpu().numpy().astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    name = "y" if world == 1 else f"y_rank{rank}"
+    np.save(os.path.join(dirname, name + ".npy"), vals)
+    np.save(os.path.join(dirname, name + "_rows.npy"), rows.astype(np.float64))
 
 
 def usable_cores() -> int:
@@ -784,39 +828,54 @@ def _run(args, budget):
     # build: W untimed steps, K timed -- what `--steps 20 --warmup 5` times on a plan that has seen nothing but its own
     # construction (1 verifying launch + the 64 launches of the plan-time block-order measurement); the headline `value`
     # is the same bracket run after the diagnostics below, i.e. in the steady state.
-    cold_elapsed, cold_launch_ms = run.time_steps(args.steps, args.warmup)
-    stage("cold window timed")
+    # Both are diagnostics of --full.  A plain run makes the same launches untimed, as its warm-up: the headline window then
+    # follows the same sequence as in a full run (measured, alternating runs: a time-based settle of 40-200 ms in its place
+    # left the K = 20 window 3-4 % slower).
     reps = min(max(args.steps, 20), 200)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
-    job.barrier()
-    for a, b in evs:
+    if not args.full:
+        for _ in range(args.warmup + args.steps):
+            hp.mul_(y, A, x)
+        job.barrier()
+        for _ in range(2 * reps):
+            hp.mul_(y, A, x)
+        torch.cuda.synchronize()
+        stage("warm-up done")
+    else:
+        cold_elapsed, cold_launch_ms = run.time_steps(args.steps, args.warmup)
+        stage("cold window timed")
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+        job.barrier()
+        for a, b in evs:
+            a.record()
+            hp.mul_(y, A, x)
+            b.record()
+        torch.cuda.synchronize()
+        per_launch_ms = np.array([a.elapsed_time(b) for a, b in evs])
+        launch_ms = float(np.mean(per_launch_ms))
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        hp.mul_(y, A, x)
+        for _ in range(reps):                # back-to-back launches between ONE event pair
+            hp.mul_(y, A, x)
         b.record()
-    torch.cuda.synchronize()
-    per_launch_ms = np.array([a.elapsed_time(b) for a, b in evs])
-    launch_ms = float(np.mean(per_launch_ms))
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):                # back-to-back launches between ONE event pair
-        hp.mul_(y, A, x)
-    b.record()
-    torch.cuda.synchronize()
-    stream_ms = a.elapsed_time(b) / reps
-    stage("per-launch cross-check done")
+        torch.cuda.synchronize()
+        stream_ms = a.elapsed_time(b) / reps
+        stage("per-launch cross-check done")
 
     elapsed, timed_region_launch_ms = run.time_steps(args.steps, args.warmup)
     stage("headline timed")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, y, nrows_loc, world, rank)
+        stage(f"outputs written to {args.dump_outputs}")
     timed_out = bool(job.max(1.0 if plan.timed_out() else 0.0))
 
     # ---- N > 1: every ordering of the distributed step + its pieces -- measured LAST (see _guarded_breakdown:
     #      it drives transports the timed loop did not use, and must not be able to cost the measured result) ----
     selftest = os.environ.get("HPCLA_BENCH_BREAKDOWN_SELFTEST", "") == "1"      # runs the local legs at N = 1
-    want_breakdown = (world > 1 and bool(job.max(1.0 if plan.has_halo else 0.0))) or selftest
+    want_breakdown = (args.full and world > 1 and bool(job.max(1.0 if plan.has_halo else 0.0))) or selftest
 
     # ---- opt-in packed copy (3 B per stored entry instead of 12; same bits), reported separately --------
     packed = None
-    if not args.no_packed and world == 1 and budget.allows("packed"):   # an optional extra must not stand between an N > 1 run and its result line
+    if args.full and not args.no_packed and world == 1 and budget.allows("packed"):   # an optional extra must not stand between an N > 1 run and its result line
         if A.enable_packed(x):
             hp.mul_(y, A, x)
             torch.cuda.synchronize()
@@ -871,24 +930,26 @@ def _run(args, budget):
                      "frac_device_events": round(achieved_events / HBM_PEAK_GBS, 4),
                      "kernel": kernel, "algorithmic_bytes_per_launch": b_alg_loc,
                      "launch_ms_timed_region": round(timed_region_launch_ms, 5),
-                     "launch_ms_event_pairs": round(launch_ms, 5), "launch_ms_back_to_back": round(stream_ms, 5),
                      "launches_before_timed_region": (1 + 2 * reps + 2 * args.warmup + args.steps +
                                                       (64 if run.plan.block_group_measured else 0)),
-                     "cold_window": {"ms_per_step": round(cold_elapsed / args.steps * 1e3, 5),
-                                     "launch_ms": round(cold_launch_ms, 5),
-                                     "frac": round(b_alg_loc / (cold_launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                     "launches_before": 1 + args.warmup + (64 if run.plan.block_group_measured else 0),
-                                     "note": "the same bracket (W untimed + K timed steps between barrier + synchronize), run FIRST "
-                                             "behind the plan build; the first ~30 launches after load begins run 2-4 % slower than "
-                                             "the steady state the headline window measures"},
-                     "block_order_group": run.plan.block_group,
-                     "launch_ms_min": round(float(per_launch_ms.min()), 5),
-                     "launch_ms_median": round(float(np.median(per_launch_ms)), 5)},
+                     "block_order_group": run.plan.block_group},
         "hbm_gbs_whole_job": round(b_alg_tot / (elapsed / args.steps) / 1e9, 1),
         "hbm_frac_of_peak_whole_job": round(b_alg_tot / (elapsed / args.steps) / 1e9 / (HBM_PEAK_GBS * world), 4),
         "verified_vs_closed_form": verified, "exchange_timed_out": timed_out, "setup_s": round(run.setup_s, 2),
         "packed_csr_opt_in": packed,
     }
+    if args.full:
+        result["roofline"].update({
+            "launch_ms_event_pairs": round(launch_ms, 5), "launch_ms_back_to_back": round(stream_ms, 5),
+            "cold_window": {"ms_per_step": round(cold_elapsed / args.steps * 1e3, 5),
+                            "launch_ms": round(cold_launch_ms, 5),
+                            "frac": round(b_alg_loc / (cold_launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                            "launches_before": 1 + args.warmup + (64 if run.plan.block_group_measured else 0),
+                            "note": "the same bracket (W untimed + K timed steps between barrier + synchronize), run FIRST "
+                                    "behind the plan build; the first ~30 launches after load begins run 2-4 % slower than "
+                                    "the steady state the headline window measures"},
+            "launch_ms_min": round(float(per_launch_ms.min()), 5),
+            "launch_ms_median": round(float(np.median(per_launch_ms)), 5)})
     if world > 1:
         # the strong-scaling speed-up (BASELINE: ">= 6x at 8 GPUs over 1") is filled in below; placed at the TOP level
         # next to the transport facts so a reader of `value` (weak scaling) cannot miss it
@@ -896,7 +957,7 @@ def _run(args, budget):
         result["n_ranks_rccl"] = world if backend.has_rccl else 0
         result["peer_windows"] = bool(backend.peer_windows)
         result["strong_scaling_speedup_vs_n1"] = None
-    if world == 1 and not args.no_cpu_baseline and budget.allows("cpu_baseline", args.cpu_seconds + 18):   # the contract: rank 0 at N = 1 only
+    if args.full and world == 1 and not args.no_cpu_baseline and budget.allows("cpu_baseline", args.cpu_seconds + 18):   # the contract: rank 0 at N = 1 only
         lo, hi = run.lo, run.hi
         xg = x.local_values()
         if plan.has_halo:
@@ -914,7 +975,7 @@ def _run(args, budget):
     # Optional stages run in order of value and only while the budget covers them (benchmarks/budget.py): a stage
     # that would not fit is recorded as {"skipped": "budget"}, decided by all ranks together.
     from benchmarks.budget import SKIPPED
-    if not strong and not args.no_strong:
+    if args.full and not strong and not args.no_strong:
         run.release()
         del A, x, y, plan
         hp.clear_plan_cache()
@@ -955,7 +1016,7 @@ def _run(args, budget):
     #      (3-D Poisson, 100 CG iterations) and configs[4] (SpMM, k = 16): config 5 at its own gather set (B = 2^24 x 16
     #      rows whatever N is: at N = 1 all of it local -- the HBM side of the 8-GPU job), the 5-point matrix x 16
     #      (the kernel's own efficiency), and the Infinity-Cache-sized B of round 2 labelled as such ----------------
-    if not strong and not args.no_extras:
+    if args.full and not strong and not args.no_extras:
         import copy
         from benchmarks import extra_workloads
         extras = {}
@@ -1002,7 +1063,8 @@ def _run(args, budget):
                 extras[name] = {"error": f"{type(exc).__name__}: {exc}"}
             stage(f"{name} sub-record done")
         result["other_configs"] = extras
-    result["configs_digest"] = configs_digest(result)
+    if args.full:
+        result["configs_digest"] = configs_digest(result)
     verified = verified and not timed_out
     result["verified_vs_closed_form"] = verified
     job.barrier()

@@ -11,6 +11,8 @@ TAG=${1:-r01}; shift
 STEPS=${@:-pytest bench}
 run() {  # run <timeout_s> <logfile> <cmd...>
   local t=$1 log=$2; shift 2
+  # every bench.py step below reads the whole line (sub-records, comparisons, per-kernel figures): those need --full
+  case " $* " in *" bench.py "*) set -- "$@" --full;; esac
   timeout -k 10 "$t" "$@" > "$log" 2>&1
   local rc=$?
   echo "[$(date +%T)] rc=$rc :: $*" | tee -a gpurun_out/${TAG}_steps.log

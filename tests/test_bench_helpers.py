@@ -236,3 +236,33 @@ def test_profiled_kernel_names_follow_the_kernel_templates():
     table = open(os.path.join(ROOT, "benchmarks", "pmc_f32_table.py")).read()
     m = re.search(r'rg = lambda kc: "rowgather_kernel<([^"]*)>"', table)
     assert m and m.group(1).count(",") == n_t - 1
+
+
+def test_bench_options_full_and_dump_outputs(monkeypatch, tmp_path):
+    """--full is off by default (a plain run times the headline only); --dump-outputs takes a directory, made absolute so that
+    spawned ranks write to the same place, and is refused for workloads it does not cover."""
+    import pytest
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "rel_dir"])
+    a = bench.parse()
+    assert a.full is True and os.path.isabs(a.dump_outputs) and a.dump_outputs.endswith("rel_dir")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--workload", "poisson3d_cg", "--dump-outputs", str(tmp_path)])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_dump_rows_are_fixed_bounded_and_cover_the_edges():
+    """The sample --dump-outputs writes: the same rows in every run, sorted and distinct, within 64 MB with its row numbers
+    (float64 values + float64 row numbers), the halo-adjacent first and last grid lines included; small outputs whole."""
+    import bench
+    n = 4096 * 4096
+    for world in (1, 2, 8):
+        r = bench.dump_rows(n, world)
+        assert np.array_equal(r, bench.dump_rows(n, world))
+        assert np.all(np.diff(r) > 0) and r[0] == 0 and r[-1] == n - 1 and r.max() < n
+        assert world * r.size * 16 <= 64 * 2**20
+        assert np.array_equal(r[:4096], np.arange(4096)) and np.array_equal(r[-4096:], np.arange(n - 4096, n))
+    assert np.array_equal(bench.dump_rows(1000, 1), np.arange(1000))

@@ -13,6 +13,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -106,7 +107,8 @@ def test_bench_launches_its_own_ranks():
     if _device_count() < 2:
         env["HPCLA_ALLOW_SHARED_GPU"] = "1"           # rehearsal: both ranks on the one GPU
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5",
-                          "--warmup", "2", "--size", "1024", "--strong-size", "1024", "--no-cpu-baseline", "--no-extras"],
+                          "--warmup", "2", "--size", "1024", "--strong-size", "1024", "--no-cpu-baseline", "--no-extras",
+                          "--full"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -139,7 +141,7 @@ def test_bench_line_single_gpu_small_roofline_follows_from_ms_per_step():
     for k in ("RANK", "WORLD_SIZE", "HPCLA_HALO_MODE"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3", "--size", "1024",
-                          "--strong-size", "1024", "--no-extras", "--cpu-seconds", "1"],
+                          "--strong-size", "1024", "--no-extras", "--cpu-seconds", "1", "--full"],
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -148,3 +150,36 @@ def test_bench_line_single_gpu_small_roofline_follows_from_ms_per_step():
     assert rec["n_gpus"] == 1 and rec["verified_vs_closed_form"] is True
     assert rec["cpu_baseline"]["value"] > 0 and rec["cpu_baseline"]["value_1core"] > 0
     _check_line_hygiene(rec)
+
+
+def test_bench_plain_run_times_only_the_headline_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) carries the headline and nothing that takes runs of its own; --dump-outputs writes y of the
+    last timed step on the fixed sample of rows, bit-exact against the closed form of the 5-point matrix."""
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "HPCLA_HALO_MODE"):
+        env.pop(k, None)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "7", "--warmup", "2", "--size", "1024",
+                          "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, out.stdout
+    rec = json.loads(lines[0])
+    assert rec["verified_vs_closed_form"] is True and rec["steps"] == 7 and rec["warmup"] == 2
+    assert rec["ms_per_step"] > 0 and rec["dtype"] == "f64" and rec["higher_is_better"] is True
+    for moved in ("cpu_baseline", "strong_scaling", "other_configs", "configs_digest", "step_breakdown_ms_max_over_ranks"):
+        assert moved not in rec, moved
+    assert "cold_window" not in rec["roofline"] and rec["packed_csr_opt_in"] is None
+    rl = rec["roofline"]
+    want = rl["algorithmic_bytes_per_launch"] / (rec["ms_per_step"] * 1e-3) / 1e9
+    assert abs(rl["achieved"] - want) <= 1e-3 * want + 0.06, (rl["achieved"], want)
+    y, rows = np.load(tmp_path / "y.npy"), np.load(tmp_path / "y_rows.npy")
+    assert y.dtype == np.float64 and rows.dtype == np.float64 and y.shape == rows.shape == (1024 * 1024,)
+    from hpcla_amd import workloads as wl
+    g = rows.astype(np.int64)
+    nx = ny = 1024
+    gi, gj = g % nx, g // nx
+    want = np.zeros(len(g))
+    for col, ok, coef in ((g - nx, gj > 0, -1.0), (g - 1, gi > 0, -1.0), (g, np.ones_like(g, bool), 4.0),
+                          (g + 1, gi < nx - 1, -1.0), (g + nx, gj < ny - 1, -1.0)):
+        want = np.where(ok, want + coef * wl.u01(wl.SEED_X, np.where(ok, col, 0)), want)
+    assert np.array_equal(y, want)

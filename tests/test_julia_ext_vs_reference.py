@@ -5,21 +5,19 @@ The extension cannot be executed here (no Julia in the image); tests/test_julia_
 package: every name in its `using HPCLinearAlgebra: ...` list, every `HPCLinearAlgebra.<name>` it extends or calls
 (with the number of positional arguments of the methods it adds), and every field it reads from the parent's structs
 (`plan.<field>` of VectorPlan / VectorRepartitionPlan / AdditionPlan, `A.<field>` of HPCSparseMatrix, `x.<field>` of
-HPCVector, `M.<field>` of HPCMatrix, `backend.<field>`, `comm.<field>`) must exist in /root/reference/src/*.jl.
+HPCVector, `M.<field>` of HPCMatrix, `backend.<field>`, `comm.<field>`) must exist in the reference's src/*.jl.
 
-The reference tree exists only in the build container (never on the GPU box): the test skips when it is absent.
-Nothing is copied from it -- it is read as text, names and arities are extracted with regular expressions.
+The reference's side is read from tests/golden/julia_reference_api.json: the struct fields, method arities, names and the
+VectorPlan constructor's collectives that the parser below extracted from the reference's src/*.jl (data only; no source
+is copied).  tests/golden/make_julia_reference_api.py regenerates it from a reference tree with the same parser.
 """
+import json
 import os
 import re
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 EXT = os.path.join(ROOT, "integration", "HPCLinearAlgebraROCmExt.jl")
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "src")), reason="reference sources not present")
+REF_API = os.path.join(ROOT, "tests", "golden", "julia_reference_api.json")
 
 # names the PARENT PATCH of INTEGRATION.md adds (they cannot exist in the unpatched reference): checked against
 # INTEGRATION.md instead
@@ -42,12 +40,22 @@ def _strip_comments_and_strings(text):
     return "\n".join(line.split("#", 1)[0] for line in text.splitlines())
 
 
-def _ref_text():
+def reference_text(ref_dir):
+    """every src/*.jl of a reference tree, comments and strings blanked (tests/golden/make_julia_reference_api.py)"""
     out = []
-    for fn in sorted(os.listdir(os.path.join(REF, "src"))):
+    for fn in sorted(os.listdir(os.path.join(ref_dir, "src"))):
         if fn.endswith(".jl"):
-            out.append(open(os.path.join(REF, "src", fn)).read())
+            out.append(open(os.path.join(ref_dir, "src", fn)).read())
     return _strip_comments_and_strings("\n".join(out))
+
+
+def _reference():
+    """tests/golden/julia_reference_api.json, arities as (min, max) tuples"""
+    with open(REF_API) as f:
+        api = json.load(f)
+    api["functions"] = {n: [tuple(a) for a in ar] for n, ar in api["functions"].items()}
+    api["vectorplan_constructor_collectives"] = [tuple(c) for c in api["vectorplan_constructor_collectives"]]
+    return api
 
 
 def _match_paren(text, i):
@@ -152,20 +160,88 @@ def reference_names(text):
     return names
 
 
+def stub_call_arities(text):
+    """name -> positional argument counts of the reference's own CALLS of every bare stub (`function f end`)"""
+    out = {}
+    for name, arities in reference_functions(text).items():
+        if arities:
+            continue
+        out[name] = []
+        for c in re.finditer(r"(?<![\w.!])%s\(" % re.escape(name), text):
+            if text[max(c.start() - 9, 0):c.start()].strip().endswith("function"):
+                continue
+            k = c.end() - 1
+            out[name].append(len([a for a, _ in _split_top(text[k + 1:_match_paren(text, k) - 1]) if a.strip()]))
+    return out
+
+
+def _collectives(text):
+    """the comm_* collectives of a function body in order: (kind, tag of isend / irecv!, which waitall)"""
+    out = []
+    for m in re.finditer(r"comm_(alltoall|isend|irecv!|waitall)\(([^\n]*)", text):
+        kind, rest = m.group(1), m.group(2)
+        if kind in ("isend", "irecv!"):
+            tag = re.search(r",\s*(\d+)\)", rest)
+            out.append((kind, tag.group(1) if tag else None))
+        elif kind == "waitall":
+            out.append((kind, "recv" if "recv" in rest else "send"))
+        else:
+            out.append((kind, None))
+    return out
+
+
+# the header of the reference's VectorPlan constructor (make_julia_reference_api.py stores its collectives)
+REF_VECTORPLAN_HEADER = r"^function VectorPlan\(A::HPCSparseMatrix\{T,Ti,B\}, x::HPCVector\{T,Bx\}\)"
+
+
 def _ext_text():
     return _strip_comments_and_strings(open(EXT).read())
 
 
+# a small Julia text of this file's own, in the shapes the parser must read: one-line and multi-line structs (an inner
+# constructor is not a field), methods with optional, keyword and varargs arguments, a bare stub, one-line definitions
+_PARSER_SAMPLE = """
+abstract type AbstractShape end
+const DEFAULT_WIDTH = 4
+struct Point <: AbstractShape end
+mutable struct Grid{T}
+    cells::Vector{T}
+    width::Int
+    label
+    function Grid{T}(n::Int) where T
+        new{T}(zeros(T, n), n, nothing)
+    end
+end
+function resize_grid!(g::Grid{T}, n, fill=zero(T); keep=true) where T
+    g
+end
+function render end
+area(g) = g.width^2
+Base.show(io::IO, g::Grid, extra...) = print(io, g.label)
+"""
+
+
+def test_reference_parser_reads_a_sample():
+    """The parser that filled tests/golden/julia_reference_api.json, on a sample whose answers are known."""
+    text = _strip_comments_and_strings(_PARSER_SAMPLE)
+    structs = reference_structs(text)
+    assert structs == {"Point": [], "Grid": ["cells", "width", "label"]}, structs
+    funcs = reference_functions(text)
+    assert funcs["resize_grid!"] == [(2, 3)] and funcs["render"] == [] and funcs["area"] == [(1, 1)], funcs
+    assert funcs["show"] == [(2, None)] and funcs["Grid"] == [(1, 1)], funcs
+    assert {"AbstractShape", "DEFAULT_WIDTH", "Point", "Grid", "render"} <= reference_names(text)
+
+
 def test_reference_parser_sees_the_known_landmarks():
     """The regex parser is only trusted if it finds what SURVEY.md section 8 cites by line."""
-    text = _ref_text()
-    structs = reference_structs(text)
+    ref = _reference()
+    structs = ref["structs"]
     assert {"send_rank_ids", "send_indices", "recv_rank_ids", "recv_perm", "local_src_indices", "local_dst_indices",
             "gathered", "gathered_cpu", "result_partition_hash", "result_partition"} <= set(structs["VectorPlan"])
     assert {"row_partition", "col_partition", "col_indices", "rowptr", "colval", "nzval", "nrows_local",
             "ncols_compressed", "rowptr_target", "colval_target", "backend", "cached_transpose"} <= set(structs["HPCSparseMatrix"])
     assert structs["HPCVector"][:4] == ["structural_hash", "partition", "v", "backend"]
-    funcs = reference_functions(text)
+    funcs = ref["functions"]
     assert (2, 2) in funcs["execute_plan!"] and (2, 2) in funcs["_convert_array"] and (2, 2) in funcs["get_vector_plan"]
     assert "backend_cuda_mpi" in funcs                       # the stub pattern the parent patch copies
 
@@ -176,9 +252,9 @@ def test_imported_names_exist_in_the_reference():
     assert m, "no `using HPCLinearAlgebra: ...` list"
     imported = [n.strip() for n in m.group(1).split(",")]
     assert len(imported) >= 12
-    names = reference_names(_ref_text())
+    names = set(_reference()["names"])
     missing = [n for n in imported if n not in names and n not in PARENT_PATCH_NAMES]
-    assert not missing, f"imported from HPCLinearAlgebra but not defined in {REF}/src: {missing}"
+    assert not missing, f"imported from HPCLinearAlgebra but not defined in the reference's src: {missing}"
     integ = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     for n in PARENT_PATCH_NAMES & set(imported):
         assert n in integ, f"{n} must be added by the parent patch shown in INTEGRATION.md"
@@ -186,11 +262,12 @@ def test_imported_names_exist_in_the_reference():
 
 def test_qualified_names_exist_and_extended_methods_have_a_reference_arity():
     ext = _ext_text()
-    text = _ref_text()
-    names = reference_names(text)
-    funcs = reference_functions(text)
+    ref = _reference()
+    names = set(ref["names"])
+    funcs = ref["functions"]
+    stubs = ref["stub_call_arities"]
     problems = []
-    names = names | _third_party_names(text)
+    names = names | set(ref["third_party_names"])
     assert {"Blake3Ctx", "update!", "digest"} <= names, "the reference no longer hashes with Blake3Ctx / update! / digest"
     for m in re.finditer(r"HPCLinearAlgebra\.([\w!]+)", ext):
         n = m.group(1)
@@ -208,23 +285,18 @@ def test_qualified_names_exist_and_extended_methods_have_a_reference_arity():
     for name, (lo, hi), line in extended:
         if name in PARENT_PATCH_NAMES:
             continue                                          # the stubs the parent patch declares (`function f end`)
-        ref = list(funcs.get(name, []))
-        if not ref and name in funcs:
+        arities = list(funcs.get(name, []))
+        if not arities and name in funcs:
             # a bare stub in the parent (`function _array_to_device end`): the contract is the parent's CALL sites
-            for c in re.finditer(r"(?<![\w.!])%s\(" % re.escape(name), text):
-                if text[max(c.start() - 9, 0):c.start()].strip().endswith("function"):
-                    continue
-                k = c.end() - 1
-                n_args = len([a for a, _ in _split_top(text[k + 1:_match_paren(text, k) - 1]) if a.strip()])
-                ref.append((n_args, n_args))
-            if not ref:
+            arities = [(n_args, n_args) for n_args in stubs[name]]
+            if not arities:
                 continue                                      # declared for extensions, never called by the parent: any arity
-        if not ref:
+        if not arities:
             problems.append(f"line {line}: {name} has neither a method nor a stub in the reference")
             continue
-        ok = any((rhi is None or lo <= rhi) and (hi is None or hi >= rlo) for rlo, rhi in ref)
+        ok = any((rhi is None or lo <= rhi) and (hi is None or hi >= rlo) for rlo, rhi in arities)
         if not ok:
-            problems.append(f"line {line}: {name} extended with {lo}..{hi} positional arguments, reference methods take {sorted(set(ref), key=str)}")
+            problems.append(f"line {line}: {name} extended with {lo}..{hi} positional arguments, reference methods take {sorted(set(arities), key=str)}")
     assert not problems, "\n".join(problems)
 
 
@@ -252,7 +324,7 @@ def _chunks(ext):
 
 def test_every_field_read_from_a_parent_struct_exists_there():
     ext = _ext_text()
-    structs = reference_structs(_ref_text())
+    structs = _reference()["structs"]
     for need in ("VectorPlan", "VectorRepartitionPlan", "AdditionPlan", "MatrixPlan", "HPCSparseMatrix", "HPCVector", "HPCMatrix",
                  "HPCBackend", "CommMPI"):
         assert need in structs and structs[need], f"struct {need} not found in the reference"
@@ -397,8 +469,8 @@ def test_vector_plan_constructor_override_builds_the_reference_struct_with_the_r
     Alltoall of the counts, isend / irecv of the requested indices with tag 20, waitall on the receives, waitall on the
     sends -- so that ranks running either method meet in every collective."""
     ext = _ext_text()
-    ref = _ref_text()
-    fields = reference_structs(ref)["VectorPlan"]
+    ref = _reference()
+    fields = ref["structs"]["VectorPlan"]
     assert len(fields) == 18, fields
     body = _function_body(ext, r"^function HPCLinearAlgebra\.VectorPlan\(A::HPCSparseMatrix\{T,Ti,B\}, x::HPCVector\{T,B\}\) where \{T,Ti,B<:ROCBackend\}")
     call = body[body.rindex("VectorPlan{T,Ti,AV}("):]
@@ -407,21 +479,7 @@ def test_vector_plan_constructor_override_builds_the_reference_struct_with_the_r
     assert len(args) == 18, args
     assert args[:12] == fields[:12], (args[:12], fields[:12])
     assert args[12:] == ["nothing"] * 6, args[12:]
-    ref_body = _function_body(ref, r"^function VectorPlan\(A::HPCSparseMatrix\{T,Ti,B\}, x::HPCVector\{T,Bx\}\)")
-
-    def collectives(text):
-        out = []
-        for m in re.finditer(r"comm_(alltoall|isend|irecv!|waitall)\(([^\n]*)", text):
-            kind, rest = m.group(1), m.group(2)
-            if kind in ("isend", "irecv!"):
-                tag = re.search(r",\s*(\d+)\)", rest)
-                out.append((kind, tag.group(1) if tag else None))
-            elif kind == "waitall":
-                out.append((kind, "recv" if "recv" in rest else "send"))
-            else:
-                out.append((kind, None))
-        return out
-    mine, theirs = collectives(body), collectives(ref_body)
+    mine, theirs = _collectives(body), ref["vectorplan_constructor_collectives"]
     assert theirs == [("alltoall", None), ("isend", "20"), ("irecv!", "20"), ("waitall", "recv"), ("waitall", "send")], theirs
     assert mine == theirs, (mine, theirs)
     # the lazily sized buffers: only for Float64, where this file's execute_plan! / mul! never read gathered_cpu
@@ -431,8 +489,7 @@ def test_vector_plan_constructor_override_builds_the_reference_struct_with_the_r
 def test_spmm_result_passes_the_fields_of_hpcmatrix_in_order():
     """`_spmm_result` builds HPCMatrix{T,B} with the inner constructor (src/dense.jl:59-69): five arguments in field order --
     hash (lazy: nothing), row partition, column partition, the local block, the backend."""
-    ref = _ref_text()
-    fields = reference_structs(ref)["HPCMatrix"]
+    fields = _reference()["structs"]["HPCMatrix"]
     assert fields == ["structural_hash", "row_partition", "col_partition", "A", "backend"], fields
     ext = _ext_text()
     m = re.search(r"_spmm_result\(A::HPCSparseMatrix\{T,Ti,B\}, C::ROCMatrix\{T\}, k::Int\) where \{T,Ti,B\} =\s*HPCMatrix\{T,B\}\(", ext)
