@@ -423,6 +423,23 @@ int64_t hpcla_gemv_t_work_bytes(int64_t nrows, int64_t ncols);
 int hpcla_gemv_t_rowmajor_f64(const double *A, int64_t lda, int64_t nrows, int64_t ncols, const double *x,
                               double *y_full, void *work, void *stream);
 
+/* transpose(X) * Y of two dense row-partitioned blocks (Base.:*(At::TransposedHPCMatrix, Bmat::HPCMatrix),
+ * src/dense.jl:1286-1310): C[i*k + j] = sum over the nrows LOCAL rows r of X[r][i] * Y[r][j], C an m x k ROW-major
+ * array of doubles.  X (nrows x m) and Y (nrows x k) are each HPCLA_LAYOUT_ROW (leading dimension >= the width) or
+ * HPCLA_LAYOUT_COL (leading dimension >= nrows).  comm NULL: the local partial only; else C is all-reduced in place
+ * (one m*k sum through RCCL or the peer window) and a rank with nrows == 0 contributes zeros.  Deterministic: fixed
+ * row chunks (a function of nrows, m, k only), one partial tile per chunk, partials summed in a fixed order.  X == Y
+ * (non-NULL) with the same layout, leading dimension and m == k: the block is read once and C is exactly symmetric (a
+ * rank with nrows == 0 reads neither block: it passes one non-NULL pointer for both when the product is X'X, NULL for
+ * both otherwise, so that every rank mirrors the all-reduced C alike).  The f32
+ * form widens on load, forms products and sums in double and returns double C (the caller rounds once, after the
+ * all-reduce).  work: hpcla_gram_work_bytes(nrows, m, k) bytes of device scratch (host-only function, monotone in
+ * nrows).  X and Y aligned to their element size. */
+int64_t hpcla_gram_work_bytes(int64_t nrows, int64_t m, int64_t k);
+int hpcla_gram_f64(hpcla_comm_t *comm, const double *X, int64_t ldx, int x_layout, const double *Y, int64_t ldy,
+                   int y_layout, int64_t nrows, int64_t m, int64_t k, double *C, void *work, void *stream);
+int hpcla_gram_f32(hpcla_comm_t *comm, const float *X, int64_t ldx, int x_layout, const float *Y, int64_t ldy,
+                   int y_layout, int64_t nrows, int64_t m, int64_t k, double *C, void *work, void *stream);
 
 /* ---- gather: replaces _gather_kernel! (src/vectors.jl:174-194) --------------------------------
  * out[dst[i]] = x[src[i]] (dst may be NULL = identity).  The SpMV hot path does not need it (split

@@ -1529,4 +1529,51 @@ function Base.:*(A::HPCMatrix{T,B}, x::HPCVector{T,B}) where {T<:Float64,B<:ROCB
     return HPCVector{T,B}(compute_partition_hash(A.row_partition), A.row_partition, y, A.backend)
 end
 
+# ---- transpose(X) * Y for dense blocks  (replaces src/dense.jl:1286-1310) --------------------------------------------
+# The parent builds the m x k product one column at a time: k products transpose(X) * Y[:, j], each a column copy, a read of
+# all of X and a host all-reduce.  Here ONE hpcla_gram_* call reads the two column-major blocks as they are
+# (HPCLA_LAYOUT_COL, leading dimension = the local row count) and all-reduces the m x k doubles on the device; X === Y reads
+# the block once and gives an exactly symmetric C.  This rank's rows of C (X.col_partition) are copied column-major on the
+# device by hpcla_transpose_f64 (Float32: rounded once, after the all-reduce), and the result is built with the inner
+# constructor as the parent's HPCMatrix_local would describe it (rows = X.col_partition, columns = uniform_partition(k)).
+function _gram(X::HPCMatrix{T,B}, M::HPCMatrix{T,B}) where {T,B<:ROCBackend}
+    assert_backends_compatible(X.backend, M.backend)
+    X.row_partition[end] == M.row_partition[end] ||
+        error("dimension mismatch: transpose(X) has $(X.row_partition[end]) columns, Y has $(M.row_partition[end]) rows")
+    same = X === M
+    X.row_partition == M.row_partition || (M = HPCLinearAlgebra.repartition(M, X.row_partition))   # PCIe: all of Y, both ways, ONLY when the row partitions differ -- the parent's host-staged repartition
+    nloc, m = size(X.A)
+    k = size(M.A, 2)
+    nranks, rank = comm_size(X.backend.comm), comm_rank(X.backend.comm)
+    C = AMDGPU.zeros(Float64, m * k)                  # row-major m x k
+    work = AMDGPU.zeros(UInt8, @ccall LIB.hpcla_gram_work_bytes(nloc::Int64, m::Int64, k::Int64)::Int64)
+    Y = same ? X : M
+    ldx, ldy = max(nloc, 1), max(size(Y.A, 1), 1)
+    # no rows to read: one non-NULL pointer for both says X'X (C is then mirrored like on the other ranks), NULL otherwise
+    xp, yp = nloc == 0 ? (same ? (_ptr(C), _ptr(C)) : (C_NULL, C_NULL)) : (_ptr(X.A), _ptr(Y.A))
+    if T === Float32
+        _check(@ccall(LIB.hpcla_gram_f32(_rccl(X.backend.comm)::Ptr{Cvoid}, xp::Ptr{Cvoid}, ldx::Int64, 1::Cint,
+               yp::Ptr{Cvoid}, ldy::Int64, 1::Cint, nloc::Int64, m::Int64, k::Int64, _ptr(C)::Ptr{Cvoid},
+               _ptr(work)::Ptr{Cvoid}, _stream()::Ptr{Cvoid})::Cint), "hpcla_gram_f32")
+    else
+        _check(@ccall(LIB.hpcla_gram_f64(_rccl(X.backend.comm)::Ptr{Cvoid}, xp::Ptr{Cvoid}, ldx::Int64, 1::Cint,
+               yp::Ptr{Cvoid}, ldy::Int64, 1::Cint, nloc::Int64, m::Int64, k::Int64, _ptr(C)::Ptr{Cvoid},
+               _ptr(work)::Ptr{Cvoid}, _stream()::Ptr{Cvoid})::Cint), "hpcla_gram_f64")
+    end
+    lo, hi = X.col_partition[rank + 1], X.col_partition[rank + 2]
+    own = AMDGPU.zeros(Float64, hi - lo, k)
+    if hi > lo                                        # own rows lo:hi-1 of the row-major C -> column-major
+        _check(@ccall(LIB.hpcla_transpose_f64((_ptr(C) + 8 * (lo - 1) * k)::Ptr{Cvoid}, k::Int64, 0::Cint, _ptr(own)::Ptr{Cvoid},
+               (hi - lo)::Int64, 1::Cint, (hi - lo)::Int64, k::Int64, _stream()::Ptr{Cvoid})::Cint), "hpcla_transpose_f64")
+    end
+    local_C = T === Float64 ? own : T.(own)           # Float32 rounds here, once
+    return HPCMatrix{T,B}(nothing, copy(X.col_partition), HPCLinearAlgebra.uniform_partition(k, nranks), local_C, X.backend)
+end
+function Base.:*(At::Transpose{Float64,HPCMatrix{Float64,B}}, M::HPCMatrix{Float64,B}) where {B<:ROCBackend}
+    return _gram(LinearAlgebra.transpose(At), M)          # the transpose of a lazy transpose is its parent
+end
+function Base.:*(At::Transpose{Float32,HPCMatrix{Float32,B}}, M::HPCMatrix{Float32,B}) where {B<:ROCBackend}
+    return _gram(LinearAlgebra.transpose(At), M)          # the transpose of a lazy transpose is its parent
+end
+
 end # module

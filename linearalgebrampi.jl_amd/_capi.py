@@ -144,6 +144,9 @@ _SIGNATURES = {
     "hpcla_gemv_rowmajor_f64": [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
     "hpcla_gemv_t_work_bytes": [_i64, _i64],
     "hpcla_gemv_t_rowmajor_f64": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
+    "hpcla_gram_work_bytes": [_i64, _i64, _i64],
+    "hpcla_gram_f64": [_vp, _vp, _i64, _i32, _vp, _i64, _i32, _i64, _i64, _i64, _vp, _vp, _vp],
+    "hpcla_gram_f32": [_vp, _vp, _i64, _i32, _vp, _i64, _i32, _i64, _i64, _i64, _vp, _vp, _vp],
     "hpcla_spgemm_bin_cap": [_i32],
     "hpcla_spgemm_ub_i32": [_vp, _vp, _i64, _i32, _vp, _vp, _vp],
     "hpcla_spgemm_ub_i64": [_vp, _vp, _i64, _i32, _vp, _vp, _vp],
@@ -209,6 +212,7 @@ _RESTYPES = {
     "hpcla_poisson3d_nnz": _i64,
     "hpcla_spgemm_bin_cap": _i64,
     "hpcla_gemv_t_work_bytes": _i64,
+    "hpcla_gram_work_bytes": _i64,
     "hpcla_spmm_runs_desc_bytes": _i64,
     "hpcla_spmv_longrows_work_bytes": _i64,
 }

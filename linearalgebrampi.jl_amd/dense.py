@@ -241,6 +241,8 @@ class TransposedHPCMatrix:
         from .vectors import HPCVector
         if isinstance(x, HPCVector):
             return dense_matvec_t(self.parent, x)
+        if isinstance(x, HPCMatrix):
+            return dense_matmat_t(self.parent, x)
         return NotImplemented
 
     __mul__ = __matmul__
@@ -275,6 +277,54 @@ def dense_matvec_t(A: HPCMatrix, x):
     _capi.call("hpcla_allreduce_f64", backend.rccl, dptr(full), ncols, 0, s)
     lo, hi = int(A.col_partition[rank]), int(A.col_partition[rank + 1])
     return HPCVector(compute_partition_hash(A.col_partition), A.col_partition.copy(), full[lo:hi].clone(), backend)
+
+
+def _block_layout(M):
+    """(tensor, leading dimension, layout) of a local block for the C ABI: a row-major view on its own row stride, a
+    column-major view (a transposed tensor) on its column stride, anything else as one contiguous copy."""
+    A = M.A
+    n, w = int(A.shape[0]), int(A.shape[1])
+    if A.stride(1) == 1 and (n <= 1 or A.stride(0) >= w):
+        return A, max(int(A.stride(0)), w), _capi.LAYOUT_ROW
+    if A.stride(0) == 1 and (w <= 1 or A.stride(1) >= n):
+        return A, max(int(A.stride(1)), n), _capi.LAYOUT_COL
+    return A.contiguous(), w, _capi.LAYOUT_ROW
+
+
+def dense_matmat_t(X: HPCMatrix, Y: HPCMatrix) -> HPCMatrix:
+    """``transpose(X) * Y`` of two dense row-partitioned blocks (src/dense.jl:1286-1310), the m x k inner-product matrix
+    of block methods.  The reference runs k column products ``transpose(X) * Y[:, j]`` (X read k times, k host
+    all-reduces); here Y is aligned to ``X.row_partition`` device to device (a no-op when it already is),
+    ``hpcla_gram_*`` forms the whole local m x k product in one pass over both blocks (X read once when ``X is Y``, the
+    result then exactly symmetric) and all-reduces it in double.  The result is an HPCMatrix on ``X.col_partition``
+    rows and ``uniform_partition(k)`` columns; its local block is this rank's rows of the reduced matrix, rounded once
+    to the backend's element type."""
+    from .repartition import repartition_dense
+    from .vectors import sfx_of, torch_dtype_of
+    torch = _torch()
+    assert_backends_compatible(X.backend, Y.backend)
+    backend = X.backend
+    nranks, rank = comm_size(backend.comm), comm_rank(backend.comm)
+    if int(Y.row_partition[-1]) != int(X.row_partition[-1]):
+        raise ValueError(f"dimension mismatch: transpose(X) has {int(X.row_partition[-1])} columns, "
+                         f"Y has {int(Y.row_partition[-1])} rows")
+    same = Y is X
+    if not np.array_equal(Y.row_partition, X.row_partition):
+        Y = repartition_dense(Y, X.row_partition)             # device to device (Float64 backends)
+    nloc, m, k = int(X.A.shape[0]), int(X.A.shape[1]), int(Y.A.shape[1])
+    Xa, ldx, xl = _block_layout(X)
+    Ya, ldy, yl = (Xa, ldx, xl) if same else _block_layout(Y)
+    dev = backend.torch_device
+    C = torch.empty((m, k), dtype=torch.float64, device=dev)
+    work = torch.empty(max(1, _capi.load().hpcla_gram_work_bytes(nloc, m, k) // 8), dtype=torch.float64, device=dev)
+    xp, yp = dptr(Xa), dptr(Ya)
+    if nloc == 0:                 # no rows to read: one non-NULL pointer for both says X'X (C mirrored like on the other ranks)
+        xp = yp = dptr(C) if same else ctypes.c_void_p(0)
+    _capi.call(f"hpcla_gram_{sfx_of(backend)}", backend.rccl, xp, ldx, xl, yp, ldy, yl, nloc, m, k,
+               dptr(C), dptr(work), current_stream_ptr())
+    lo, hi = int(X.col_partition[rank]), int(X.col_partition[rank + 1])
+    loc = C[lo:hi].to(dtype=torch_dtype_of(backend), copy=True)
+    return HPCMatrix(X.col_partition.copy(), uniform_partition(k, nranks), loc, backend)
 
 
 # width-k halo plans hang off the same key as the vector plan, plus k
