@@ -441,6 +441,35 @@ int hpcla_gram_f64(hpcla_comm_t *comm, const double *X, int64_t ldx, int x_layou
 int hpcla_gram_f32(hpcla_comm_t *comm, const float *X, int64_t ldx, int x_layout, const float *Y, int64_t ldy,
                    int y_layout, int64_t nrows, int64_t m, int64_t k, double *C, void *work, void *stream);
 
+/* ---- transposed SpMM: W = A^T X for transpose(X) * A and X * A, A sparse (src/sparse.jl:3617-3690) ------------------
+ * Structure, once per sparse structure: a local CSC of this rank's rows (rowptr, colval: 0-based CSR over ncols columns,
+ * the split column space of the SpMV plan) -- colptr_t (ncols + 1), rowidx_t (nnz: local row, ascending within a column)
+ * and perm (nnz: CSC position -> CSR position), in the index type of the inputs.  Stable device sort: equal columns keep
+ * their stored order.  work: hpcla_spmm_t_struct_work_bytes(nnz, ncols, index_is_i64) bytes of device scratch (host-only
+ * function; -1 on a bad size).
+ * Product: W[c, j] = sum over e in [colptr_t[c], colptr_t[c+1]) of nzval[perm[e]] * X[rowidx_t[e], j], j < m, each one
+ * running sum from 0.0 in ascending e with separate multiply and add -- the bits of the SpMM over the materialised A^T.  X
+ * (the rank's nrows x m block; HPCLA_LAYOUT_ROW is the fast one: one line per entry) and W (ncols x m) each row- or
+ * column-major with their leading dimensions.  nzval is read through perm on every call (a matrix with the same structure
+ * and new values shares the CSC).  No atomics; the result does not depend on timing.
+ * Reverse halo: V[rows[u] * ldv + j] += R[pos[t] * ldr + j] for t in [ptr[u], ptr[u+1]) in list order (int64 lists, u <
+ * n_rows, j < m): the owner's own partial plus the partials its peers sent back, in a fixed order. */
+int64_t hpcla_spmm_t_struct_work_bytes(int64_t nnz, int64_t ncols, int index_is_i64);
+int hpcla_spmm_t_struct_i32(const int32_t *rowptr, const int32_t *colval, int64_t nrows, int64_t nnz, int64_t ncols,
+                            int32_t *colptr_t, int32_t *rowidx_t, int32_t *perm, void *work, int64_t work_bytes,
+                            void *stream);
+int hpcla_spmm_t_struct_i64(const int64_t *rowptr, const int64_t *colval, int64_t nrows, int64_t nnz, int64_t ncols,
+                            int64_t *colptr_t, int64_t *rowidx_t, int64_t *perm, void *work, int64_t work_bytes,
+                            void *stream);
+int hpcla_spmm_t_f64_i32(const int32_t *colptr_t, const int32_t *rowidx_t, const int32_t *perm, const double *nzval,
+                         int64_t ncols, const double *X, int64_t ldx, int x_layout, int64_t m, double *W, int64_t ldw,
+                         int w_layout, void *stream);
+int hpcla_spmm_t_f64_i64(const int64_t *colptr_t, const int64_t *rowidx_t, const int64_t *perm, const double *nzval,
+                         int64_t ncols, const double *X, int64_t ldx, int x_layout, int64_t m, double *W, int64_t ldw,
+                         int w_layout, void *stream);
+int hpcla_spmm_t_accumulate_f64(double *V, int64_t ldv, const double *R, int64_t ldr, const int64_t *rows,
+                                const int64_t *ptr, const int64_t *pos, int64_t n_rows, int64_t m, void *stream);
+
 /* ---- gather: replaces _gather_kernel! (src/vectors.jl:174-194) --------------------------------
  * out[dst[i]] = x[src[i]] (dst may be NULL = identity).  The SpMV hot path does not need it (split
  * column space); used for execute_plan! returning `gathered`, the SpGEMM value gather and the value

@@ -1456,7 +1456,7 @@ function clear_rocm_plan_cache!()
     end
     for rp0 in keys(_spmm_order_in_force); @ccall LIB.hpcla_spmm_block_order_hint(_ptr(rp0)::Ptr{Cvoid}, 0::Cint)::Cint; end
     empty!(_rocm_plans); empty!(_spmm_plans); empty!(_rocm_exec); empty!(_rocm_matexec); empty!(_merge_lists); empty!(_spmm_runs_cache); empty!(_stage32); empty!(_banded_cache); empty!(_spmm_cm_tuned); empty!(_spmm_order_in_force)
-    empty!(_spgemm_cache); empty!(_spgemm_map_lru)
+    empty!(_spgemm_cache); empty!(_spgemm_map_lru); empty!(_spmm_t_plans)
     return nothing
 end
 
@@ -1574,6 +1574,208 @@ function Base.:*(At::Transpose{Float64,HPCMatrix{Float64,B}}, M::HPCMatrix{Float
 end
 function Base.:*(At::Transpose{Float32,HPCMatrix{Float32,B}}, M::HPCMatrix{Float32,B}) where {B<:ROCBackend}
     return _gram(LinearAlgebra.transpose(At), M)          # the transpose of a lazy transpose is its parent
+end
+
+# ---- X * A and transpose(X) * A for a sparse A  (replaces src/sparse.jl:3617-3690) -------------------------------------------
+# The parent loops over the n columns of A: per column a sparse column extraction across ranks, a dense mat-vec with its own
+# all-reduce and a copy of the column to the host -- n distributed operations.  Here ONE transposed SpMM (hpcla_spmm_t_f64_*)
+# forms W = A^T X from this rank's rows of A over the split column space of the SpMV plan for x on A.col_partition; with
+# N > 1 the ghost rows of W are partial sums of other ranks' columns: they go back to their owners
+# (hpcla_exchange_ranges_f64, the plan's lists run backwards) and hpcla_spmm_t_accumulate_f64 adds them in ascending rank
+# order.  The result's rows are then collected with one more range exchange.  Float64 only (Float32 keeps the parent's
+# method).
+const _spmm_t_plans = IdDict{Any,Any}()    # reference plan -> device CSC + reverse lists; freed by clear_rocm_plan_cache!
+
+function _spmm_t_plan(A::HPCSparseMatrix{T,Ti,B}) where {T,Ti,B<:ROCBackend}
+    probe = HPCVector{T,B}(_partition_hash(A.col_partition), A.col_partition, similar(A.nzval, 0), A.backend)   # plan key only
+    plan = get_vector_plan(A, probe)
+    get!(_spmm_t_plans, plan) do
+        rank = comm_rank(A.backend.comm)
+        n_own = A.col_partition[rank + 2] - A.col_partition[rank + 1]
+        # the device half is shared with A * x on this structure: hand it n_own readable values, so that its block-order
+        # measurement runs whichever product builds it first (the values are multiplied and discarded)
+        xz = AMDGPU.zeros(T, max(n_own, 1))
+        d = Base.GC.@preserve xz _device_plan(A, A.col_partition, n_own, n_own > 0 ? _ptr(xz) : C_NULL, plan)
+        Tk = eltype(d.colval_split)
+        nnz = length(A.nzval)
+        seg = Int64.(length.(plan.recv_perm))
+        n_split = n_own + sum(seg; init=0)
+        colptr = ROCVector{Tk}(undef, n_split + 1)
+        rowidx = ROCVector{Tk}(undef, max(nnz, 1))
+        perm = ROCVector{Tk}(undef, max(nnz, 1))
+        wb = @ccall LIB.hpcla_spmm_t_struct_work_bytes(nnz::Int64, n_split::Int64, (Tk === Int64 ? 1 : 0)::Cint)::Int64
+        wb >= 0 || error("hpcla_spmm_t_struct_work_bytes: bad size")
+        work = AMDGPU.zeros(UInt8, max(wb, 1))
+        if Tk === Int64
+            _check(@ccall(LIB.hpcla_spmm_t_struct_i64(_ptr(d.rowptr0)::Ptr{Cvoid}, _ptr(d.colval_split)::Ptr{Cvoid},
+                   A.nrows_local::Int64, nnz::Int64, n_split::Int64, _ptr(colptr)::Ptr{Cvoid}, _ptr(rowidx)::Ptr{Cvoid},
+                   _ptr(perm)::Ptr{Cvoid}, _ptr(work)::Ptr{Cvoid}, wb::Int64, _stream()::Ptr{Cvoid})::Cint), "hpcla_spmm_t_struct_i64")
+        else
+            _check(@ccall(LIB.hpcla_spmm_t_struct_i32(_ptr(d.rowptr0)::Ptr{Cvoid}, _ptr(d.colval_split)::Ptr{Cvoid},
+                   A.nrows_local::Int64, nnz::Int64, n_split::Int64, _ptr(colptr)::Ptr{Cvoid}, _ptr(rowidx)::Ptr{Cvoid},
+                   _ptr(perm)::Ptr{Cvoid}, _ptr(work)::Ptr{Cvoid}, wb::Int64, _stream()::Ptr{Cvoid})::Cint), "hpcla_spmm_t_struct_i32")
+        end
+        # reverse halo: ghost segment i (rows of W) back to recv_rank_ids[i]; received in the forward send_indices order
+        back_off = Int64.(n_own .+ cumsum([0; seg])[1:end-1])
+        from_cnt = Int64.(length.(plan.send_indices))
+        from_off = Int64.(cumsum([0; from_cnt])[1:end-1])
+        rows = Int64.(reduce(vcat, plan.send_indices; init=Ti[]) .- 1)          # 0-based own rows, ascending sender rank
+        order = sortperm(rows; alg=MergeSort)                                    # stable: peers stay in ascending rank
+        urows = unique(rows[order])
+        ptr = Int64[searchsortedfirst(rows[order], r) - 1 for r in urows]
+        acc = isempty(urows) ? nothing :
+              (ROCVector(urows), ROCVector([ptr; length(rows)]), ROCVector(Int64.(order .- 1)), length(urows))
+        AMDGPU.synchronize()
+        (colptr=colptr, rowidx=rowidx, perm=perm, Tk=Tk, n_own=n_own, n_split=n_split,
+         back_ranks=Cint.(plan.recv_rank_ids), back_off=back_off, back_cnt=seg,
+         from_ranks=Cint.(plan.send_rank_ids), from_off=from_off, from_cnt=from_cnt, n_recv=sum(from_cnt; init=0), acc=acc)
+    end
+end
+
+# W = A^T X: X this rank's rows (A.nrows_local x m) read as ROWS (row-major, leading dimension ldx); W row-major (ldw = m)
+function _spmm_t_product!(W::ROCArray{Float64}, A::HPCSparseMatrix{T,Ti,B}, st, xp::Ptr{Cvoid}, ldx::Int, m::Int) where {T,Ti,B}
+    if st.Tk === Int64
+        _check(@ccall(LIB.hpcla_spmm_t_f64_i64(_ptr(st.colptr)::Ptr{Cvoid}, _ptr(st.rowidx)::Ptr{Cvoid}, _ptr(st.perm)::Ptr{Cvoid},
+               _ptr(A.nzval)::Ptr{Cvoid}, st.n_split::Int64, xp::Ptr{Cvoid}, ldx::Int64, 0::Cint, m::Int64,
+               _ptr(W)::Ptr{Cvoid}, max(m, 1)::Int64, 0::Cint, _stream()::Ptr{Cvoid})::Cint), "hpcla_spmm_t_f64_i64")
+    else
+        _check(@ccall(LIB.hpcla_spmm_t_f64_i32(_ptr(st.colptr)::Ptr{Cvoid}, _ptr(st.rowidx)::Ptr{Cvoid}, _ptr(st.perm)::Ptr{Cvoid},
+               _ptr(A.nzval)::Ptr{Cvoid}, st.n_split::Int64, xp::Ptr{Cvoid}, ldx::Int64, 0::Cint, m::Int64,
+               _ptr(W)::Ptr{Cvoid}, max(m, 1)::Int64, 0::Cint, _stream()::Ptr{Cvoid})::Cint), "hpcla_spmm_t_f64_i32")
+    end
+    return W
+end
+
+# one range exchange of doubles on the task's stream (0-based offsets and counts, in units of `width` doubles)
+function _ranges!(comm, src, dst, sr, so, sc, rr, ro, rc, lsrc, ldst, lcnt, width)
+    _check(@ccall(LIB.hpcla_exchange_ranges_f64(_rccl(comm)::Ptr{Cvoid}, _ptr(src)::Ptr{Cvoid}, _ptr(dst)::Ptr{Cvoid},
+           length(sr)::Cint, Cint.(sr)::Ptr{Cint}, Int64.(so)::Ptr{Int64}, Int64.(sc)::Ptr{Int64}, length(rr)::Cint,
+           Cint.(rr)::Ptr{Cint}, Int64.(ro)::Ptr{Int64}, Int64.(rc)::Ptr{Int64}, Int64(lsrc)::Int64, Int64(ldst)::Int64,
+           Int64(lcnt)::Int64, Cint(width)::Cint, _stream()::Ptr{Cvoid})::Cint), "hpcla_exchange_ranges_f64")
+end
+
+# strided block copy on the device: rows x cols, row-major source (ld ls) -> row-major destination (ld ld)
+_place!(src::Ptr{Cvoid}, ls, dst::Ptr{Cvoid}, ld, rows, cols) = rows > 0 && cols > 0 &&
+    _check(@ccall(LIB.hpcla_transpose_f64(src::Ptr{Cvoid}, Int64(ls)::Int64, 0::Cint, dst::Ptr{Cvoid}, Int64(ld)::Int64, 0::Cint,
+           Int64(rows)::Int64, Int64(cols)::Int64, _stream()::Ptr{Cvoid})::Cint), "hpcla_transpose_f64")
+
+# transpose(X) * A for X's rows as ROWS (xp, ldx; aligned with A's rows) -> this rank's rows Q of the m x n product, column-major
+function _spmm_t_result(A::HPCSparseMatrix{T,Ti,B}, Xr::ROCArray{Float64}, ldx::Int, m::Int, Q::Vector{Int}) where {T,Ti,B<:ROCBackend}
+    # (raw pointers of X's rows and of the temporaries below go to queued kernels: every array stays referenced to the end)
+    Base.GC.@preserve Xr _spmm_t_result_preserved(A, Xr, ldx, m, Q)
+end
+function _spmm_t_result_preserved(A::HPCSparseMatrix{T,Ti,B}, Xr::ROCArray{Float64}, ldx::Int, m::Int, Q::Vector{Int}) where {T,Ti,B<:ROCBackend}
+    xp = A.nrows_local > 0 ? _ptr(Xr) : C_NULL
+    comm = A.backend.comm
+    nranks, rank = comm_size(comm), comm_rank(comm)
+    n = A.col_partition[end] - 1
+    st = _spmm_t_plan(A)
+    if nranks == 1                     # W row-major over the (global) columns IS the column-major m x n block
+        C = ROCMatrix{Float64}(undef, m, n)
+        return _spmm_t_product!(C, A, st, xp, ldx, m)
+    end
+    W = ROCVector{Float64}(undef, max(st.n_split * m, 1))
+    R = ROCVector{Float64}(undef, max(st.n_recv * m, 1))
+    send = ROCVector{Float64}(undef, max(st.n_own * m, 1))
+    C = ROCMatrix{Float64}(undef, Q[rank + 2] - Q[rank + 1], n)
+    Base.GC.@preserve W R send C begin
+    _spmm_t_product!(W, A, st, xp, ldx, m)
+    if m > 0
+        _ranges!(comm, W, R, st.back_ranks, st.back_off, st.back_cnt, st.from_ranks, st.from_off, st.from_cnt, 0, 0, 0, m)
+        if st.acc !== nothing
+            rows, ptr, pos, nu = st.acc
+            _check(@ccall(LIB.hpcla_spmm_t_accumulate_f64(_ptr(W)::Ptr{Cvoid}, m::Int64, _ptr(R)::Ptr{Cvoid}, m::Int64,
+                   _ptr(rows)::Ptr{Cvoid}, _ptr(ptr)::Ptr{Cvoid}, _ptr(pos)::Ptr{Cvoid}, nu::Int64, m::Int64,
+                   _stream()::Ptr{Cvoid})::Cint), "hpcla_spmm_t_accumulate_f64")
+        end
+    end
+    # V = W[1:n_own, :] (row-major, rows on A.col_partition): rank r gets V[:, Q_r] row-major, which is the column-major
+    # (q_r x n_own) block at column A.col_partition[rank] of its result -- packed here, received in place
+    P = A.col_partition
+    q_me = Q[rank + 2] - Q[rank + 1]
+    so, sc, sr = Int64[], Int64[], Int[]
+    lsrc = 0
+    for r in 0:nranks-1
+        qr = Q[r + 2] - Q[r + 1]
+        _place!(_ptr(W) + 8 * (Q[r + 1] - 1), m, _ptr(send) + 8 * st.n_own * (Q[r + 1] - 1), qr, st.n_own, qr)
+        r == rank && (lsrc = st.n_own * (Q[r + 1] - 1))
+        r != rank && qr * st.n_own > 0 && (push!(sr, r); push!(so, st.n_own * (Q[r + 1] - 1)); push!(sc, qr * st.n_own))
+    end
+    rr = [q for q in 0:nranks-1 if q != rank && q_me * (P[q + 2] - P[q + 1]) > 0]
+    _ranges!(comm, send, C, sr, so, sc, rr, [q_me * (P[q + 1] - 1) for q in rr], [q_me * (P[q + 2] - P[q + 1]) for q in rr],
+             lsrc, q_me * (P[rank + 1] - 1), q_me * st.n_own, 1)
+    end
+    return C
+end
+
+# a row-major block (width m) on the row partition PX, moved to the row partition PA: one range exchange, device to device
+function _rows_on(comm, rows, PX::Vector{Int}, PA::Vector{Int}, m::Int)
+    PX == PA && return rows
+    nranks, rank = comm_size(comm), comm_rank(comm)
+    out = ROCVector{Float64}(undef, max((PA[rank + 2] - PA[rank + 1]) * m, 1))
+    ov(a, b) = (max(PX[a + 1], PA[b + 1]), min(PX[a + 2], PA[b + 2]))      # rows of X-rank a that A-rank b holds
+    sr = [r for r in 0:nranks-1 if r != rank && ov(rank, r)[2] > ov(rank, r)[1]]
+    rr = [q for q in 0:nranks-1 if q != rank && ov(q, rank)[2] > ov(q, rank)[1]]
+    lo, hi = ov(rank, rank)
+    _ranges!(comm, rows, out, sr, [ov(rank, r)[1] - PX[rank + 1] for r in sr], [ov(rank, r)[2] - ov(rank, r)[1] for r in sr],
+             rr, [ov(q, rank)[1] - PA[rank + 1] for q in rr], [ov(q, rank)[2] - ov(q, rank)[1] for q in rr],
+             max(lo - PX[rank + 1], 0), max(lo - PA[rank + 1], 0), max(hi - lo, 0), m)
+    return out
+end
+
+function _dense_sparse_t(X::HPCMatrix{T,B}, A::HPCSparseMatrix{T,Ti,B}) where {T,Ti,B<:ROCBackend}
+    assert_backends_compatible(X.backend, A.backend)
+    X.row_partition[end] == A.row_partition[end] ||
+        error("dimension mismatch: transpose(X) has $(X.row_partition[end] - 1) columns, A has $(A.row_partition[end] - 1) rows")
+    nloc, m = size(X.A)
+    rows = ROCVector{Float64}(undef, max(nloc * m, 1))          # the column-major block as rows (the kernel's layout)
+    nloc > 0 && m > 0 && _check(@ccall(LIB.hpcla_transpose_f64(_ptr(X.A)::Ptr{Cvoid}, max(nloc, 1)::Int64, 1::Cint,
+           _ptr(rows)::Ptr{Cvoid}, m::Int64, 0::Cint, nloc::Int64, m::Int64, _stream()::Ptr{Cvoid})::Cint), "hpcla_transpose_f64")
+    C = Base.GC.@preserve rows begin
+        aligned = _rows_on(A.backend.comm, rows, X.row_partition, A.row_partition, m)   # X on another row partition: device to device
+        _spmm_t_result(A, aligned, max(m, 1), m, X.col_partition)
+    end
+    return HPCMatrix{T,B}(nothing, copy(X.col_partition),
+                          HPCLinearAlgebra.uniform_partition(A.col_partition[end] - 1, comm_size(A.backend.comm)), C, A.backend)
+end
+
+function _dense_sparse(X::HPCMatrix{T,B}, A::HPCSparseMatrix{T,Ti,B}) where {T,Ti,B<:ROCBackend}
+    assert_backends_compatible(X.backend, A.backend)
+    mloc, p = size(X.A)
+    p == A.row_partition[end] - 1 || error("dimension mismatch: X has $p columns, A has $(A.row_partition[end] - 1) rows")
+    comm = A.backend.comm
+    nranks, rank = comm_size(comm), comm_rank(comm)
+    m = X.row_partition[end] - 1
+    if nranks == 1                     # the column-major m x p block IS transpose(X) as rows (leading dimension m)
+        C = _spmm_t_result(A, X.A, max(m, 1), m, X.row_partition)
+    else
+        # transpose(X) onto A's rows: X's column-major block is (p x mloc) row-major, rank r's rows are one range; the blocks
+        # land side by side as rows of leading dimension m
+        PA, PX = A.row_partition, X.row_partition
+        nloc = A.nrows_local
+        buf = ROCVector{Float64}(undef, max(nloc * m, 1))
+        Xt = ROCVector{Float64}(undef, max(nloc * m, 1))
+        rr = [q for q in 0:nranks-1 if q != rank && nloc * (PX[q + 2] - PX[q + 1]) > 0]
+        sr = [r for r in 0:nranks-1 if r != rank && mloc * (PA[r + 2] - PA[r + 1]) > 0]
+        Base.GC.@preserve buf Xt begin
+        _ranges!(comm, X.A, buf, sr, [mloc * (PA[r + 1] - 1) for r in sr], [mloc * (PA[r + 2] - PA[r + 1]) for r in sr],
+                 rr, [nloc * (PX[q + 1] - 1) for q in rr], [nloc * (PX[q + 2] - PX[q + 1]) for q in rr],
+                 mloc * (PA[rank + 1] - 1), nloc * (PX[rank + 1] - 1), nloc * mloc, 1)
+        for q in 0:nranks-1
+            mq = PX[q + 2] - PX[q + 1]
+            _place!(_ptr(buf) + 8 * nloc * (PX[q + 1] - 1), mq, _ptr(Xt) + 8 * (PX[q + 1] - 1), m, nloc, mq)
+        end
+        end
+        C = _spmm_t_result(A, Xt, max(m, 1), m, X.row_partition)
+    end
+    return HPCMatrix{T,B}(nothing, copy(X.row_partition),
+                          HPCLinearAlgebra.uniform_partition(A.col_partition[end] - 1, nranks), C, A.backend)
+end
+function Base.:*(M::HPCMatrix{Float64,B}, A::HPCSparseMatrix{Float64,Ti,B}) where {Ti,B<:ROCBackend}
+    return _dense_sparse(M, A)
+end
+function Base.:*(Mt::Transpose{Float64,HPCMatrix{Float64,B}}, A::HPCSparseMatrix{Float64,Ti,B}) where {Ti,B<:ROCBackend}
+    return _dense_sparse_t(LinearAlgebra.transpose(Mt), A)     # the transpose of a lazy transpose is its parent
 end
 
 end # module

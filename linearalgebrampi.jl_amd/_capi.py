@@ -147,6 +147,12 @@ _SIGNATURES = {
     "hpcla_gram_work_bytes": [_i64, _i64, _i64],
     "hpcla_gram_f64": [_vp, _vp, _i64, _i32, _vp, _i64, _i32, _i64, _i64, _i64, _vp, _vp, _vp],
     "hpcla_gram_f32": [_vp, _vp, _i64, _i32, _vp, _i64, _i32, _i64, _i64, _i64, _vp, _vp, _vp],
+    "hpcla_spmm_t_struct_work_bytes": [_i64, _i64, _i32],
+    "hpcla_spmm_t_struct_i32": [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp],
+    "hpcla_spmm_t_struct_i64": [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp],
+    "hpcla_spmm_t_f64_i32": [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i64, _vp, _i64, _i32, _vp],
+    "hpcla_spmm_t_f64_i64": [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i64, _vp, _i64, _i32, _vp],
+    "hpcla_spmm_t_accumulate_f64": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp],
     "hpcla_spgemm_bin_cap": [_i32],
     "hpcla_spgemm_ub_i32": [_vp, _vp, _i64, _i32, _vp, _vp, _vp],
     "hpcla_spgemm_ub_i64": [_vp, _vp, _i64, _i32, _vp, _vp, _vp],
@@ -213,6 +219,7 @@ _RESTYPES = {
     "hpcla_spgemm_bin_cap": _i64,
     "hpcla_gemv_t_work_bytes": _i64,
     "hpcla_gram_work_bytes": _i64,
+    "hpcla_spmm_t_struct_work_bytes": _i64,
     "hpcla_spmm_runs_desc_bytes": _i64,
     "hpcla_spmv_longrows_work_bytes": _i64,
 }

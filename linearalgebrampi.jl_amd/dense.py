@@ -48,9 +48,12 @@ class HPCMatrix:
         return int(self.row_partition[-1]), int(self.A.shape[1])
 
     def __matmul__(self, x):
+        from .sparse import HPCSparseMatrix
         from .vectors import HPCVector
         if isinstance(x, HPCVector):
             return dense_matvec(self, x)
+        if isinstance(x, HPCSparseMatrix):
+            return dense_sparse_matmat(self, x)
         return NotImplemented
 
     def __mul__(self, other):
@@ -159,6 +162,7 @@ def clear_dense_plan_cache() -> None:
         if halo:
             _capi.call("hpcla_halo_plan_destroy", halo)
     _dense_vector_plan_cache.clear()
+    _dense_transpose_cache.clear()
 
 
 def _dense_vector_plan(A: HPCMatrix, x):
@@ -238,14 +242,22 @@ class TransposedHPCMatrix:
         return n, m
 
     def __matmul__(self, x):
+        from .sparse import HPCSparseMatrix
         from .vectors import HPCVector
         if isinstance(x, HPCVector):
             return dense_matvec_t(self.parent, x)
         if isinstance(x, HPCMatrix):
             return dense_matmat_t(self.parent, x)
+        if isinstance(x, HPCSparseMatrix):
+            return dense_sparse_matmat_t(self.parent, x)
         return NotImplemented
 
     __mul__ = __matmul__
+
+    def materialize(self) -> HPCMatrix:
+        """``copy(transpose(X))`` (src/dense.jl:978): the n x m transpose as an HPCMatrix with rows on ``X.col_partition``
+        and columns on ``X.row_partition`` (the reference ``DenseTransposePlan``'s partitions), moved device to device."""
+        return _materialize_transpose(self.parent, self.parent.col_partition)
 
 
 def dense_matvec_t(A: HPCMatrix, x):
@@ -327,6 +339,191 @@ def dense_matmat_t(X: HPCMatrix, Y: HPCMatrix) -> HPCMatrix:
     return HPCMatrix(X.col_partition.copy(), uniform_partition(k, nranks), loc, backend)
 
 
+# ---- dense x sparse: transpose(X) * A and X * A (src/sparse.jl:3617-3690) -------------------------------------------------
+_dense_transpose_cache: Dict[tuple, object] = {}
+_spmm_t_cache: Dict[tuple, "SpmmTPlan"] = {}
+
+
+def _tensor_layout(A):
+    """(tensor, leading dimension, layout) of a 2-D device block, as _block_layout."""
+    n, w = int(A.shape[0]), int(A.shape[1])
+    if A.stride(1) == 1 and (n <= 1 or A.stride(0) >= w):
+        return A, max(int(A.stride(0)), w, 1), _capi.LAYOUT_ROW
+    if A.stride(0) == 1 and (w <= 1 or A.stride(1) >= n):
+        return A, max(int(A.stride(1)), n, 1), _capi.LAYOUT_COL
+    return A.contiguous(), max(w, 1), _capi.LAYOUT_ROW
+
+
+def _at(t, offset: int) -> ctypes.c_void_p:
+    """Device pointer ``offset`` doubles into the tensor t."""
+    return ctypes.c_void_p(t.data_ptr() + 8 * int(offset))
+
+
+def _transpose_blocks(M, P, Q, backend):
+    """The transpose of the row-partitioned block matrix whose local rows are ``M`` (n_me x m, any layout; rows on P):
+    this rank's rows ``Q[rank]:Q[rank+1]`` of the m x P[-1] transpose, row-major.  One hpcla_transpose_f64 into the send
+    layout, one hpcla_exchange_ranges_f64, one strided placement per source rank (hpcla_transpose_f64 on row-major
+    blocks); with one rank the first transpose is the result."""
+    from .repartition import exchange_ranges
+    from .transpose import DenseTransposeLists
+    torch = _torch()
+    nranks, rank = comm_size(backend.comm), comm_rank(backend.comm)
+    dev = backend.torch_device
+    n_me, m = int(M.shape[0]), int(M.shape[1])
+    s = current_stream_ptr()
+    Ma, ld, lay = _tensor_layout(M)
+    T = torch.empty((m, n_me), dtype=torch.float64, device=dev)        # this rank's rows, transposed
+    _capi.call("hpcla_transpose_f64", dptr(Ma), ld, lay, dptr(T), max(n_me, 1), _capi.LAYOUT_COL, n_me, m, s)
+    if nranks == 1:
+        return T
+    key = (compute_partition_hash(P), compute_partition_hash(Q), rank)
+    L = _dense_transpose_cache.get(key)
+    if L is None:
+        L = _dense_transpose_cache[key] = DenseTransposeLists(P, Q, rank)
+    buf = torch.empty(max(L.n_buf, 1), dtype=torch.float64, device=dev)
+    exchange_ranges(backend, T, buf, L.send_ranks, L.send_offsets, L.send_counts, L.recv_ranks, L.recv_offsets,
+                    L.recv_counts, L.local_src, L.local_dst, L.local_count, 1)
+    out = torch.empty((L.q_me, L.ncols), dtype=torch.float64, device=dev)
+    for _q, off, n_q, c0 in L.blocks:
+        _capi.call("hpcla_transpose_f64", _at(buf, off), n_q, _capi.LAYOUT_ROW, _at(out, c0), max(L.ncols, 1),
+                   _capi.LAYOUT_ROW, L.q_me, n_q, s)
+    return out
+
+
+def _materialize_transpose(X: HPCMatrix, Q) -> HPCMatrix:
+    """``copy(transpose(X))`` with its rows on the partition Q of X's columns (``X.col_partition`` for the public
+    ``materialize()``; ``A.row_partition`` when X * A needs the transpose aligned with A's rows)."""
+    from .repartition import check_partition
+    from .vectors import f64_only
+    f64_only(X.backend, "copy(transpose(X)) for dense X")
+    Q = check_partition(Q, int(X.A.shape[1]), comm_size(X.backend.comm))
+    local = _transpose_blocks(X.A, X.row_partition, Q, X.backend)
+    return HPCMatrix(Q.copy(), X.row_partition.copy(), local, X.backend)
+
+
+class SpmmTPlan:
+    """Memoised plan of ``transpose(X) * A`` for one sparse structure (key: the structural hash, the column partition and
+    the index type): the host lists of ``transpose.HostSpmmTPlan`` and the device CSC of this rank's rows over the split
+    column space (``hpcla_spmm_t_struct_*``), in Int32 when the plan narrows an Int64 matrix as the SpMV plans do
+    (sparse.can_narrow_indices).  The CSC keeps ``perm``, not values: every call reads the calling matrix's nzval."""
+
+    def __init__(self, A):
+        from .sparse import can_narrow_indices, narrowed_rowptr, narrowing_enabled, split_colval
+        from .transpose import HostSpmmTPlan
+        torch = _torch()
+        backend = A.backend
+        dev = backend.torch_device
+        self.host = h = HostSpmmTPlan(A.col_indices, A.col_partition, backend.comm)
+        a64 = A.Ti == np.dtype(np.int64)
+        narrowed = bool(a64 and narrowing_enabled() and can_narrow_indices(A.nnz, A.nrows_local, h.n_own, h.n_ghost))
+        self.is_i64 = a64 and not narrowed
+        if max(h.ncols_split, A.nnz) > np.iinfo(np.int64 if self.is_i64 else np.int32).max:
+            raise OverflowError("transpose(X)*A: split column space does not fit the index type")
+        sfx = "i64" if self.is_i64 else "i32"
+        tdt = torch.int64 if self.is_i64 else torch.int32
+        colval_split, _ = split_colval(A, h.cmap, to_i32=narrowed)
+        rowptr = narrowed_rowptr(A) if narrowed else A.rowptr_target
+        self.colptr = torch.empty(h.ncols_split + 1, dtype=tdt, device=dev)
+        self.rowidx = torch.empty(max(A.nnz, 1), dtype=tdt, device=dev)
+        self.perm = torch.empty(max(A.nnz, 1), dtype=tdt, device=dev)
+        wb = int(_capi.load().hpcla_spmm_t_struct_work_bytes(A.nnz, h.ncols_split, int(self.is_i64)))
+        if wb < 0:
+            raise _capi.HPCLAError("hpcla_spmm_t_struct_work_bytes", wb, "sort workspace query failed")
+        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
+        _capi.call(f"hpcla_spmm_t_struct_{sfx}", dptr(rowptr), dptr(colval_split), A.nrows_local, A.nnz, h.ncols_split,
+                   dptr(self.colptr), dptr(self.rowidx), dptr(self.perm), dptr(work), wb, current_stream_ptr())
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)
+        self.acc = (up(h.acc_rows), up(h.acc_ptr), up(h.acc_pos)) if len(h.acc_rows) else None
+        del work, colval_split                       # (stream-ordered frees: the build has been queued before them)
+
+
+def _spmm_t_plan(A) -> SpmmTPlan:
+    from .sparse import narrowing_enabled
+    key = (A._ensure_hash(), compute_partition_hash(A.col_partition), str(A.Ti), narrowing_enabled())
+    plan = _spmm_t_cache.get(key)
+    if plan is None:
+        plan = _spmm_t_cache[key] = SpmmTPlan(A)
+    return plan
+
+
+def _spmm_t(Xloc, Q, A) -> HPCMatrix:
+    """``transpose(X) * A`` for X's local rows ``Xloc`` (A.nrows_local x m, any layout) aligned with A's rows: an m x n
+    HPCMatrix with rows on the partition Q of m and columns on ``uniform_partition(n)``.  One rank: the product writes
+    the result block itself (column-major W = the row-major m x n block).  N > 1: W row-major over the split column space,
+    its ghost rows sent back to their owners, the owners' rows completed in ascending rank order
+    (``hpcla_spmm_t_accumulate_f64``), then this rank's rows of the transpose collected (``_transpose_blocks``)."""
+    from .repartition import exchange_ranges
+    torch = _torch()
+    backend = A.backend
+    nranks = comm_size(backend.comm)
+    dev = backend.torch_device
+    nloc, m, n = int(Xloc.shape[0]), int(Xloc.shape[1]), int(A.shape[1])
+    if nloc != A.nrows_local:
+        raise ValueError("transpose(X)*A: X's local rows do not match A's")
+    plan = _spmm_t_plan(A)
+    h = plan.host
+    s = current_stream_ptr()
+    Xa, ldx, xl = _tensor_layout(Xloc)
+    if xl == _capi.LAYOUT_COL and nloc > 0 and m > 0:   # the product reads X as rows: one conversion
+        rows = torch.empty((nloc, m), dtype=torch.float64, device=dev)
+        _capi.call("hpcla_transpose_f64", dptr(Xa), ldx, xl, dptr(rows), m, _capi.LAYOUT_ROW, nloc, m, s)
+        Xa, ldx, xl = rows, m, _capi.LAYOUT_ROW
+    sfx = "i64" if plan.is_i64 else "i32"
+
+    def product(W, ldw, layout):
+        _capi.call(f"hpcla_spmm_t_f64_{sfx}", dptr(plan.colptr), dptr(plan.rowidx), dptr(plan.perm), dptr(A.nzval),
+                   h.ncols_split, dptr(Xa) if nloc else None, ldx, xl, m, dptr(W), ldw, layout, s)
+    if nranks == 1:
+        out = torch.empty((m, n), dtype=torch.float64, device=dev)
+        product(out, max(n, 1), _capi.LAYOUT_COL)
+        return HPCMatrix(np.asarray(Q, dtype=np.int64).copy(), uniform_partition(n, 1), out, backend)
+    W = torch.empty((h.ncols_split, m), dtype=torch.float64, device=dev)
+    product(W, max(m, 1), _capi.LAYOUT_ROW)
+    if m > 0:
+        R = torch.empty((max(h.n_recv, 1), m), dtype=torch.float64, device=dev)
+        exchange_ranges(backend, W, R, h.back_ranks, h.back_offsets, h.back_counts, h.from_ranks, h.from_offsets,
+                        h.from_counts, 0, 0, 0, m)
+        if plan.acc is not None:
+            rows_d, ptr_d, pos_d = plan.acc
+            _capi.call("hpcla_spmm_t_accumulate_f64", dptr(W), m, dptr(R), m, dptr(rows_d), dptr(ptr_d), dptr(pos_d),
+                       int(rows_d.numel()), m, s)
+    local = _transpose_blocks(W[:h.n_own], A.col_partition, Q, backend)
+    return HPCMatrix(np.asarray(Q, dtype=np.int64).copy(), uniform_partition(n, nranks), local, backend)
+
+
+def dense_sparse_matmat_t(X: HPCMatrix, A) -> HPCMatrix:
+    """``transpose(X) * A`` for a dense X (p x m) and a sparse A (p x n) (src/sparse.jl:3660-3690): the m x n product
+    with rows on ``X.col_partition`` (as ``transpose(A) * b`` returns ``A.col_partition``) and columns on
+    ``uniform_partition(n)``.  The reference loops over the n columns of A (a sparse column extraction, a mat-vec with
+    its own all-reduce and a host copy each); here one transposed SpMM over this rank's rows (``hpcla_spmm_t_f64_*``: A^T X
+    from A's own rows, no A^T) plus, with N > 1, the reverse halo.  X on another row partition is aligned with
+    ``repartition_dense`` first."""
+    from .repartition import repartition_dense
+    from .vectors import f64_only
+    f64_only(A.backend, "transpose(X)*A for sparse A")
+    assert_backends_compatible(X.backend, A.backend)
+    if int(X.row_partition[-1]) != int(A.row_partition[-1]):
+        raise ValueError(f"dimension mismatch: transpose(X) has {int(X.row_partition[-1])} columns, "
+                         f"A has {int(A.row_partition[-1])} rows")
+    if not np.array_equal(X.row_partition, A.row_partition):
+        X = repartition_dense(X, A.row_partition)                # device to device
+    return _spmm_t(X.A, X.col_partition, A)
+
+
+def dense_sparse_matmat(X: HPCMatrix, A) -> HPCMatrix:
+    """``X * A`` for a dense X (m x p) and a sparse A (p x n) (src/sparse.jl:3617-3652): the m x n product with rows on
+    ``X.row_partition`` and columns on ``uniform_partition(n)``, computed as ``transpose(transpose(X)) * A`` -- the
+    transpose of X materialised straight onto ``A.row_partition`` (no second repartition pass), then the transposed
+    SpMM."""
+    from .vectors import f64_only
+    f64_only(A.backend, "X*A for sparse A")
+    assert_backends_compatible(X.backend, A.backend)
+    if int(X.A.shape[1]) != int(A.row_partition[-1]):
+        raise ValueError(f"dimension mismatch: X has {int(X.A.shape[1])} columns, A has {int(A.row_partition[-1])} rows")
+    Xt = _materialize_transpose(X, A.row_partition)
+    return _spmm_t(Xt.A, X.row_partition, A)
+
+
 # width-k halo plans hang off the same key as the vector plan, plus k
 _spmm_halo_cache: Dict[tuple, object] = {}
 
@@ -361,6 +558,7 @@ def clear_spmm_cache() -> None:
         if h[0]:
             _capi.call("hpcla_halo_plan_destroy", h[0])
     _spmm_halo_cache.clear()
+    _spmm_t_cache.clear()
 
 
 def spmm_pitch(A, k: int) -> int:

@@ -124,6 +124,83 @@ class TransposePlan:
                                self.colval, out, self.rowptr_dev, A.backend)
 
 
+class HostSpmmTPlan:
+    """Index half of ``transpose(X) * A`` for a sparse A (src/sparse.jl:3660-3690), host numpy: the SpMV plan's lists
+    (``VectorPlan(A, x)`` with x on ``A.col_partition``, src/sparse.jl:1875-1953) run backwards.
+
+    The local product writes one row per column of the SPLIT column space (``split_column_map``): rows ``0 .. n_own-1``
+    are this rank's own columns of A (in ``col_partition`` order, zero where no local row has an entry), rows ``n_own ..``
+    the ghost segments, contiguous per owner in ``recv_rank_ids`` order.  Those are partial sums of other ranks' columns:
+
+    ``back_ranks`` / ``back_offsets`` / ``back_counts``   ghost segment i (rows of W) goes back to its owner
+    ``from_ranks`` / ``from_offsets`` / ``from_counts``   what this rank receives, in its forward ``send_indices`` order
+                                                          (ascending rank), back to back in a buffer of ``n_recv`` rows
+    ``acc_rows`` / ``acc_ptr`` / ``acc_pos``   own row ``acc_rows[u]`` adds the received rows ``acc_pos[acc_ptr[u]:
+                                                acc_ptr[u+1]]`` in that order: own partial + peers in ascending rank"""
+
+    def __init__(self, col_indices, col_partition, comm):
+        from .sparse import build_host_vector_plan, split_column_map
+        h = build_host_vector_plan(col_indices, col_partition, comm)
+        self.host = h
+        self.n_own = h.n_own
+        self.n_ghost = h.n_gathered - len(h.local_dst_indices)
+        self.ncols_split = self.n_own + self.n_ghost
+        self.cmap = split_column_map(h)
+        seg = [len(p) for p in h.recv_perm]
+        self.back_ranks = list(h.recv_rank_ids)
+        self.back_counts = seg
+        self.back_offsets = [self.n_own + int(o) for o in np.concatenate([[0], np.cumsum(seg)])[:len(seg)]]
+        self.from_ranks = list(h.send_rank_ids)
+        self.from_counts = [len(i) for i in h.send_indices]
+        self.from_offsets = [int(o) for o in np.concatenate([[0], np.cumsum(self.from_counts)])[:len(self.from_counts)]]
+        self.n_recv = int(sum(self.from_counts))
+        rows = (np.concatenate(h.send_indices) if h.send_indices else np.zeros(0)).astype(np.int64)
+        order = np.argsort(rows, kind="stable")                 # stable: ascending sender rank within a row
+        self.acc_rows, starts = np.unique(rows[order], return_index=True)
+        self.acc_ptr = np.append(starts, len(order)).astype(np.int64)
+        self.acc_pos = order.astype(np.int64)
+
+
+class DenseTransposeLists:
+    """Block lists of ``copy(transpose(X))`` for a dense row-partitioned block (the reference's ``DenseTransposePlan``,
+    src/dense.jl:978): X has ``P[-1]`` rows on partition P and m columns; its transpose has m rows on partition Q and
+    ``P[-1]`` columns.  This rank transposes its rows into ``T`` (m x n_me, row-major): the rows ``Q[r]:Q[r+1]`` of T are
+    then one contiguous range for rank r.  It receives one (q_me x n_q) block per source rank q into a buffer of ``n_buf``
+    doubles, blocks back to back in ascending q (its own at its rank position), and places block q at column ``P[q]`` of
+    its (q_me x P[-1]) result.  Offsets and counts in doubles."""
+
+    def __init__(self, P, Q, rank: int):
+        P = np.asarray(P, dtype=np.int64)
+        Q = np.asarray(Q, dtype=np.int64)
+        nranks = len(P) - 1
+        n_me, q_me = int(P[rank + 1] - P[rank]), int(Q[rank + 1] - Q[rank])
+        self.n_me, self.q_me, self.ncols = n_me, q_me, int(P[-1])
+        self.send_ranks, self.send_offsets, self.send_counts = [], [], []
+        for r in range(nranks):
+            cnt = int(Q[r + 1] - Q[r]) * n_me
+            if r != rank and cnt > 0:
+                self.send_ranks.append(r)
+                self.send_offsets.append(int(Q[r]) * n_me)
+                self.send_counts.append(cnt)
+        self.blocks = []                                        # (source rank, buffer offset, n_q, result column offset)
+        self.recv_ranks, self.recv_offsets, self.recv_counts = [], [], []
+        self.local_src = self.local_dst = self.local_count = 0
+        off = 0
+        for q in range(nranks):
+            n_q = int(P[q + 1] - P[q])
+            if n_q == 0 or q_me == 0:
+                continue
+            self.blocks.append((q, off, n_q, int(P[q])))
+            if q == rank:
+                self.local_src, self.local_dst, self.local_count = int(Q[rank]) * n_me, off, q_me * n_me
+            else:
+                self.recv_ranks.append(q)
+                self.recv_offsets.append(off)
+                self.recv_counts.append(q_me * n_q)
+            off += q_me * n_q
+        self.n_buf = off
+
+
 _transpose_plan_cache = {}
 
 
