@@ -280,7 +280,7 @@ def _colmajor_cost(hp, A, B, k, b_alg, direct_too=True):
                    "structure whose blocks fit) against transpose + row-major product + transpose; the record's own ms_per_step is "
                    "the row-major host layer"}
     # round 5: the run tiles on the column-major blocks (k = 16, every column owned here, B's columns on the 16-byte grid)
-    from hpcla_amd.dense import _spmm_runs
+    from hpcla_amd.spmm_plans import _spmm_runs
     desc = _spmm_runs(A, plan, rp, cv, plan.is_i64) if k == 16 else None
     if desc is not None and nb % 2 == 0 and Bc.data_ptr() % 16 == 0 and plan.n_own == nb:
         def runs_direct():
@@ -508,7 +508,7 @@ def run_record(args, backend, rank, world, job):
             k15 = 15
             B15 = hp.HPCMatrix_local(Bl[:, :k15].contiguous(), backend)
             C15 = A @ B15                                    # plan build + (first product of a result on the padded pitch)
-            B15p = hp.HPCMatrix(B15.row_partition, B15.col_partition, hp.dense._rows_on_pitch(B15.A, hp.dense.spmm_pitch(A, k15))[:, :k15],
+            B15p = hp.HPCMatrix(B15.row_partition, B15.col_partition, hp.spmm_plans._rows_on_pitch(B15.A, hp.spmm_plans.spmm_pitch(A, k15))[:, :k15],
                                 backend)                     # as a chained product finds it: already on the pitch, no copy
             for _ in range(3):
                 C15 = A @ B15p

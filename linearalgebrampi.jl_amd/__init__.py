@@ -8,7 +8,8 @@ Layout
   partition.py       uniform_partition, structural hashes
   vectors.py         HPCVector, dot, norm, fused updates
   sparse.py          HPCSparseMatrix, VectorPlan (host lists + device plan), A*x, mul!
-  dense.py           HPCMatrix, A*B (SpMM)
+  dense.py           HPCMatrix, dense A*x and transpose(A)*x, transpose(X)*Y, X*A and transpose(X)*A
+  spmm_plans.py      A*B for a sparse A and a dense B (SpMM): exchange entries, sequential and panel orders
   cg.py              fixed-iteration CG harness
   transpose.py matmat.py addition.py repartition.py   the SURVEY 8f "next" rows and their plans
 
@@ -28,9 +29,9 @@ from .sparse import (HPCSparseMatrix, HPCSparseMatrix_from_global, HPCSparseMatr
                      HostVectorPlan, VectorPlan, build_host_vector_plan, cache_sizes,
                      ExchangeTimeout, check_exchange_health,
                      clear_plan_cache, execute_plan, get_vector_plan, mul_, mul_dot_, split_column_map)
-from .dense import (HPCMatrix, HPCMatrix_local, TransposedHPCMatrix, clear_dense_plan_cache, clear_spmm_cache,
-                    dense_matmat_t, dense_matvec, dense_matvec_t, dense_sparse_matmat,
-                    dense_sparse_matmat_t, spmm, spmm_block_order_of, spmm_exchange_bytes, spmm_runs_fit_of)
+from .dense import (HPCMatrix, HPCMatrix_local, TransposedHPCMatrix, clear_dense_plan_cache, dense_matmat_t, dense_matvec,
+                    dense_matvec_t, dense_sparse_matmat, dense_sparse_matmat_t)
+from .spmm_plans import clear_spmm_cache, spmm, spmm_block_order_of, spmm_exchange_bytes, spmm_runs_fit_of
 from .matmat import clear_matrix_plan_cache, get_matrix_plan, spgemm
 from .cg import CGGraphPair, CGWorkspace, cg_fixed_iterations, cg_iterate, cg_setup
 from .convert import to_backend

@@ -16,7 +16,7 @@ from __future__ import annotations
 import ctypes
 import os
 from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -545,6 +545,55 @@ def attach_halo_windows(backend: "HPCBackend", halo, probe=None) -> bool:
             sys.stderr.write(f"hpcla: halo plan stays on RCCL: {why}\n")
         return False
     return mine
+
+
+def create_halo_plan(backend: "HPCBackend", send_ranks: Sequence[int], send_lists: Sequence[np.ndarray], idx_dtype,
+                     recv_ranks: Sequence[int], recv_counts: Sequence[int], width: int, *,
+                     double_buffer: bool = False) -> ctypes.c_void_p:
+    """The one constructor of halo plans (``hpcla_halo_plan_create_ex``): this rank sends its rows ``send_lists[i]``
+    (local row numbers, uploaded as ``idx_dtype``, np.int32 or np.int64) to ``send_ranks[i]`` and receives
+    ``recv_counts[i]`` rows of ``width`` doubles from ``recv_ranks[i]``, back to back in its ghost buffer.  The library
+    copies the indices before it returns (csrc/comm.hip), so the upload is not kept.
+
+    Single-buffered unless ``double_buffer``: a plan driven through halo_begin / halo_end has its consumers take the
+    ghost pointer from the host (``halo_ghost_ptr``, once at plan time), which is a constant of a single-buffered plan
+    only.  The fused SpMV's vector plans alone are double-buffered: that kernel finds the buffer of its exchange itself."""
+    import torch
+    from . import _capi
+    from .vectors import dptr
+    n_send, n_recv = len(send_ranks), len(recv_ranks)
+    c_send_ranks = (ctypes.c_int32 * max(n_send, 1))(*send_ranks)
+    c_send_counts = (ctypes.c_int64 * max(n_send, 1))(*[len(i) for i in send_lists])
+    c_recv_ranks = (ctypes.c_int32 * max(n_recv, 1))(*recv_ranks)
+    c_recv_counts = (ctypes.c_int64 * max(n_recv, 1))(*recv_counts)
+    is_i64 = np.dtype(idx_dtype) == np.dtype(np.int64)
+    send_idx = torch.from_numpy(np.concatenate(send_lists).astype(idx_dtype)).to(backend.torch_device) if n_send else None
+    torch.cuda.current_stream().synchronize()          # the library reads the upload outside the caller's stream
+    halo = ctypes.c_void_p()
+    _capi.call("hpcla_halo_plan_create_ex", ctypes.byref(halo), backend.rccl, n_send, c_send_ranks, c_send_counts,
+               dptr(send_idx), 1 if is_i64 else 0, n_recv, c_recv_ranks, c_recv_counts, int(width),
+               0 if double_buffer else _capi.HALO_SINGLE_BUFFER)
+    return halo
+
+
+def halo_ghost_ptr(halo) -> Tuple[ctypes.c_void_p, int]:
+    """(device pointer of the plan's ghost buffer, ghost rows).  A constant of a single-buffered plan, fetched once at
+    plan time; on a double-buffered plan with attached windows the call waits for the device (include/hpcla_rocm.h)."""
+    from . import _capi
+    ghost, n_ghost = ctypes.c_void_p(), ctypes.c_int64()
+    _capi.call("hpcla_halo_ghost_ptr", halo, ctypes.byref(ghost), ctypes.byref(n_ghost))
+    return ghost, int(n_ghost.value)
+
+
+def halo_timed_out(halo) -> bool:
+    """True if a push-mode exchange of this plan gave up waiting for a neighbour (its results are NaN, the plan is
+    dead); False for no plan.  A synchronising 4-byte read."""
+    from . import _capi
+    if not halo:
+        return False
+    flag = ctypes.c_int(0)
+    _capi.call("hpcla_halo_status", halo, ctypes.byref(flag))
+    return bool(flag.value)
 
 
 def backend_rocm_serial(T=np.float64, Ti=np.int64, device_index: int = 0) -> HPCBackend:

@@ -24,8 +24,8 @@ from typing import Dict, List
 import numpy as np
 
 from . import _capi
-from .backends import (assert_backends_compatible, comm_alltoall_counts, comm_exchange_arrays, comm_rank,
-                       comm_size)
+from .backends import (assert_backends_compatible, comm_alltoall_counts, comm_exchange_arrays, comm_rank, comm_size,
+                       create_halo_plan, halo_ghost_ptr)
 from .partition import owner_of
 from .vectors import current_stream_ptr, dptr
 
@@ -132,17 +132,8 @@ class MatrixPlan:
         self.identity = (not self.has_halo and len(h.local_src) == self.nnz_g and int(h.local_dst_start) == 0 and
                          bool(np.array_equal(h.local_src, np.arange(self.nnz_g, dtype=h.local_src.dtype))))
         if self.has_halo:
-            n_send, n_recv = len(h.send_rank_ids), len(h.recv_rank_ids)
-            send_ranks = (ctypes.c_int32 * max(n_send, 1))(*h.send_rank_ids)
-            send_counts = (ctypes.c_int64 * max(n_send, 1))(*[len(p) for p in h.send_pos])
-            recv_ranks = (ctypes.c_int32 * max(n_recv, 1))(*h.recv_rank_ids)
-            recv_counts = (ctypes.c_int64 * max(n_recv, 1))(*h.recv_counts)
-            self._send_idx = (torch.from_numpy(np.concatenate(h.send_pos).astype(np.int64)).to(dev)
-                              if n_send else None)
-            torch.cuda.current_stream().synchronize()
-            _capi.check("hpcla_halo_plan_create", _capi.load().hpcla_halo_plan_create(
-                ctypes.byref(self.halo), backend.rccl, n_send, send_ranks, send_counts, dptr(self._send_idx), 1,
-                n_recv, recv_ranks, recv_counts, 1))
+            self.halo = create_halo_plan(backend, h.send_rank_ids, h.send_pos, np.int64, h.recv_rank_ids, h.recv_counts, 1)
+            self.ghost, _ = halo_ghost_ptr(self.halo)         # a constant of the single-buffered plan
             self._ident = torch.arange(max(h.recv_counts) if h.recv_counts else 0, dtype=torch.int64, device=dev)
 
     def gather_values(self, B):
@@ -160,13 +151,10 @@ class MatrixPlan:
                        ctypes.c_void_p(g_val.data_ptr() + 8 * h.local_dst_start), len(h.local_src), 0, s)
         if self.has_halo:
             _capi.call("hpcla_halo_end", self.halo, s)
-            ghost = ctypes.c_void_p()
-            ng = ctypes.c_int64()
-            _capi.call("hpcla_halo_ghost_ptr", self.halo, ctypes.byref(ghost), ctypes.byref(ng))
             off = 0
             for cnt, dst in zip(h.recv_counts, h.recv_dst_start):
                 if cnt:
-                    _capi.call("hpcla_gather_f64_i64", ctypes.c_void_p(ghost.value + 8 * off), dptr(self._ident),
+                    _capi.call("hpcla_gather_f64_i64", ctypes.c_void_p(self.ghost.value + 8 * off), dptr(self._ident),
                                None, ctypes.c_void_p(g_val.data_ptr() + 8 * dst), cnt, 0, s)
                 off += cnt
         return g_val

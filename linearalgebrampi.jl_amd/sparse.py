@@ -24,7 +24,7 @@ import numpy as np
 from . import _capi
 from .backends import (CommSerial, HPCBackend, assert_backends_compatible, attach_halo_windows, comm_allgather,
                        comm_alltoall_counts, comm_barrier, comm_exchange_indices, comm_rank, comm_size,
-                       require_device)
+                       create_halo_plan, halo_ghost_ptr, halo_timed_out, require_device)
 from .partition import (compute_partition_hash, compute_structural_hash, owner_of,
                         uniform_partition)
 from .vectors import HPCVector, current_stream_ptr, dptr
@@ -152,7 +152,7 @@ def whole_slice_lists(plan: HostVectorPlan, col_indices: np.ndarray, x_partition
 
 
 def panel_chunk_lists(send_indices, recv_counts, n_chunks: int):
-    """Cut an exchange into ``n_chunks`` chunk-sets for the panel-ordered SpMM (dense.SpmmPanelPlan): every link's list is
+    """Cut an exchange into ``n_chunks`` chunk-sets for the panel-ordered SpMM (spmm_plans.SpmmPanelPlan): every link's list is
     cut at ``floor(c * len / n_chunks)`` on BOTH ends (sender: its index list; receiver: the count it expects), so the
     two ends agree without exchanging anything.  Returns
 
@@ -274,26 +274,15 @@ class VectorPlan:
         # halo plan (RCCL)
         self.halo = ctypes.c_void_p()
         self.n_ghost = n_ghost
-        n_send, n_recv = len(h.send_rank_ids), len(h.recv_rank_ids)
-        send_ranks = (ctypes.c_int32 * max(n_send, 1))(*h.send_rank_ids)
-        send_counts = (ctypes.c_int64 * max(n_send, 1))(*[len(i) for i in h.send_indices])
-        recv_ranks = (ctypes.c_int32 * max(n_recv, 1))(*h.recv_rank_ids)
-        recv_counts = (ctypes.c_int64 * max(n_recv, 1))(*[len(p) for p in h.recv_perm])
-        if n_send:
-            send_idx = torch.from_numpy(np.concatenate(h.send_indices).astype(Tk)).to(dev)
-        else:
-            send_idx = None
-        self.has_halo = (n_send + n_recv) > 0
-        # Float32 plans (csrc/f32.hip) drive the exchange through begin / end with the ghost pointer taken from the host in
-        # between: one ghost buffer, so that the pointer is a constant of the plan
+        self.has_halo = (len(h.send_rank_ids) + len(h.recv_rank_ids)) > 0
+        # Float64 plans are double-buffered: the fused SpMV finds the buffer of its exchange in the kernel.  Float32 plans
+        # (csrc/f32.hip) drive the exchange through begin / end with the ghost pointer taken from the host in between: one
+        # ghost buffer, so that the pointer is a constant of the plan
         self.is_f32 = A.T == np.dtype(np.float32)
         self._stage32 = None
         if self.has_halo:
-            torch.cuda.current_stream().synchronize()
-            _capi.check("hpcla_halo_plan_create_ex", _capi.load().hpcla_halo_plan_create_ex(
-                ctypes.byref(self.halo), backend.rccl, n_send, send_ranks, send_counts,
-                dptr(send_idx), 1 if self.is_i64 else 0, n_recv, recv_ranks, recv_counts, 1,
-                _capi.HALO_SINGLE_BUFFER if self.is_f32 else 0))
+            self.halo = create_halo_plan(backend, h.send_rank_ids, h.send_indices, Tk, h.recv_rank_ids,
+                                         [len(p) for p in h.recv_perm], 1, double_buffer=not self.is_f32)
         # collective (ranks without neighbours take part with an empty descriptor): map the neighbours'
         # ghost windows -> push transport for this plan (csrc/window.hip)
         xp = np.asarray(x.partition, dtype=np.int64)
@@ -313,7 +302,7 @@ class VectorPlan:
             self.boundary = torch.nonzero(flags != 0).flatten().to(torch.int32).contiguous()
             self.n_interior = int(self.interior.numel())
             self.n_boundary = int(self.boundary.numel())
-        self._keep = (cmap_dev, send_idx)
+        self._keep = cmap_dev
         # block order of the SpMV launches over this structure: measured once, here (hpcla_spmv_tune_block_order_*, a few
         # dozen launches into a scratch vector); HPCLA_BLOCK_ORDER=natural skips it, =<G> forces groups of G row blocks
         self.block_group = 1
@@ -361,19 +350,11 @@ class VectorPlan:
         return self._stage32
 
     def ghost_tensor_ptr(self) -> Tuple[ctypes.c_void_p, int]:
-        g = ctypes.c_void_p()
-        n = ctypes.c_int64()
-        if self.has_halo:
-            _capi.call("hpcla_halo_ghost_ptr", self.halo, ctypes.byref(g), ctypes.byref(n))
-        return g, n.value
+        return halo_ghost_ptr(self.halo) if self.has_halo else (ctypes.c_void_p(), 0)
 
     def timed_out(self) -> bool:
         """True if a push-mode exchange of this plan gave up waiting for a neighbour (results invalid)."""
-        if not self.halo:
-            return False
-        flag = ctypes.c_int(0)
-        _capi.call("hpcla_halo_status", self.halo, ctypes.byref(flag))
-        return bool(flag.value)
+        return halo_timed_out(self.halo)
 
     def destroy(self) -> None:
         if self.halo:
@@ -463,23 +444,15 @@ def check_exchange_health(backend=None, always: bool = False) -> None:
     for plan in _vector_plan_cache.values():
         if plan.timed_out():
             bad.append("halo plan of a sparse matrix")
-    from . import dense, matmat
-
-    def _status(handle) -> bool:
-        if not handle:
-            return False
-        flag = ctypes.c_int(0)
-        _capi.call("hpcla_halo_status", handle, ctypes.byref(flag))
-        return bool(flag.value)
-
-    for ent in dense._spmm_halo_cache.values():
-        if _status(ent[0]):
+    from . import matmat, spmm_plans
+    for ent in spmm_plans._spmm_halo_cache.values():
+        if halo_timed_out(ent.halo):
             bad.append("SpMM ghost-row plan")
-    for pp in dense._spmm_panel_cache.values():           # the chained chunk-set plans of the panel-ordered SpMM
-        if any(_status(h) for h in pp.halos):
+    for pp in spmm_plans._spmm_panel_cache.values():      # the chained chunk-set plans of the panel-ordered SpMM
+        if any(halo_timed_out(h) for h in pp.halos):
             bad.append("SpMM chunk-set plan (panel order)")
     for mp in matmat._plan_cache.values():                # sparse x sparse: the value exchange of the gathered rows
-        if _status(getattr(mp, "halo", None)):
+        if halo_timed_out(mp.halo):
             bad.append("MatrixPlan value exchange")
     if bad:
         raise ExchangeTimeout("exchange timed out (" + ", ".join(sorted(set(bad))) + "): a neighbour did not publish its "
@@ -705,7 +678,8 @@ class HPCSparseMatrix:
 
     # -- A * x (src/sparse.jl:2096-2128) and A * B (src/sparse.jl:2391-2413) ---------------------------
     def __matmul__(self, other):
-        from .dense import HPCMatrix, spmm
+        from .dense import HPCMatrix
+        from .spmm_plans import spmm
         if isinstance(other, HPCVector):
             plan = get_vector_plan(self, other)
             y = HPCVector(plan.result_partition_hash, plan.result_partition,

@@ -94,7 +94,7 @@ def main():
         np.testing.assert_array_equal(ext[hp.split_column_map(got)], x[cis[rank]])
 
         if kind == "config5":
-            # SpMM ghost rows (dense._spmm_plan): wishes -> Alltoall -> whole-slice lists, then the width-k exchange over
+            # SpMM ghost rows (spmm_plans._spmm_plan): wishes -> Alltoall -> whole-slice lists, then the width-k exchange over
             # gloo; every needed row of B must sit where the split column map of the SpMM says
             from hpcla_amd.sparse import whole_slice_lists, whole_slice_wishes
             wish = whole_slice_wishes(got, xp, nranks)

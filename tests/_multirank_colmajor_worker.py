@@ -20,7 +20,7 @@ def main():
     import torch
     import torch.distributed as dist
     import hpcla_amd as hp
-    from hpcla_amd import dense
+    from hpcla_amd import spmm_plans
     from hpcla_amd.vectors import current_stream_ptr, dptr
     from oracle import oracle as orc
     capi = hp._capi
@@ -50,12 +50,11 @@ def main():
                 Bgs = [orc.fill_uniform(0, ng * k, seed).reshape(ng, k).astype(T) - T(0.25) for seed in (4711, 1234)]
                 # the host layer's plan for (A, row partition of B, k): halo handle, split columns, ghost segment
                 probe = hp.HPCMatrix_local(torch.from_numpy(np.ascontiguousarray(Bgs[0][lo:hi])).cuda(), backend)
-                plan, ent = dense._spmm_plan(A, probe, width=k)      # (column-major blocks: the exchange carries exactly k values per row)
-                assert ent is not None and ent[0] is not None, f"{tag} {name}: no exchange entry"
-                halo, _i, _b, _s, colval_split, ghost = ent[:6]
-                is64 = bool(ent[10])
-                sfx = "i64" if is64 else "i32"
-                rowptr = dense._entry_rowptr(A, plan, is64)
+                plan, ent = spmm_plans._spmm_plan(A, probe, width=k)      # (column-major blocks: the exchange carries exactly k values per row)
+                assert ent is not None and ent.halo is not None, f"{tag} {name}: no exchange entry"
+                halo, colval_split, ghost = ent.halo, ent.colval_split, ent.ghost
+                sfx = "i64" if ent.is_i64 else "i32"
+                rowptr = ent.rowptr(A, plan)
                 # 256-row blocks: with / without ghost columns
                 nblk = (A.nrows_local + rpb - 1) // rpb
                 flags = torch.zeros(max(nblk, 1), dtype=torch.int32, device="cuda")

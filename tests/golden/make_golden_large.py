@@ -54,17 +54,17 @@ def laplacian_2d_sparse(n):
     for b in range(g):               # kron(I_g, L1D): block b, inner index a; kron(L1D, I_g): couples blocks b +- 1
         for a in range(g):
             i = b * g + a
-            ent = {}
-            ent[i] = 2.0 + 2.0       # kron(I, L1D)[i, i] + kron(L1D, I)[i, i]: one fp64 addition
+            entries = {}
+            entries[i] = 2.0 + 2.0       # kron(I, L1D)[i, i] + kron(L1D, I)[i, i]: one fp64 addition
             if a > 0:
-                ent[i - 1] = -1.0
+                entries[i - 1] = -1.0
             if a < g - 1:
-                ent[i + 1] = -1.0
+                entries[i + 1] = -1.0
             if b > 0:
-                ent[i - g] = -1.0
+                entries[i - g] = -1.0
             if b < g - 1:
-                ent[i + g] = -1.0
-            rows.append(sorted(ent.items()))
+                entries[i + g] = -1.0
+            rows.append(sorted(entries.items()))
     return g * g, rows
 
 
@@ -82,11 +82,11 @@ def generate_sparse(n, nnz_per_row=10):
             A[i][perm[t]] = math.sqrt(-2.0 * math.log(1.0 - u1)) * math.cos(2.0 * math.pi * u2)     # randn()
     rows = []
     for i in range(n):                                        # A + A'
-        ent = dict(A[i])
+        entries = dict(A[i])
         for j in range(n):
             if i in A[j]:
-                ent[j] = (ent[j] + A[j][i]) if j in ent else A[j][i]       # one fp64 add where both are stored
-        rows.append(sorted(ent.items()))
+                entries[j] = (entries[j] + A[j][i]) if j in entries else A[j][i]       # one fp64 add where both are stored
+        rows.append(sorted(entries.items()))
     return n, rows
 
 

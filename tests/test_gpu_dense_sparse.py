@@ -136,7 +136,7 @@ def test_integer_inputs_bit_equal_every_layout_and_index_type(hp, monkeypatch, l
 
 
 def test_integer_inputs_padded_pitch_block_of_an_spmm(hp):
-    """X = A1 * B with an odd width: the (rows, k) view of a (rows, k + 1) buffer (dense.spmm_pitch)."""
+    """X = A1 * B with an odd width: the (rows, k) view of a (rows, k + 1) buffer (spmm_plans.spmm_pitch)."""
     backend = hp.backend_rocm_serial(np.float64, np.int32)
     rng = np.random.default_rng(3)
     p, n, k = 1500, 900, 15

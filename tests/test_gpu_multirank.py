@@ -18,6 +18,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WORKER = os.path.join(ROOT, "tests", "_multirank_gpu_worker.py")
+RCCL_PLANS_WORKER = os.path.join(ROOT, "tests", "_multirank_rccl_plans_worker.py")
 
 pytestmark = pytest.mark.gpu
 
@@ -89,6 +90,17 @@ def test_rccl_transport_two_gpus(mode):
     if _device_count() < 2:
         pytest.skip("RCCL needs one GPU per rank (this box has fewer than 2)")
     assert _spawn(2, {"HPCLA_HALO_MODE": mode}) == 0
+
+
+@pytest.mark.parametrize("nranks", [2, 3])
+def test_rccl_plans_across_ranks(nranks):
+    """Dense A*x and the value exchange of sparse A * sparse B at N > 1: single-buffered halo plans that are never attached
+    to the peer windows, so RCCL carries them and each rank needs a GPU of its own (tests/_multirank_rccl_plans_worker.py)."""
+    if _device_count() < nranks:
+        pytest.skip(f"RCCL needs one GPU per rank ({nranks} ranks)")
+    from hpcla_amd.launch import spawn_ranks
+    assert spawn_ranks([RCCL_PLANS_WORKER], nranks, env_extra={"HPCLA_PUSH_TIMEOUT_S": "30"}, timeout=300,
+                       forward_rank0_stdout=False) == 0
 
 
 def test_push_transport_two_gpus_explicit_mode():

@@ -792,7 +792,7 @@ def test_spmm_bit_exact_padded_pitch(hp, orc, gpu_backend_i32, k, c_layout, Ti):
 
 @pytest.mark.parametrize("k", [3, 7, 15, 17])
 def test_spmm_host_layer_odd_k_runs_on_the_padded_pitch(hp, orc, gpu_backend_i32, k):
-    """Round 6, host layer: ``A @ B`` with an odd k allocates its result on the even pitch k + 1 (dense.spmm_pitch) and
+    """Round 6, host layer: ``A @ B`` with an odd k allocates its result on the even pitch k + 1 (spmm_plans.spmm_pitch) and
     multiplies B on that pitch too -- one copy for a B that arrives on the pitch k, none for a B that is itself such a
     result (the chained product below).  Bits of the oracle's column loop (src/sparse.jl:2391-2413) both times."""
     import torch

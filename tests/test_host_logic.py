@@ -419,26 +419,57 @@ def test_element_type_of_a_backend_and_what_float32_covers(hp):
 
 
 def test_spmm_pitch_and_rows_on_pitch(hp, monkeypatch):
-    """Round 6: odd k runs on the even row pitch k + 1 (dense.spmm_pitch, dense._rows_on_pitch) -- host logic, CPU tensors:
+    """Round 6: odd k runs on the even row pitch k + 1 (spmm_plans.spmm_pitch, spmm_plans._rows_on_pitch) -- host logic, CPU tensors:
     the pitch is a function of (element type, k, order) only (every rank computes the same exchange width); a block that
     already sits on the pitch is taken as it is, any other is copied once; the padding is never part of the block."""
     import types
     import torch
-    dense = hp.dense
+    spmm_plans = hp.spmm_plans
     A64 = types.SimpleNamespace(T=np.dtype(np.float64))
     A32 = types.SimpleNamespace(T=np.dtype(np.float32))
     monkeypatch.delenv("HPCLA_SPMM_ORDER", raising=False)
-    assert [dense.spmm_pitch(A64, k) for k in (0, 1, 2, 3, 4, 5, 15, 16, 17)] == [0, 1, 2, 4, 4, 6, 16, 16, 18]
-    assert [dense.spmm_pitch(A32, k) for k in (1, 3, 15)] == [1, 3, 15]            # Float32 kernels keep the pitch k
+    assert [spmm_plans.spmm_pitch(A64, k) for k in (0, 1, 2, 3, 4, 5, 15, 16, 17)] == [0, 1, 2, 4, 4, 6, 16, 16, 18]
+    assert [spmm_plans.spmm_pitch(A32, k) for k in (1, 3, 15)] == [1, 3, 15]            # Float32 kernels keep the pitch k
     monkeypatch.setenv("HPCLA_SPMM_ORDER", "panel")
-    assert dense.spmm_pitch(A64, 15) == 15                                        # the panel order keeps the pitch k
+    assert spmm_plans.spmm_pitch(A64, 15) == 15                                        # the panel order keeps the pitch k
     monkeypatch.delenv("HPCLA_SPMM_ORDER")
     M = torch.arange(35, dtype=torch.float64).reshape(7, 5)
-    P = dense._rows_on_pitch(M, 6)
+    P = spmm_plans._rows_on_pitch(M, 6)
     assert tuple(P.shape) == (7, 6) and P.stride(0) == 6 and torch.equal(P[:, :5], M)
     V = P[:, :5]                                                                   # a result as spmm() hands it out
-    assert dense._rows_on_pitch(V, 6).data_ptr() == V.data_ptr()                   # already on the pitch: no copy
-    assert dense._rows_on_pitch(V, 5).is_contiguous() and torch.equal(dense._rows_on_pitch(V, 5), M)
-    E = dense._rows_on_pitch(torch.empty((0, 5), dtype=torch.float64), 6)
+    assert spmm_plans._rows_on_pitch(V, 6).data_ptr() == V.data_ptr()                   # already on the pitch: no copy
+    assert spmm_plans._rows_on_pitch(V, 5).is_contiguous() and torch.equal(spmm_plans._rows_on_pitch(V, 5), M)
+    E = spmm_plans._rows_on_pitch(torch.empty((0, 5), dtype=torch.float64), 6)
     assert tuple(E.shape) == (0, 6)
+
+
+def test_halo_plans_have_one_constructor(hp):
+    """backends.create_halo_plan is the one place a halo plan is made: the library's plan-creation, ghost-pointer and
+    status entries are named in backends.py alone (_capi.py binds them), only the fused SpMV's VectorPlan asks for a
+    double-buffered plan, and the SpMM's exchange entry is a record with named fields that nothing indexes by position."""
+    import ast
+    import dataclasses
+    entries = re.compile(r"\bhpcla_halo_(?:plan_create(?:_ex)?|ghost_ptr|status)\b")
+    named, double_buffered = {}, []
+
+    def find_double_buffer(node, owner, fn):
+        for child in ast.iter_child_nodes(node):
+            if isinstance(child, ast.Call) and any(kw.arg == "double_buffer" for kw in child.keywords):
+                double_buffered.append((fn, owner))
+            find_double_buffer(child, child.name if isinstance(child, ast.ClassDef) else owner, fn)
+
+    pkg = os.path.join(ROOT, "linearalgebrampi.jl_amd")
+    for fn in sorted(os.listdir(pkg)):
+        if not fn.endswith(".py"):
+            continue
+        src = open(os.path.join(pkg, fn)).read()
+        if fn != "_capi.py" and entries.search(src):
+            named[fn] = sorted(set(entries.findall(src)))
+        find_double_buffer(ast.parse(src), None, fn)
+        assert not re.search(r"\bent\[", src), f"{fn}: an SpMM exchange entry indexed by position"
+    assert named == {"backends.py": ["hpcla_halo_ghost_ptr", "hpcla_halo_plan_create_ex", "hpcla_halo_status"]}, named
+    assert double_buffered == [("sparse.py", "VectorPlan")], double_buffered
+    SpmmExchange = hp.spmm_plans.SpmmExchange
+    assert dataclasses.is_dataclass(SpmmExchange) and not issubclass(SpmmExchange, tuple)
+    assert not hasattr(SpmmExchange, "__getitem__") and not hasattr(SpmmExchange, "__iter__")
 
