@@ -668,6 +668,51 @@ int hpcla_spmv_dist_dot_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, con
                                 const int32_t *boundary_blocks, int64_t n_boundary,
                                 double *dot_out_dev, void *work, void *stream);
 
+/* ---- 16-bit block-relative columns: the plan's own narrow copy of the column stream (no reference counterpart: the
+ * reference streams colval as stored, src/sparse.jl:2055-2066) ---------------------------------------------------------
+ * colval_split is a plan-time copy keyed by the STRUCTURE (src/sparse.jl:1875-1984 builds it once per (A, x.partition)),
+ * so the library may store it in any width that holds it -- the step that narrows Int64 to Int32 above, taken once more.
+ * For every row block of hpcla_spmv_rows_per_block() = 256 rows whose columns are all owned (< n_own) and lie within
+ * [r0 - 32768, r0 + 32767] of the block's first row r0, cols16[j] = colval_split[j] - index_base - r0 as int16: the SpMV
+ * then streams 10 instead of 12 bytes per stored entry (2-D 5-point 4096^2: 1.342 GB -> 1.174 GB per product), nzval is
+ * read LIVE from the caller's array on every call (unlike the packed copy below, nothing of the values is kept), and y
+ * has the same bits: indices are never results.  Cost: 2 bytes of device memory per stored entry and plan.
+ *   padded_len: entries the copy must hold for nnz stored entries (a whole number of 8-entry vectors plus one, so that
+ *               every aligned 16-byte load of the kernel stays inside the allocation); the buffer must be 16-byte aligned.
+ *   encode:     fills the copy for the listed row blocks (block_list == NULL: all; a plan with neighbours lists its
+ *               INTERIOR blocks), zeroes every other entry and the pad, and leaves *ineligible_dev (device int) != 0 when
+ *               a listed block has a ghost column or a column outside the window: the copy is then not to be used.
+ *   spmv_cols16:           y = A*x over the listed (or all) row blocks, every one of which must have been encoded.
+ *   spmv_dist_cols16 / spmv_dist_dot_cols16: hpcla_spmv_dist_f64_i32 / hpcla_spmv_dist_dot_f64_i32 with the interior blocks
+ *               (no neighbours: all blocks) through the narrow kernel and the boundary blocks through the Int32 kernel;
+ *               a contiguous interior run is addressed by its base.  Under the push transport the step is push kernel,
+ *               interior launch, waiting boundary launch instead of one fused grid.  cols16 == NULL, a copy that is not
+ *               16-byte aligned or nzval that is not 32-byte aligned: exactly the Int32 entry points.
+ *   tune_block_order_cols16: hpcla_spmv_tune_block_order_f64_i32 timing the NARROW kernel, the form such a plan launches,
+ *               over all blocks (block_base < 0) or over the contiguous run of n_blocks encoded blocks from block_base.
+ * Int32 plans (narrowed Int64 plans included), Float64. */
+int64_t hpcla_cols16_padded_len(int64_t nnz);
+int hpcla_cols16_encode_i32(const int32_t *rowptr, const int32_t *colval_split, int64_t nrows, int64_t nnz, int64_t n_own,
+                            int index_base, const int32_t *block_list, int64_t n_blocks, int16_t *cols16,
+                            int *ineligible_dev, void *stream);
+int hpcla_spmv_cols16_f64_i32(const int32_t *rowptr, const int16_t *cols16, const double *nzval, const double *x, double *y,
+                              int64_t nrows, int64_t nnz, int index_base, const int32_t *block_list, int64_t n_blocks,
+                              void *stream);
+int hpcla_spmv_dist_cols16_f64_i32(hpcla_halo_plan_t *plan, const int32_t *rowptr, const int32_t *colval_split,
+                                   const int16_t *cols16, const double *nzval, const double *x, int64_t n_own, double *y,
+                                   int64_t nrows, int64_t nnz, int index_base, const int32_t *interior_blocks,
+                                   int64_t n_interior, const int32_t *boundary_blocks, int64_t n_boundary, void *stream);
+int hpcla_spmv_dist_dot_cols16_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int32_t *rowptr,
+                                       const int32_t *colval_split, const int16_t *cols16, const double *nzval,
+                                       const double *x, int64_t n_own, double *y, int64_t nrows, int64_t nnz,
+                                       int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                       const int32_t *boundary_blocks, int64_t n_boundary, double *dot_out_dev,
+                                       void *work, void *stream);
+int hpcla_spmv_tune_block_order_cols16_f64_i32(const int32_t *rowptr, const int16_t *cols16, const double *nzval,
+                                               const double *x_own, double *y_scratch, int64_t nrows, int64_t nnz,
+                                               int index_base, int64_t block_base, int64_t n_blocks, void *stream,
+                                               int *chosen_group);
+
 /* ---- OPT-IN packed copy of the matrix for SpMV (no reference counterpart) ----------------------------
  * For matrices with <= 256 distinct values whose row blocks reach only columns within +-32 K of the
  * block's first row (stencils, graph Laplacians ...), a plan-time copy with 16-bit block-relative

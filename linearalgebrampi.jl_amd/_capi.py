@@ -56,6 +56,10 @@ _SIGNATURES = {
     "hpcla_spmv_block_order_hint": [_vp, _i32],
     "hpcla_spmv_tune_block_order_f64_i32": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp],
     "hpcla_spmv_tune_block_order_f64_i64": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp],
+    "hpcla_spmv_tune_block_order_cols16_f64_i32": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i64, _i64, _vp, _vp],
+    "hpcla_cols16_padded_len": [_i64],
+    "hpcla_cols16_encode_i32": [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp],
+    "hpcla_spmv_cols16_f64_i32": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp],
     "hpcla_spmm_rows_per_block": [],
     "hpcla_spmm_runs_desc_bytes": [_i64],
     "hpcla_spmm_runs_build_i32": [_vp, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp],
@@ -122,6 +126,9 @@ _SIGNATURES = {
     "hpcla_halo_end": [_vp, _vp],
     "hpcla_spmv_dist_f64_i32": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp],
     "hpcla_spmv_dist_f64_i64": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp],
+    "hpcla_spmv_dist_cols16_f64_i32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp],
+    "hpcla_spmv_dist_dot_cols16_f64_i32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
+                                           _vp, _vp, _vp],
     "hpcla_spmv_dot_work_bytes": [_i64],
     "hpcla_spmv_dist_dot_f64_i32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
     "hpcla_spmv_dist_dot_f64_i64": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
@@ -222,6 +229,7 @@ _RESTYPES = {
     "hpcla_spmm_t_struct_work_bytes": _i64,
     "hpcla_spmm_runs_desc_bytes": _i64,
     "hpcla_spmv_longrows_work_bytes": _i64,
+    "hpcla_cols16_padded_len": _i64,
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -34,6 +34,11 @@ int spmv_split_i32(const int32_t *, const int32_t *, const double *, const doubl
 int spmv_split_i64(const int64_t *, const int64_t *, const double *, const double *, const double *,
                    int64_t, double *, int64_t, int64_t, int, const int32_t *, int64_t, void *,
                    double *, int64_t);
+// 16-bit block-relative column copy of a plan (spmv.hip): the row-gather kernel over a list or a contiguous run of row blocks
+// whose columns are all owned and inside the int16 window
+int spmv_cols16_i32(const int32_t *, const int16_t *, const double *, const double *, double *, int64_t, int64_t, int,
+                    const int32_t *, int64_t, void *, double *, int64_t);
+bool cols16_usable(const int16_t *cols16, const double *nzval);
 int spmv_fused_i32(const int32_t *, const int32_t *, const double *, const double *, const double *, int64_t,
                    double *, int64_t, int64_t, int, const int32_t *, int64_t, int64_t, const int32_t *, int64_t,
                    const HaloWait &, const PushArgs &, void *, double *);
@@ -771,11 +776,32 @@ static int spmv_dist_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, const
                           const double *nzval, const double *x, int64_t n_own, double *y,
                           int64_t nrows, int64_t nnz, int index_base, const int32_t *interior,
                           int64_t n_interior, const int32_t *boundary, int64_t n_boundary,
-                          void *stream, double *dot_partial = nullptr)
+                          void *stream, double *dot_partial = nullptr, const int16_t *cols16 = nullptr)
 {
+    // cols16 != null (Int32 plans only): the plan's 16-bit block-relative copy of the columns of its INTERIOR blocks (plans
+    // without neighbours: of every block).  Those blocks then go through the narrow form of the row-gather kernel
+    // (spmv_cols16_i32: 10 instead of 12 bytes per stored entry, the same bits); boundary blocks keep the Int32 kernel.
+    const bool narrow = sizeof(I) == 4 && cols16_usable(cols16, nzval);
+    // the interior blocks in the narrow form on `st`: a contiguous run by its BASE (never through the list: probe_interior)
+    auto interior_narrow = [&](void *st) -> int {
+        if constexpr (sizeof(I) == 4) {
+            if (n_interior <= 0) return HPCLA_OK;
+            if (int rcq = probe_interior(plan, interior, n_interior)) return rcq;
+            if (plan->probed_contig)
+                return spmv_cols16_i32(rowptr, cols16, nzval, x, y, nrows, nnz, index_base, nullptr, n_interior, st, dot_partial,
+                                       plan->probed_first);
+            return spmv_cols16_i32(rowptr, cols16, nzval, x, y, nrows, nnz, index_base, interior, n_interior, st, dot_partial, -1);
+        } else {
+            (void)st;
+            return set_error(HPCLA_ERR_INVALID, "spmv_dist: 16-bit columns need an Int32 plan");
+        }
+    };
     const bool has_halo = plan && !(plan->send_ranks.empty() && plan->recv_ranks.empty());
     if (!has_halo) {
         // no neighbours: every column is owned; one launch over all row blocks
+        if constexpr (sizeof(I) == 4)
+            if (narrow)
+                return spmv_cols16_i32(rowptr, cols16, nzval, x, y, nrows, nnz, index_base, nullptr, 0, stream, dot_partial, -1);
         return split_fn(rowptr, colval, nzval, x, plan ? plan->ghost : nullptr, n_own, y, nrows,
                         nnz, index_base, nullptr, 0, stream, dot_partial, -1);
     }
@@ -804,6 +830,32 @@ static int spmv_dist_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, const
             int rcq = probe_interior(plan, interior, n_interior);
             if (rcq) return rcq;
         }
+        if (narrow) {
+            //  ... with a 16-bit column copy: the push in a kernel of its own, the interior blocks in a plain launch of the
+            //  narrow kernel, then the boundary blocks through the waiting form of the Int32 kernel with no interior part
+            //  (the ordering of hpcla_spmv_dist_packed_f64_i32).  Both column widths in one kernel body would cost the
+            //  stencil path registers at the 64-VGPR edge; two more launches on one stream buy 2 B per interior entry.
+            //  Everything that can be refused is checked BEFORE the exchange is posted: push_post commits the step's readers.
+            const int64_t all_blocks = (nrows + hpcla_spmv_rows_per_block() - 1) / hpcla_spmv_rows_per_block();
+            if (nrows < 0 || nnz < 0 || (index_base != 0 && index_base != 1))
+                return set_error(HPCLA_ERR_INVALID, "spmv_dist: bad size or index_base");
+            if (n_interior < 0 || n_boundary < 0 || n_interior + n_boundary > all_blocks)
+                return set_error(HPCLA_ERR_INVALID, "spmv_dist: block counts out of range");
+            if (!rowptr || !y || (nnz > 0 && (!colval || !nzval || !x)))
+                return set_error(HPCLA_ERR_INVALID, "spmv_dist: null array");
+            int rcn = push_post(plan, x, n_boundary, stream);
+            if (rcn) return rcn;
+            rcn = interior_narrow(stream);
+            if (rcn) { (void)push_abandon_waiters(plan, n_boundary, stream); return rcn; }   // the posted readers still release
+            if (n_boundary > 0) {
+                PushArgs nopush;
+                memset(&nopush, 0, sizeof(nopush));
+                rcn = fused_fn(rowptr, colval, nzval, x, plan->ghost, n_own, y, nrows, nnz, index_base, nullptr, 0, 0, boundary,
+                               n_boundary, push_wait_args(plan, n_boundary), nopush, stream, dot_partial);
+                if (rcn) { (void)push_abandon_waiters(plan, n_boundary, stream); return rcn; }
+            }
+            return HPCLA_OK;
+        }
         PushArgs pa;
         int rcp;
         const bool own_push_kernel = (plan->idx_is_i64 != 0) != (sizeof(I) == 8);
@@ -827,6 +879,12 @@ static int spmv_dist_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, const
     if (mode == HALO_SERIAL) {
         int rc0 = halo_post(plan, x, stream, false, true);
         if (rc0) return rc0;
+        if (narrow) {      // same stream: the interior blocks narrow, then the boundary blocks (ghost columns) on Int32 columns
+            rc0 = interior_narrow(stream);
+            if (rc0 || n_boundary <= 0) return rc0;
+            return split_fn(rowptr, colval, nzval, x, plan->ghost, n_own, y, nrows, nnz, index_base, boundary, n_boundary,
+                            stream, dot_partial, -1);
+        }
         return split_fn(rowptr, colval, nzval, x, plan->ghost, n_own, y, nrows, nnz, index_base, nullptr, 0,
                         stream, dot_partial, -1);
     }
@@ -845,7 +903,10 @@ static int spmv_dist_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, const
         if (rc) return join_and_fail(rc);
     }
     HPCLA_CHECK_HIP(hipEventRecord(plan->ev_done, plan->side));
-    if (n_interior > 0) {
+    if (n_interior > 0 && narrow) {
+        rc = interior_narrow(stream);
+        if (rc) return join_and_fail(rc);
+    } else if (n_interior > 0) {
         rc = probe_interior(plan, interior, n_interior);
         if (rc) return join_and_fail(rc);
         if (plan->probed_contig)
@@ -867,7 +928,8 @@ static int spmv_dist_dot_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, h
                               const I *colval, const double *nzval, const double *x, int64_t n_own,
                               double *y, int64_t nrows, int64_t nnz, int index_base,
                               const int32_t *interior, int64_t n_interior, const int32_t *boundary,
-                              int64_t n_boundary, double *dot_out_dev, void *work, void *stream)
+                              int64_t n_boundary, double *dot_out_dev, void *work, void *stream,
+                              const int16_t *cols16 = nullptr)
 {
     if (!dot_out_dev || !work) return set_error(HPCLA_ERR_INVALID, "spmv_dist_dot: null out/work");
     if (n_own != nrows)
@@ -880,7 +942,7 @@ static int spmv_dist_dot_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, h
     double *scratch = reinterpret_cast<double *>(work);          // 2048 doubles of stage-1 scratch
     double *partial = scratch + 2048;                            // then one double per row block
     int rc = spmv_dist_impl<I>(split_fn, fused_fn, plan, rowptr, colval, nzval, x, n_own, y, nrows, nnz, index_base,
-                               interior, n_interior, boundary, n_boundary, stream, partial);
+                               interior, n_interior, boundary, n_boundary, stream, partial, cols16);
     if (rc) return rc;
     rc = reduce_partials_sum(partial, all_blocks, scratch, dot_out_dev, stream);
     if (rc) return rc;
@@ -942,6 +1004,30 @@ HPCLA_API int hpcla_spmv_dist_f64_i64(hpcla_halo_plan_t *plan, const int64_t *ro
     return spmv_dist_impl<int64_t>(spmv_split_i64, spmv_fused_i64, plan, rowptr, colval_split, nzval, x, n_own, y,
                                    nrows, nnz, index_base, interior_blocks, n_interior,
                                    boundary_blocks, n_boundary, stream);
+}
+
+// The two products above for a plan that holds a 16-bit copy of its interior blocks' columns (hpcla_cols16_encode_i32).
+// cols16 == NULL, or a copy / nzval the vector loads cannot take (alignment): exactly the Int32 entry points.
+HPCLA_API int hpcla_spmv_dist_cols16_f64_i32(hpcla_halo_plan_t *plan, const int32_t *rowptr, const int32_t *colval_split,
+                                             const int16_t *cols16, const double *nzval, const double *x, int64_t n_own,
+                                             double *y, int64_t nrows, int64_t nnz, int index_base,
+                                             const int32_t *interior_blocks, int64_t n_interior,
+                                             const int32_t *boundary_blocks, int64_t n_boundary, void *stream)
+{
+    return spmv_dist_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, rowptr, colval_split, nzval, x, n_own, y, nrows, nnz,
+                                   index_base, interior_blocks, n_interior, boundary_blocks, n_boundary, stream, nullptr, cols16);
+}
+
+HPCLA_API int hpcla_spmv_dist_dot_cols16_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int32_t *rowptr,
+                                                 const int32_t *colval_split, const int16_t *cols16, const double *nzval,
+                                                 const double *x, int64_t n_own, double *y, int64_t nrows, int64_t nnz,
+                                                 int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                                 const int32_t *boundary_blocks, int64_t n_boundary, double *dot_out_dev,
+                                                 void *work, void *stream)
+{
+    return spmv_dist_dot_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, comm, rowptr, colval_split, nzval, x, n_own, y,
+                                       nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks, n_boundary,
+                                       dot_out_dev, work, stream, cols16);
 }
 
 // ---- k fused CG iterations in ONE host call ----------------------------------------------------------

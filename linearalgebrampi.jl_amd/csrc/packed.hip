@@ -45,6 +45,10 @@ int spmv_fused_i32(const int32_t *, const int32_t *, const double *, const doubl
                    double *, int64_t, int64_t, int, const int32_t *, int64_t, int64_t, const int32_t *, int64_t,
                    const HaloWait &, const PushArgs &, void *, double *);     // spmv.hip
 int halo_exchange_inline(hpcla_halo_plan_t *plan, const double *x, void *stream);   // comm.hip
+// 16-bit block-relative columns of the listed (or all nb) row blocks; *flag_dev |= 1 when a listed block has a ghost column or
+// one outside the int16 window (spmv.hip: the same encoder serves the default narrow-column path)
+int encode_cols16_i32(const int32_t *rowptr, const int32_t *colval, int64_t nrows, int index_base, int64_t n_own,
+                      const int32_t *block_list, int64_t n_blocks, int16_t *dcol, int *flag_dev, void *stream);
 
 }  // namespace hpcla
 
@@ -92,30 +96,6 @@ __global__ __launch_bounds__(256) void encode_values_kernel(const double *__rest
             if (slot < cap) missing[slot] = v;
         }
     }
-}
-
-// encode columns of the listed row blocks; flags[0] |= 1 when an entry is a ghost column or outside
-// the int16 window (block not packable).
-template <typename I>
-__global__ __launch_bounds__(256) void encode_cols_kernel(const I *__restrict__ rowptr,
-                                                          const I *__restrict__ colval, int64_t nrows,
-                                                          int base, int64_t n_own,
-                                                          const int32_t *__restrict__ block_list,
-                                                          short *__restrict__ dcol,
-                                                          int *__restrict__ flags)
-{
-    const int64_t blk = block_list ? (int64_t)block_list[blockIdx.x] : (int64_t)blockIdx.x;
-    const int64_t r0 = blk * P_RPB;
-    const int nr = (int)((nrows - r0) < P_RPB ? (nrows - r0) : P_RPB);
-    const int64_t p0 = (int64_t)rowptr[r0] - base, p1 = (int64_t)rowptr[r0 + nr] - base;
-    int bad = 0;
-    for (int64_t j = p0 + threadIdx.x; j < p1; j += 256) {
-        const int64_t c = (int64_t)colval[j] - base;
-        const int64_t d = c - r0;
-        if (c >= n_own || d < -32768 || d > 32767) bad = 1;
-        dcol[j] = (short)d;
-    }
-    if (__syncthreads_or(bad) && threadIdx.x == 0) atomicOr(flags, 1);
 }
 
 // ---- the packed SpMV kernel ----------------------------------------------------------------------------
@@ -243,9 +223,10 @@ HPCLA_API int hpcla_packed_create_i32(hpcla_packed_t **out, const int32_t *rowpt
 
     // ---- columns -----------------------------------------------------------------------------
     PK_HIP(hipMemsetAsync(d_cnt, 0, 2 * sizeof(int), s));
-    encode_cols_kernel<int32_t><<<(uint32_t)nb, 256, 0, s>>>(rowptr, colval_split, nrows, index_base,
-                                                             n_own, block_list, p->dcol, d_cnt + 1);
-    PK_HIP(hipGetLastError());
+    if (const int rce = encode_cols16_i32(rowptr, colval_split, nrows, index_base, n_own, block_list, nb, p->dcol, d_cnt + 1, stream)) {
+        packed_free(p); (void)hipFree(d_missing); (void)hipFree(d_cnt);
+        return rce;                                    // (the reason is already recorded)
+    }
     int h_flags[2] = {0, 0};
     PK_HIP(hipMemcpyAsync(h_flags, d_cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     PK_HIP(hipStreamSynchronize(s));

@@ -15,8 +15,8 @@
 // add (this file is compiled with -ffp-contract=off): results are bit-identical to the reference
 // loop, not merely within tolerance.  No MFMA: 2 flop per 12 bytes is a bandwidth-bound gather.
 //
-// HBM traffic per row block = the algorithmic bytes: 12 B/nnz (int32) + 4 B/row rowptr + 8 B/row y
-// (+ x once).  Rows longer than a pass are handled by the pass loop (the row's running sum is
+// HBM traffic per row block = the algorithmic bytes: 12 B/nnz (int32; 10 B/nnz where the plan holds 16-bit block-relative
+// columns, IndexPolicy<Cols16> below) + 4 B/row rowptr + 8 B/row y (+ x once).  Rows longer than a pass are handled by the pass loop (the row's running sum is
 // carried in a register), so there is no row-length limit and no preprocessing.
 //
 // Measured choices (benchmarks/tune_spmv.py, tune_spmv_lib.py; profiles/): 16-byte loads beat
@@ -34,6 +34,7 @@
 
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 
 #include "common.h"
@@ -47,6 +48,33 @@ constexpr int UNROLL = CHUNK / RPB;      // ... entries per lane per pass
 
 template <typename T, int N>
 using vec = T __attribute__((ext_vector_type(N)));
+
+// Index POLICY of the row-gather kernel (its first template parameter): what the row pointers and the streamed column
+// entries are, how many entries one 16-byte column load covers, and how a streamed entry becomes a position in x.
+//   int32_t / int64_t   the caller's (or the plan's narrowed) CSR arrays: rowptr and colval of that type, quads.
+//   Cols16              Int32 row pointers and the plan's own 16-bit copy of the columns (hpcla_cols16_encode_i32): entry j
+//                       of row block b holds colval_split[j] - index_base - 256 b, so a lane loads EIGHT columns with one
+//                       16-byte load (8-byte loads run at 0.54-0.70 x the rate of 16-byte ones on this chip) and the
+//                       position in x is r0 + d.  Only blocks whose columns are all owned and inside the window are
+//                       ever launched in this form; every column is an owned one, so there is no SPLIT form.
+// A further narrow form (8-bit diagonal codes through a table) is one more specialisation: col_t, VEC and decode().
+struct Cols16 {};
+template <typename P>
+struct IndexPolicy {
+    using row_t = P;
+    using col_t = P;
+    static constexpr int VEC = 4;
+    static __device__ __forceinline__ int64_t decode(col_t c, int base, int64_t /*r0*/) { return (int64_t)(P)(c - (P)base); }
+    static __device__ __forceinline__ col_t fill(int base) { return (P)base; }
+};
+template <>
+struct IndexPolicy<Cols16> {
+    using row_t = int32_t;
+    using col_t = int16_t;
+    static constexpr int VEC = 8;
+    static __device__ __forceinline__ int64_t decode(col_t d, int /*base*/, int64_t r0) { return r0 + (int)d; }
+    static __device__ __forceinline__ col_t fill(int /*base*/) { return 0; }
+};
 
 template <bool SPLIT>
 __device__ __forceinline__ double gather_x(const double *__restrict__ x_own,
@@ -141,7 +169,7 @@ __device__ __forceinline__ void block_dot_epilogue(double *s_scratch, double *__
 // Harness (benchmarks/tune/spmv_variants.hip k_rowg / k_rowg_wave, profiles/r04_spmv_rowg.log): 7-point slab -4.3 ... -4.8 %,
 // 4096^2 -1.5 %, 8192^2 -2.2 % against the quad kernel under its measured block order.
 constexpr int RG_CHW = 464;                         // entries per wave and pass: 64 rows x 7 + the <= 3 entries in front of the aligned start, rounded up (5.4 KiB of LDS per wave: 7 workgroups per CU)
-constexpr int RG_NQ = (RG_CHW / 4 + 63) / 64;       // quads per lane per pass
+                                                    // (Cols16: 58 octets = 64 rows x 7 + the <= 7 entries in front, 4.5 KiB per wave: 8 workgroups per CU)
 constexpr int RG_UR = 8;                            // entries per gather step
 
 // LONGR (round 5, OPT-IN: hpcla_spmv_longrows_*): rows of at least `long_min` entries are LEFT OUT here -- their lanes sum
@@ -151,19 +179,28 @@ constexpr int RG_UR = 8;                            // entries per gather step
 // order -- the reference's bits, and its cliff (one work-item per row, src/sparse.jl:2055-2066).
 template <typename I, bool SPLIT, bool WAIT, bool LONGR = false>
 __global__ __launch_bounds__(RPB) void spmv_rowgather_kernel(
-    const I *__restrict__ rowptr, const I *__restrict__ colval, const double *__restrict__ nzval,
-    const double *__restrict__ x_own, const double *x_ghost, int64_t n_own,
+    const typename IndexPolicy<I>::row_t *__restrict__ rowptr, const typename IndexPolicy<I>::col_t *__restrict__ colval,
+    const double *__restrict__ nzval, const double *__restrict__ x_own, const double *x_ghost, int64_t n_own,
     double *__restrict__ y, int64_t nrows, int64_t nnz, int base,
     BlockSel bs, double *__restrict__ dot_partial, HaloWait hw, PushArgs push, int64_t long_min = 0)
 {
+    using IP = IndexPolicy<I>;
+    using R = typename IP::row_t;                       // row pointers
+    using C = typename IP::col_t;                       // streamed column entries
+    constexpr int V = IP::VEC;                          // entries per 16-byte column load: a lane stages V entries at a time
+    constexpr int NV = (RG_CHW / V + 63) / 64;          // ... NV times per pass
     static_assert(!LONGR || !WAIT, "the long-row form is a plain launch");
-    __shared__ __attribute__((aligned(16))) I s_col_all[(RPB / 64) * RG_CHW];
+    static_assert(V * sizeof(C) == 16 || sizeof(C) == 8, "one 16-byte column load per staged vector (Int64: two)");
+    static_assert(RG_CHW % V == 0 && RG_CHW >= 64 * 7 + V - 1, "a pass holds a 7-entry stencil's wave behind any aligned start");
+    __shared__ __attribute__((aligned(16))) C s_col_all[(RPB / 64) * RG_CHW];
     __shared__ __attribute__((aligned(16))) double s_val_all[(RPB / 64) * RG_CHW];
     __shared__ double s_red[RPB / 64];
 
-    if (WAIT && (int)blockIdx.x < push.n_blocks) {
-        halo_push_block<I, RPB>(push, (int)blockIdx.x);
-        return;
+    if constexpr (WAIT) {
+        if ((int)blockIdx.x < push.n_blocks) {
+            halo_push_block<R, RPB>(push, (int)blockIdx.x);
+            return;
+        }
     }
     const int tid = threadIdx.x;
     bool wait_ghosts;
@@ -183,7 +220,7 @@ __global__ __launch_bounds__(RPB) void spmv_rowgather_kernel(
     }
 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    I *s_col = s_col_all + wave * RG_CHW;
+    C *s_col = s_col_all + wave * RG_CHW;
     double *s_val = s_val_all + wave * RG_CHW;
     const int64_t rw = r0 + wave * 64;                                   // this wave's rows
     const int nrw = nr - wave * 64 < 0 ? 0 : (nr - wave * 64 > 64 ? 64 : nr - wave * 64);
@@ -191,12 +228,16 @@ __global__ __launch_bounds__(RPB) void spmv_rowgather_kernel(
     if (nrw > 0) {                                                       // wave-uniform
         const int64_t p0 = (int64_t)rowptr[rw] - base;
         const int64_t p1 = (int64_t)rowptr[rw + nrw] - base;
-        const int64_t pa = p0 & ~(int64_t)3;                             // quad-aligned start (<= 3 entries of the rows before)
+        // vector-aligned start: <= V - 1 entries of the rows before.  (Cols16: when those rows belong to the row block IN FRONT,
+        // their entries hold deltas relative to THAT block's first row -- and the same goes for the entries behind the wave's last
+        // row in the pass's last vector.  They are staged and never gathered: a lane only walks [lo, hi) of its own row, and the
+        // whole-pass branch only runs when one row of this wave owns every entry of the pass.  So no clamp of r0 + d is needed.)
+        const int64_t pa = p0 & ~(int64_t)(V - 1);
         const int64_t total = p1 - pa;
         // this lane's row bounds, raw and UNCONDITIONAL (lanes past the wave's last row read that row's pair: a predicated
         // load is a branch whose merge copies the loaded register, i.e. waits for it on the spot); first used behind the A stream
         const int ll = lane < nrw ? lane : nrw - 1;
-        I rlo = rowptr[rw + ll], rhi = rowptr[rw + ll + 1];
+        R rlo = rowptr[rw + ll], rhi = rowptr[rw + ll + 1];
         if (dot_partial) x_row = x_own[rw + ll];                         // the epilogue's x rides along with the stream
         const bool is_long = LONGR && lane < nrw && (int64_t)rhi - (int64_t)rlo >= long_min;
         for (int64_t c = 0; c < total; c += RG_CHW) {
@@ -211,35 +252,38 @@ __global__ __launch_bounds__(RPB) void spmv_rowgather_kernel(
                 }
             }
             const int n = (int)((total - c) < RG_CHW ? (total - c) : RG_CHW);
-            if (pa + c + ((n + 3) & ~3) <= nnz) {
-                // every quad of the pass lies inside the arrays: ALL of a lane's quads are requested before the first is
-                // written (lanes past the end re-read the pass's last quad -- lines their neighbours read anyway -- and
+            if (pa + c + ((n + V - 1) & ~(V - 1)) <= nnz) {
+                // every vector of the pass lies inside the arrays: ALL of a lane's vectors are requested before the first is
+                // written (lanes past the end re-read the pass's last vector -- lines their neighbours read anyway -- and
                 // write nothing)
-                const int last = (n - 1) & ~3;
-                vec<I, 4> cq[RG_NQ];
-                vec<double, 2> va[RG_NQ], vb[RG_NQ];
+                const int last = (n - 1) & ~(V - 1);
+                vec<C, V> cq[NV];
+                vec<double, 2> va[NV][V / 2];
 #pragma unroll
-                for (int u = 0; u < RG_NQ; ++u) {
-                    const int e0 = (u * 64 + lane) * 4;
+                for (int u = 0; u < NV; ++u) {
+                    const int e0 = (u * 64 + lane) * V;
                     const int ee = e0 < last ? e0 : last;
-                    cq[u] = *reinterpret_cast<const vec<I, 4> *>(colval + pa + c + ee);
-                    va[u] = *reinterpret_cast<const vec<double, 2> *>(nzval + pa + c + ee);
-                    vb[u] = *reinterpret_cast<const vec<double, 2> *>(nzval + pa + c + ee + 2);
+                    cq[u] = *reinterpret_cast<const vec<C, V> *>(colval + pa + c + ee);
+#pragma unroll
+                    for (int k = 0; k < V / 2; ++k)
+                        va[u][k] = *reinterpret_cast<const vec<double, 2> *>(nzval + pa + c + ee + 2 * k);
                 }
 #pragma unroll
-                for (int u = 0; u < RG_NQ; ++u) {
-                    const int e0 = (u * 64 + lane) * 4;
+                for (int u = 0; u < NV; ++u) {
+                    const int e0 = (u * 64 + lane) * V;
                     if (e0 < n) {
-                        *reinterpret_cast<vec<I, 4> *>(&s_col[e0]) = cq[u];
-                        *reinterpret_cast<vec<double, 2> *>(&s_val[e0]) = va[u];
-                        *reinterpret_cast<vec<double, 2> *>(&s_val[e0 + 2]) = vb[u];
+                        *reinterpret_cast<vec<C, V> *>(&s_col[e0]) = cq[u];
+#pragma unroll
+                        for (int k = 0; k < V / 2; ++k)
+                            *reinterpret_cast<vec<double, 2> *>(&s_val[e0 + 2 * k]) = va[u][k];
                     }
                 }
             } else {
-                // the one pass of the launch that reaches past the end of the arrays: entry by entry
+                // the one pass of the launch that reaches past the end of nzval (the caller's array: it ends at nnz, whatever
+                // the padding of a column copy of the plan's own): entry by entry
                 for (int e = lane; e < n; e += 64) {
                     const int64_t g = pa + c + e;
-                    s_col[e] = g < nnz ? colval[g] : (I)base;
+                    s_col[e] = g < nnz ? colval[g] : IP::fill(base);
                     s_val[e] = g < nnz ? nzval[g] : 0.0;
                 }
             }
@@ -265,7 +309,7 @@ __global__ __launch_bounds__(RPB) void spmv_rowgather_kernel(
                     // CU; unrolled freely it took 96 and the headline lost 7 %, profiles/r05_arrow_and_long_rows.log)
 #pragma unroll 4
                     for (int e = lane; e < n; e += 64)
-                        s_val[e] = s_val[e] * gather_x<SPLIT>(x_own, x_ghost, n_own, (int64_t)(I)(s_col[e] - (I)base));
+                        s_val[e] = s_val[e] * gather_x<SPLIT>(x_own, x_ghost, n_own, IP::decode(s_col[e], base, r0));
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                     if (lane == __ffsll((unsigned long long)whole) - 1) {
@@ -293,7 +337,7 @@ __global__ __launch_bounds__(RPB) void spmv_rowgather_kernel(
 #pragma unroll
                     for (int u = 0; u < RG_UR; ++u) {
                         cc[u] = 0; vv[u] = 0.0;
-                        if (j + u < e) { cc[u] = (int64_t)(I)(s_col[j + u] - (I)base); vv[u] = s_val[j + u]; }
+                        if (j + u < e) { cc[u] = IP::decode(s_col[j + u], base, r0); vv[u] = s_val[j + u]; }
                     }
 #pragma unroll
                     for (int u = 0; u < RG_UR; ++u) { xx[u] = 0.0; if (j + u < e) xx[u] = gather_x<SPLIT>(x_own, x_ghost, n_own, cc[u]); }
@@ -550,8 +594,10 @@ static int spmv_nt_y(bool /*with_dot*/)
     return on;
 }
 
+// (I: an index policy -- int32_t / int64_t arrays, or Cols16: Int32 row pointers with the plan's 16-bit column copy)
 template <typename I>
-static int spmv_launch(const I *rowptr, const I *colval, const double *nzval, const double *x_own,
+static int spmv_launch(const typename IndexPolicy<I>::row_t *rowptr, const typename IndexPolicy<I>::col_t *colval,
+                       const double *nzval, const double *x_own,
                        const double *x_ghost, int64_t n_own, bool split, double *y, int64_t nrows,
                        int64_t nnz, int index_base, const int32_t *block_list, int64_t n_blocks,
                        void *stream, double *dot_partial = nullptr, int64_t block_base = -1)
@@ -583,8 +629,9 @@ static int spmv_launch(const I *rowptr, const I *colval, const double *nzval, co
     hipStream_t s = as_stream(stream);
     // no ghost segment => no column can be >= n_own: take the plain-x kernel (no per-entry select)
     if (split && !x_ghost) split = false;
-    // 16-byte staging loads from any quad-aligned entry offset: colval 4*sizeof(I)-, nzval 32-byte aligned (else: the fallback kernel)
-    const bool aligned = (reinterpret_cast<uintptr_t>(colval) % (4 * sizeof(I)) == 0) &&
+    // 16-byte staging loads from any vector-aligned entry offset: colval VEC*sizeof(col_t)-, nzval 32-byte aligned (else: the fallback kernel)
+    using IP = IndexPolicy<I>;
+    const bool aligned = (reinterpret_cast<uintptr_t>(colval) % (IP::VEC * sizeof(typename IP::col_t)) == 0) &&
                          (reinterpret_cast<uintptr_t>(nzval) % 32 == 0);
     const BlockSel bs{block_list, block_base, nullptr, 0, 0, launch_blocks, block_list ? 0 : block_order_of(rowptr),
                       spmv_nt_y(dot_partial != nullptr)};
@@ -592,7 +639,12 @@ static int spmv_launch(const I *rowptr, const I *colval, const double *nzval, co
     memset(&nowait, 0, sizeof(nowait));
     PushArgs nopush;
     memset(&nopush, 0, sizeof(nopush));
-    if (aligned) {
+    if constexpr (std::is_same<I, Cols16>::value) {
+        // the narrow form has no fallback kernel of its own: the callers send misaligned arrays down the Int32 path (cols16_usable)
+        if (!aligned) return set_error(HPCLA_ERR_INVALID, "spmv: 16-bit columns need a 16-byte aligned copy and 32-byte aligned nzval");
+        spmv_rowgather_kernel<Cols16, false, false><<<grid, block, 0, s>>>(
+            rowptr, colval, nzval, x_own, nullptr, 0, y, nrows, nnz, index_base, bs, dot_partial, nowait, nopush);
+    } else if (aligned) {
         if (split)
             spmv_rowgather_kernel<I, true, false><<<grid, block, 0, s>>>(
                 rowptr, colval, nzval, x_own, x_ghost, n_own, y, nrows, nnz, index_base, bs, dot_partial, nowait, nopush);
@@ -693,6 +745,55 @@ int spmv_split_i64(const int64_t *rowptr, const int64_t *colval, const double *n
                                 index_base, bl, nb, stream, dot_partial, block_base);
 }
 
+// ---- 16-bit block-relative columns (plan-time copy; exported to comm.hip and packed.hip) ---------------------------------
+// encode the columns of the listed (or all) row blocks; flags[0] |= 1 when an entry is a ghost column or outside the int16
+// window (block not encodable).  Shared by the default narrow path (hpcla_cols16_encode_i32) and the opt-in packed copy.
+__global__ __launch_bounds__(256) void encode_cols_kernel(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ colval,
+                                                          int64_t nrows, int base, int64_t n_own,
+                                                          const int32_t *__restrict__ block_list, int16_t *__restrict__ dcol,
+                                                          int *__restrict__ flags)
+{
+    const int64_t blk = block_list ? (int64_t)block_list[blockIdx.x] : (int64_t)blockIdx.x;
+    const int64_t r0 = blk * RPB;
+    const int nr = (int)((nrows - r0) < RPB ? (nrows - r0) : RPB);
+    const int64_t p0 = (int64_t)rowptr[r0] - base, p1 = (int64_t)rowptr[r0 + nr] - base;
+    int bad = 0;
+    for (int64_t j = p0 + threadIdx.x; j < p1; j += 256) {
+        const int64_t c = (int64_t)colval[j] - base;
+        const int64_t d = c - r0;
+        if (c < 0 || c >= n_own || d < -32768 || d > 32767) bad = 1;
+        dcol[j] = (int16_t)d;
+    }
+    if (__syncthreads_or(bad) && threadIdx.x == 0) atomicOr(flags, 1);
+}
+
+// entries of a 16-bit column copy of nnz entries: rounded up to a whole vector of 8 plus one more, so that every aligned
+// 16-byte load of a kernel that starts inside the array stays inside the allocation
+int64_t cols16_padded_len(int64_t nnz) { return ((nnz + 7) / 8) * 8 + 8; }
+
+int encode_cols16_i32(const int32_t *rowptr, const int32_t *colval, int64_t nrows, int index_base, int64_t n_own,
+                      const int32_t *block_list, int64_t n_blocks, int16_t *dcol, int *flag_dev, void *stream)
+{
+    if (n_blocks <= 0) return HPCLA_OK;
+    encode_cols_kernel<<<(uint32_t)n_blocks, 256, 0, as_stream(stream)>>>(rowptr, colval, nrows, index_base, n_own, block_list,
+                                                                         dcol, flag_dev);
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
+bool cols16_usable(const int16_t *cols16, const double *nzval)
+{
+    return cols16 && reinterpret_cast<uintptr_t>(cols16) % 16 == 0 && reinterpret_cast<uintptr_t>(nzval) % 32 == 0;
+}
+
+int spmv_cols16_i32(const int32_t *rowptr, const int16_t *cols16, const double *nzval, const double *x, double *y,
+                    int64_t nrows, int64_t nnz, int index_base, const int32_t *bl, int64_t nb, void *stream,
+                    double *dot_partial, int64_t block_base)
+{
+    return spmv_launch<Cols16>(rowptr, cols16, nzval, x, nullptr, 0, false, y, nrows, nnz, index_base, bl, nb, stream,
+                               dot_partial, block_base);
+}
+
 }  // namespace hpcla
 
 using namespace hpcla;
@@ -713,16 +814,21 @@ static void set_block_order(const void *rowptr, int group_log2)
 // config 4's planes and the 256^3 cube, but not that 4096- and 8192-wide 2-D grids gain 3 % from groups of 32 / 64
 // although their neighbours already share an XCD in the natural order, nor that a 1000-wide grid loses 1 % with
 // groups of 64 -- profiles/r03_spmv_xcd_group_order.log -- so the choice is measured, like an FFT plan's.)
+// (I: an index policy, see IndexPolicy.  run_base >= 0: the launches cover the contiguous run of run_blocks row blocks from
+//  run_base -- the interior run of a plan whose boundary blocks take another kernel form -- instead of every block.)
 template <typename I>
-static int tune_block_order(const I *rowptr, const I *colval_split, const double *nzval, const double *x_own,
+static int tune_block_order(const typename IndexPolicy<I>::row_t *rowptr, const typename IndexPolicy<I>::col_t *colval_split,
+                            const double *nzval, const double *x_own,
                             const double *x_ghost, int64_t n_own, double *y_scratch, int64_t nrows, int64_t nnz,
-                            int index_base, void *stream, int *chosen_group)
+                            int index_base, void *stream, int *chosen_group, int64_t run_base = -1, int64_t run_blocks = 0)
 {
     if (chosen_group) *chosen_group = 1;
     if (nrows < 0 || nnz < 0 || !rowptr) return set_error(HPCLA_ERR_INVALID, "spmv_tune_block_order: bad arguments");
     set_block_order(rowptr, 0);
     const int64_t n_blocks = (nrows + RPB - 1) / RPB;
     if (n_blocks < 4096 || nnz == 0) return HPCLA_OK;      // small matrices live in the caches whatever the order
+    if (run_base >= 0 && (run_blocks <= 0 || run_base + run_blocks > n_blocks))
+        return run_blocks == 0 ? HPCLA_OK : set_error(HPCLA_ERR_INVALID, "spmv_tune_block_order: block run out of bounds");
     if (!y_scratch) return set_error(HPCLA_ERR_INVALID, "spmv_tune_block_order: null scratch vector");
     constexpr int NC = 4, ROUNDS = 4, REPS = 4;            // round 0 warms up (clocks, TLBs) and is not counted
     const int cand[NC] = {0, 3, 5, 6};
@@ -738,7 +844,7 @@ static int tune_block_order(const I *rowptr, const I *colval_split, const double
             if (hipEventRecord(e0, s) != hipSuccess) { rc = set_error(HPCLA_ERR_HIP, "spmv_tune_block_order: event"); break; }
             for (int i = 0; i < REPS && rc == HPCLA_OK; ++i)
                 rc = spmv_launch<I>(rowptr, colval_split, nzval, x_own, x_ghost, n_own, true, y_scratch, nrows, nnz,
-                                    index_base, nullptr, 0, stream);
+                                    index_base, nullptr, run_base >= 0 ? run_blocks : 0, stream, nullptr, run_base);
             if (rc != HPCLA_OK) break;
             if (hipEventRecord(e1, s) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
                 hipEventElapsedTime(&ms[c][r], e0, e1) != hipSuccess)
@@ -778,6 +884,48 @@ HPCLA_API int hpcla_spmv_tune_block_order_f64_i64(const int64_t *rowptr, const i
 {
     return tune_block_order<int64_t>(rowptr, colval_split, nzval, x_own, x_ghost, n_own, y_scratch, nrows, nnz, index_base,
                                      stream, chosen_group);
+}
+
+HPCLA_API int hpcla_spmv_tune_block_order_cols16_f64_i32(const int32_t *rowptr, const int16_t *cols16, const double *nzval,
+                                                         const double *x_own, double *y_scratch, int64_t nrows, int64_t nnz,
+                                                         int index_base, int64_t block_base, int64_t n_blocks, void *stream,
+                                                         int *chosen_group)
+{
+    if (!cols16_usable(cols16, nzval))
+        return set_error(HPCLA_ERR_INVALID, "spmv_tune_block_order_cols16: null or misaligned column copy / nzval");
+    return tune_block_order<Cols16>(rowptr, cols16, nzval, x_own, nullptr, 0, y_scratch, nrows, nnz, index_base, stream,
+                                    chosen_group, block_base, n_blocks);
+}
+
+// ---- plan-time 16-bit column copy ----------------------------------------------------------------------------------------
+HPCLA_API int64_t hpcla_cols16_padded_len(int64_t nnz) { return cols16_padded_len(nnz > 0 ? nnz : 0); }
+
+HPCLA_API int hpcla_cols16_encode_i32(const int32_t *rowptr, const int32_t *colval_split, int64_t nrows, int64_t nnz,
+                                      int64_t n_own, int index_base, const int32_t *block_list, int64_t n_blocks,
+                                      int16_t *cols16, int *ineligible_dev, void *stream)
+{
+    if (nrows < 0 || nnz < 0 || n_own < 0) return set_error(HPCLA_ERR_INVALID, "cols16_encode: negative size");
+    if (index_base != 0 && index_base != 1) return set_error(HPCLA_ERR_INVALID, "cols16_encode: index_base must be 0 or 1");
+    if (!cols16 || !ineligible_dev) return set_error(HPCLA_ERR_INVALID, "cols16_encode: null output");
+    const int64_t all_blocks = (nrows + RPB - 1) / RPB;
+    const int64_t nb = block_list ? n_blocks : all_blocks;
+    if (nb < 0 || nb > all_blocks) return set_error(HPCLA_ERR_INVALID, "cols16_encode: n_blocks out of range");
+    if (nb > 0x7fffffffLL) return set_error(HPCLA_ERR_INVALID, "cols16_encode: too many blocks");
+    if (nb > 0 && (!rowptr || (nnz > 0 && !colval_split))) return set_error(HPCLA_ERR_INVALID, "cols16_encode: null array");
+    hipStream_t s = as_stream(stream);
+    // the whole copy, pad included, is defined: entries of blocks that are not listed (boundary blocks) and the pad read 0
+    HPCLA_CHECK_HIP(hipMemsetAsync(cols16, 0, (size_t)cols16_padded_len(nnz) * sizeof(int16_t), s));
+    HPCLA_CHECK_HIP(hipMemsetAsync(ineligible_dev, 0, sizeof(int), s));
+    return encode_cols16_i32(rowptr, colval_split, nrows, index_base, n_own, block_list, nb, cols16, ineligible_dev, stream);
+}
+
+HPCLA_API int hpcla_spmv_cols16_f64_i32(const int32_t *rowptr, const int16_t *cols16, const double *nzval, const double *x,
+                                        double *y, int64_t nrows, int64_t nnz, int index_base, const int32_t *block_list,
+                                        int64_t n_blocks, void *stream)
+{
+    if (nnz > 0 && !cols16_usable(cols16, nzval))
+        return set_error(HPCLA_ERR_INVALID, "spmv_cols16: null or misaligned column copy / nzval (take hpcla_spmv_split_f64_i32)");
+    return spmv_cols16_i32(rowptr, cols16, nzval, x, y, nrows, nnz, index_base, block_list, n_blocks, stream, nullptr, -1);
 }
 
 HPCLA_API int hpcla_spmv_block_order_hint(const void *rowptr, int group)

@@ -193,6 +193,26 @@ def narrowing_enabled() -> bool:
     return _os.environ.get("HPCLA_NARROW_INDICES", "1").strip().lower() not in ("0", "off", "false", "no")
 
 
+def narrow_cols_enabled() -> bool:
+    """``HPCLA_NARROW_COLS=0`` keeps every plan on the Int32 column stream (A/B measurements against the 16-bit
+    block-relative copy of ``VectorPlan.cols16``); no 16-bit array is allocated then."""
+    return _os.environ.get("HPCLA_NARROW_COLS", "1").strip().lower() not in ("0", "off", "false", "no")
+
+
+def encode_cols16(rowptr_dev, colval_split, nrows: int, nnz: int, n_own: int, block_list, n_blocks: int):
+    """16-bit block-relative copy of ``colval_split`` for the listed row blocks (``block_list`` None: all), or None when
+    the library finds a listed block with a ghost column or a column outside [r0 - 32768, r0 + 32767] of its first row
+    (``hpcla_cols16_encode_i32``: eligibility is decided on the device, all or nothing).  The tensor is padded to
+    ``hpcla_cols16_padded_len(nnz)`` entries so that the kernel's aligned 16-byte loads stay inside it."""
+    torch = _torch()
+    dev = colval_split.device
+    out = torch.empty(_capi.load().hpcla_cols16_padded_len(nnz), dtype=torch.int16, device=dev)
+    bad = torch.empty(1, dtype=torch.int32, device=dev)
+    _capi.call("hpcla_cols16_encode_i32", dptr(rowptr_dev), dptr(colval_split), nrows, nnz, n_own, 0,
+               dptr(block_list) if block_list is not None else None, n_blocks, dptr(out), dptr(bad), current_stream_ptr())
+    return None if int(bad.item()) else out
+
+
 def can_narrow_indices(nnz: int, nrows_local: int, n_own: int, n_ghost: int, index_base: int = 0) -> bool:
     """May the kernels of a plan over an Int64 matrix stream Int32 indices?  Everything an index array of the plan
     can hold must fit: row pointers reach ``nnz + index_base``, split columns reach ``n_own + n_ghost - 1 +
@@ -303,6 +323,16 @@ class VectorPlan:
             self.n_interior = int(self.interior.numel())
             self.n_boundary = int(self.boundary.numel())
         self._keep = cmap_dev
+        # 16-bit block-relative copy of the interior blocks' columns (plans without neighbours: of all blocks).  Like
+        # colval_split itself it belongs to the STRUCTURE, not to a matrix: nzval is read live on every product.  The SpMV
+        # then streams 10 instead of 12 bytes per stored entry (same bits); + 2 B per stored entry of device memory.
+        # None: not eligible (Int64 kernel arrays, Float32, a column outside the window, HPCLA_NARROW_COLS=0) -- colval_split
+        # stays either way: the boundary blocks, SpMM, the transposes and classify_blocks read it.
+        self.cols16 = None
+        if (narrow_cols_enabled() and not self.is_i64 and not self.is_f32 and A.nrows_local > 0 and A.nnz > 0
+                and (not self.has_halo or self.n_interior > 0)):
+            self.cols16 = encode_cols16(self.rowptr_of(A), self.colval_split, A.nrows_local, A.nnz, self.n_own,
+                                        self.interior if self.has_halo else None, self.n_interior if self.has_halo else 0)
         # block order of the SpMV launches over this structure: measured once, here (hpcla_spmv_tune_block_order_*, a few
         # dozen launches into a scratch vector); HPCLA_BLOCK_ORDER=natural skips it, =<G> forces groups of G row blocks
         self.block_group = 1
@@ -321,10 +351,25 @@ class VectorPlan:
             scratch = torch.empty(A.nrows_local, dtype=torch.float64, device=dev)
             ghost, _ng = self.ghost_tensor_ptr()
             chosen = ctypes.c_int(1)
+            # the tuner times the kernel form the plan will launch, once: the narrow one over the blocks that hold 16-bit
+            # columns (all, or the contiguous interior run -- a list keeps its own order), else the Int32 / Int64 one
+            run = None
+            if self.cols16 is not None and A.nzval.data_ptr() % 32 == 0:
+                if not self.has_halo:
+                    run = (-1, 0)
+                else:
+                    first, last = int(self.interior[0]), int(self.interior[-1])
+                    if last - first + 1 == self.n_interior:
+                        run = (first, self.n_interior)
             try:
-                _capi.call(f"hpcla_spmv_tune_block_order_f64_{sfx}", dptr(self.rowptr_of(A)), dptr(self.colval_split),
-                           dptr(A.nzval), dptr(x.v), ghost, self.n_own, dptr(scratch), A.nrows_local, A.nnz, 0, s,
-                           ctypes.byref(chosen))
+                if run is not None:
+                    _capi.call("hpcla_spmv_tune_block_order_cols16_f64_i32", dptr(self.rowptr_of(A)), dptr(self.cols16),
+                               dptr(A.nzval), dptr(x.v), dptr(scratch), A.nrows_local, A.nnz, 0, run[0], run[1], s,
+                               ctypes.byref(chosen))
+                else:
+                    _capi.call(f"hpcla_spmv_tune_block_order_f64_{sfx}", dptr(self.rowptr_of(A)), dptr(self.colval_split),
+                               dptr(A.nzval), dptr(x.v), ghost, self.n_own, dptr(scratch), A.nrows_local, A.nnz, 0, s,
+                               ctypes.byref(chosen))
             except _capi.HPCLAError as exc:        # an optional performance step must not take A*x down with it
                 import sys
                 sys.stderr.write(f"hpcla: block-order measurement failed ({exc}); natural order\n")
@@ -371,6 +416,8 @@ def get_vector_plan(A: "HPCSparseMatrix", x: HPCVector) -> VectorPlan:
     key = (A._ensure_hash(), x.structural_hash, str(A.T), str(A.Ti), "ROCArray")
     if A.Ti == np.dtype(np.int64) and not narrowing_enabled():
         key += ("wide",)                       # HPCLA_NARROW_INDICES=0: a plan of its own, on the Int64 kernels
+    if not narrow_cols_enabled():
+        key += ("cols32",)                     # HPCLA_NARROW_COLS=0: a plan of its own, without the 16-bit column copy
     plan = _vector_plan_cache.get(key)
     if plan is None:
         plan = VectorPlan(A, x)
@@ -769,6 +816,12 @@ def _spmv_into(y: HPCVector, A: HPCSparseMatrix, x: HPCVector, plan: VectorPlan)
                    None, plan.n_own, dptr(y.v), A.nrows_local, A.nnz, 0, dptr(rows), int(rows.numel()), min_len, dptr(work),
                    current_stream_ptr())
         return
+    if plan.cols16 is not None:                           # interior blocks on 16-bit columns, boundary blocks on Int32
+        _capi.call("hpcla_spmv_dist_cols16_f64_i32", plan.halo if plan.has_halo else None,
+                   dptr(plan.rowptr_of(A)), dptr(plan.colval_split), dptr(plan.cols16), dptr(A.nzval), dptr(x.v), plan.n_own,
+                   dptr(y.v), A.nrows_local, A.nnz, 0, dptr(plan.interior), plan.n_interior,
+                   dptr(plan.boundary), plan.n_boundary, current_stream_ptr())
+        return
     _capi.call(f"hpcla_spmv_dist_f64_{sfx}", plan.halo if plan.has_halo else None,
                dptr(plan.rowptr_of(A)), dptr(plan.colval_split), dptr(A.nzval), dptr(x.v), plan.n_own,
                dptr(y.v), A.nrows_local, A.nnz, 0, dptr(plan.interior), plan.n_interior,
@@ -821,6 +874,12 @@ def mul_dot_(y: HPCVector, A: HPCSparseMatrix, x: HPCVector, out) -> HPCVector:
         _capi.call("hpcla_spmv_dist_packed_f64_i32", plan.halo if plan.has_halo else None, A.backend.rccl,
                    pk, dptr(plan.rowptr_of(A)), dptr(plan.colval_split), dptr(A.nzval), dptr(x.v),
                    plan.n_own, dptr(y.v), A.nrows_local, A.nnz, 0, dptr(plan.interior), plan.n_interior,
+                   dptr(plan.boundary), plan.n_boundary, dptr(out), dptr(work), current_stream_ptr())
+        return y
+    if plan.cols16 is not None:
+        _capi.call("hpcla_spmv_dist_dot_cols16_f64_i32", plan.halo if plan.has_halo else None, A.backend.rccl,
+                   dptr(plan.rowptr_of(A)), dptr(plan.colval_split), dptr(plan.cols16), dptr(A.nzval), dptr(x.v), plan.n_own,
+                   dptr(y.v), A.nrows_local, A.nnz, 0, dptr(plan.interior), plan.n_interior,
                    dptr(plan.boundary), plan.n_boundary, dptr(out), dptr(work), current_stream_ptr())
         return y
     sfx = "i64" if plan.is_i64 else "i32"
