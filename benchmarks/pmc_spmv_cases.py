@@ -3,7 +3,7 @@
 (why does the 3-D 7-point SpMV(+p.Ap) inside the CG loop run at 0.636 of peak against 0.727 for the
 2-D 5-point one, at the same ~1.05x traffic?).
 
-Cases, in this order (every launch of `spmv_rowblock_quad_kernel` in the process belongs to exactly one of them; the
+Cases, in this order (every launch of `spmv_rowgather_kernel` in the process belongs to exactly one of them; the
 plan-time block-order measurement is switched off by fixing the order):
 
   2d      4096 x 4096 5-point, y = A x                       (the headline kernel)
@@ -94,7 +94,7 @@ def main():
         torch.cuda.empty_cache()
     if args.manifest:
         json.dump({"cases": manifest, "event_ms": times, "order2d": args.order2d, "order3d": args.order3d,
-                   "kernel": "spmv_rowgather_kernel" if hp._capi.load().hpcla_get_spmv_kernel() == 0 else "spmv_rowblock_quad_kernel"},
+                   "kernel": "spmv_rowgather_kernel"},          # the only CSR SpMV kernel since the quad kernel was retired
                   open(args.manifest, "w"))
     print(json.dumps({"event_ms_per_launch": {k: round(v, 5) for k, v in times.items()}}))
 
