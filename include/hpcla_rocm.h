@@ -713,6 +713,57 @@ int hpcla_spmv_tune_block_order_cols16_f64_i32(const int32_t *rowptr, const int1
                                                int index_base, int64_t block_base, int64_t n_blocks, void *stream,
                                                int *chosen_group);
 
+/* ---- repeating block patterns: the column and row-pointer streams of a structured matrix from a table (no reference
+ * counterpart: the reference streams rowptr and colval as stored, src/sparse.jl:2055-2066) ---------------------------------
+ * A 256-row block has a PATTERN: its row lengths, its block-relative columns (the cols16 copy above) and the position of
+ * its first stored entry modulo 8 (the kernel's 16-byte loads start at an 8-entry boundary).  A structured-grid matrix
+ * repeats a handful of patterns (2-D 5-point 4096 wide: 18 in 8192 blocks, 46 KB), so a table of them stays in every
+ * XCD's L2 and the SpMV no longer streams 2 B per entry of cols16 nor 4 B per row of rowptr from HBM: 8 B per entry of
+ * nzval, 16 B per row of x and y and one 8-byte record per block remain (4096^2: 1.174 GB -> 0.940 GB per product).
+ * Like cols16 the table is pure STRUCTURE (src/sparse.jl:1875-1984 builds colval_split once per (A, x.partition)):
+ * nzval is read live on every call, y has the same bits.
+ *   create: hashes every candidate block on the device -- the listed ones, the contiguous run of n_blocks from
+ *           block_base (block_list == NULL, block_base >= 0), or all (block_list == NULL, block_base < 0); every one
+ *           must have been encoded in cols16 -- counts the hashes on the host, keeps the most frequent patterns up to
+ *           256 KiB of table, builds the table from one representative per pattern and compares every block EXACTLY
+ *           with its pattern on the device: a block that differs (hash collision), holds more than 65535 entries or
+ *           whose pattern was not kept streams cols16 and rowptr as before.  *out == NULL with status 0 when fewer than
+ *           half of the candidates ended up in the table (unstructured matrices): launch the cols16 entry points.
+ *           HPCLA_BLOCK_PATTERNS_WEAK_HASH leaves the columns out of the hash, so that blocks with equal row lengths
+ *           collide: for tests of the exact comparison.  Synchronizes the stream.
+ *   info:   kept patterns, bytes of the table, candidate blocks, blocks that read the table.
+ *   spmv_patterns / spmv_dist_patterns / spmv_dist_dot_patterns / tune_block_order_patterns: the cols16 entry points of
+ *           the same names with the handle; patterns == NULL is exactly those.  The handle must have been created for the
+ *           same (nrows, nnz, index_base) and the same rowptr / cols16 contents.  Boundary blocks keep the Int32 kernel. */
+#define HPCLA_BLOCK_PATTERNS_WEAK_HASH 1
+typedef struct hpcla_block_patterns hpcla_block_patterns_t;
+int hpcla_block_patterns_create_i32(hpcla_block_patterns_t **out, const int32_t *rowptr, const int16_t *cols16, int64_t nrows,
+                                    int64_t nnz, int index_base, const int32_t *block_list, int64_t block_base,
+                                    int64_t n_blocks, int flags, void *stream);
+int hpcla_block_patterns_destroy(hpcla_block_patterns_t *p);
+int hpcla_block_patterns_info(const hpcla_block_patterns_t *p, int64_t *n_patterns, int64_t *table_bytes,
+                              int64_t *n_candidates, int64_t *n_patterned);
+int hpcla_spmv_patterns_f64_i32(const int32_t *rowptr, const int16_t *cols16, const hpcla_block_patterns_t *patterns,
+                                const double *nzval, const double *x, double *y, int64_t nrows, int64_t nnz, int index_base,
+                                const int32_t *block_list, int64_t n_blocks, void *stream);
+int hpcla_spmv_dist_patterns_f64_i32(hpcla_halo_plan_t *plan, const int32_t *rowptr, const int32_t *colval_split,
+                                     const int16_t *cols16, const hpcla_block_patterns_t *patterns, const double *nzval,
+                                     const double *x, int64_t n_own, double *y, int64_t nrows, int64_t nnz, int index_base,
+                                     const int32_t *interior_blocks, int64_t n_interior, const int32_t *boundary_blocks,
+                                     int64_t n_boundary, void *stream);
+int hpcla_spmv_dist_dot_patterns_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int32_t *rowptr,
+                                         const int32_t *colval_split, const int16_t *cols16,
+                                         const hpcla_block_patterns_t *patterns, const double *nzval, const double *x,
+                                         int64_t n_own, double *y, int64_t nrows, int64_t nnz, int index_base,
+                                         const int32_t *interior_blocks, int64_t n_interior,
+                                         const int32_t *boundary_blocks, int64_t n_boundary, double *dot_out_dev, void *work,
+                                         void *stream);
+int hpcla_spmv_tune_block_order_patterns_f64_i32(const int32_t *rowptr, const int16_t *cols16,
+                                                 const hpcla_block_patterns_t *patterns, const double *nzval,
+                                                 const double *x_own, double *y_scratch, int64_t nrows, int64_t nnz,
+                                                 int index_base, int64_t block_base, int64_t n_blocks, void *stream,
+                                                 int *chosen_group);
+
 /* ---- OPT-IN packed copy of the matrix for SpMV (no reference counterpart) ----------------------------
  * For matrices with <= 256 distinct values whose row blocks reach only columns within +-32 K of the
  * block's first row (stencils, graph Laplacians ...), a plan-time copy with 16-bit block-relative

@@ -21,6 +21,7 @@ WINDOW_DESC_BYTES = 128
 WINDOW_TABLE_ROWS = 4
 COMM_NO_RCCL = 1
 HALO_SINGLE_BUFFER = 1
+BLOCK_PATTERNS_WEAK_HASH = 1
 
 
 class HPCLAError(RuntimeError):
@@ -60,6 +61,11 @@ _SIGNATURES = {
     "hpcla_cols16_padded_len": [_i64],
     "hpcla_cols16_encode_i32": [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp],
     "hpcla_spmv_cols16_f64_i32": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp],
+    "hpcla_block_patterns_create_i32": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp],
+    "hpcla_block_patterns_destroy": [_vp],
+    "hpcla_block_patterns_info": [_vp, _vp, _vp, _vp, _vp],
+    "hpcla_spmv_patterns_f64_i32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp],
+    "hpcla_spmv_tune_block_order_patterns_f64_i32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i64, _i64, _vp, _vp],
     "hpcla_spmm_rows_per_block": [],
     "hpcla_spmm_runs_desc_bytes": [_i64],
     "hpcla_spmm_runs_build_i32": [_vp, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp],
@@ -129,6 +135,9 @@ _SIGNATURES = {
     "hpcla_spmv_dist_cols16_f64_i32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp],
     "hpcla_spmv_dist_dot_cols16_f64_i32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
                                            _vp, _vp, _vp],
+    "hpcla_spmv_dist_patterns_f64_i32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp],
+    "hpcla_spmv_dist_dot_patterns_f64_i32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp,
+                                             _i64, _vp, _vp, _vp],
     "hpcla_spmv_dot_work_bytes": [_i64],
     "hpcla_spmv_dist_dot_f64_i32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
     "hpcla_spmv_dist_dot_f64_i64": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp],

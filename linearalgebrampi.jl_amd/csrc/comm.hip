@@ -37,7 +37,7 @@ int spmv_split_i64(const int64_t *, const int64_t *, const double *, const doubl
 // 16-bit block-relative column copy of a plan (spmv.hip): the row-gather kernel over a list or a contiguous run of row blocks
 // whose columns are all owned and inside the int16 window
 int spmv_cols16_i32(const int32_t *, const int16_t *, const double *, const double *, double *, int64_t, int64_t, int,
-                    const int32_t *, int64_t, void *, double *, int64_t);
+                    const int32_t *, int64_t, void *, double *, int64_t, const hpcla_block_patterns *);
 bool cols16_usable(const int16_t *cols16, const double *nzval);
 int spmv_fused_i32(const int32_t *, const int32_t *, const double *, const double *, const double *, int64_t,
                    double *, int64_t, int64_t, int, const int32_t *, int64_t, int64_t, const int32_t *, int64_t,
@@ -776,11 +776,14 @@ static int spmv_dist_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, const
                           const double *nzval, const double *x, int64_t n_own, double *y,
                           int64_t nrows, int64_t nnz, int index_base, const int32_t *interior,
                           int64_t n_interior, const int32_t *boundary, int64_t n_boundary,
-                          void *stream, double *dot_partial = nullptr, const int16_t *cols16 = nullptr)
+                          void *stream, double *dot_partial = nullptr, const int16_t *cols16 = nullptr,
+                          const hpcla_block_patterns *patterns = nullptr)
 {
     // cols16 != null (Int32 plans only): the plan's 16-bit block-relative copy of the columns of its INTERIOR blocks (plans
     // without neighbours: of every block).  Those blocks then go through the narrow form of the row-gather kernel
     // (spmv_cols16_i32: 10 instead of 12 bytes per stored entry, the same bits); boundary blocks keep the Int32 kernel.
+    // patterns != null: those narrow launches take the pattern form (the plan's table of repeating block patterns,
+    // patterns.hip) -- in every ordering below the same launches with one more argument.
     const bool narrow = sizeof(I) == 4 && cols16_usable(cols16, nzval);
     // the interior blocks in the narrow form on `st`: a contiguous run by its BASE (never through the list: probe_interior)
     auto interior_narrow = [&](void *st) -> int {
@@ -789,8 +792,9 @@ static int spmv_dist_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, const
             if (int rcq = probe_interior(plan, interior, n_interior)) return rcq;
             if (plan->probed_contig)
                 return spmv_cols16_i32(rowptr, cols16, nzval, x, y, nrows, nnz, index_base, nullptr, n_interior, st, dot_partial,
-                                       plan->probed_first);
-            return spmv_cols16_i32(rowptr, cols16, nzval, x, y, nrows, nnz, index_base, interior, n_interior, st, dot_partial, -1);
+                                       plan->probed_first, patterns);
+            return spmv_cols16_i32(rowptr, cols16, nzval, x, y, nrows, nnz, index_base, interior, n_interior, st, dot_partial, -1,
+                                   patterns);
         } else {
             (void)st;
             return set_error(HPCLA_ERR_INVALID, "spmv_dist: 16-bit columns need an Int32 plan");
@@ -801,7 +805,8 @@ static int spmv_dist_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, const
         // no neighbours: every column is owned; one launch over all row blocks
         if constexpr (sizeof(I) == 4)
             if (narrow)
-                return spmv_cols16_i32(rowptr, cols16, nzval, x, y, nrows, nnz, index_base, nullptr, 0, stream, dot_partial, -1);
+                return spmv_cols16_i32(rowptr, cols16, nzval, x, y, nrows, nnz, index_base, nullptr, 0, stream, dot_partial, -1,
+                                       patterns);
         return split_fn(rowptr, colval, nzval, x, plan ? plan->ghost : nullptr, n_own, y, nrows,
                         nnz, index_base, nullptr, 0, stream, dot_partial, -1);
     }
@@ -929,7 +934,7 @@ static int spmv_dist_dot_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, h
                               double *y, int64_t nrows, int64_t nnz, int index_base,
                               const int32_t *interior, int64_t n_interior, const int32_t *boundary,
                               int64_t n_boundary, double *dot_out_dev, void *work, void *stream,
-                              const int16_t *cols16 = nullptr)
+                              const int16_t *cols16 = nullptr, const hpcla_block_patterns *patterns = nullptr)
 {
     if (!dot_out_dev || !work) return set_error(HPCLA_ERR_INVALID, "spmv_dist_dot: null out/work");
     if (n_own != nrows)
@@ -942,7 +947,7 @@ static int spmv_dist_dot_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, h
     double *scratch = reinterpret_cast<double *>(work);          // 2048 doubles of stage-1 scratch
     double *partial = scratch + 2048;                            // then one double per row block
     int rc = spmv_dist_impl<I>(split_fn, fused_fn, plan, rowptr, colval, nzval, x, n_own, y, nrows, nnz, index_base,
-                               interior, n_interior, boundary, n_boundary, stream, partial, cols16);
+                               interior, n_interior, boundary, n_boundary, stream, partial, cols16, patterns);
     if (rc) return rc;
     rc = reduce_partials_sum(partial, all_blocks, scratch, dot_out_dev, stream);
     if (rc) return rc;
@@ -1028,6 +1033,32 @@ HPCLA_API int hpcla_spmv_dist_dot_cols16_f64_i32(hpcla_halo_plan_t *plan, hpcla_
     return spmv_dist_dot_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, comm, rowptr, colval_split, nzval, x, n_own, y,
                                        nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks, n_boundary,
                                        dot_out_dev, work, stream, cols16);
+}
+
+// ... and for a plan that also holds a table of repeating block patterns over those blocks (hpcla_block_patterns_create_i32).
+// patterns == NULL: exactly the two entry points above.
+HPCLA_API int hpcla_spmv_dist_patterns_f64_i32(hpcla_halo_plan_t *plan, const int32_t *rowptr, const int32_t *colval_split,
+                                               const int16_t *cols16, const hpcla_block_patterns_t *patterns,
+                                               const double *nzval, const double *x, int64_t n_own, double *y, int64_t nrows,
+                                               int64_t nnz, int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                               const int32_t *boundary_blocks, int64_t n_boundary, void *stream)
+{
+    return spmv_dist_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, rowptr, colval_split, nzval, x, n_own, y, nrows, nnz,
+                                   index_base, interior_blocks, n_interior, boundary_blocks, n_boundary, stream, nullptr, cols16,
+                                   patterns);
+}
+
+HPCLA_API int hpcla_spmv_dist_dot_patterns_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int32_t *rowptr,
+                                                   const int32_t *colval_split, const int16_t *cols16,
+                                                   const hpcla_block_patterns_t *patterns, const double *nzval,
+                                                   const double *x, int64_t n_own, double *y, int64_t nrows, int64_t nnz,
+                                                   int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                                   const int32_t *boundary_blocks, int64_t n_boundary, double *dot_out_dev,
+                                                   void *work, void *stream)
+{
+    return spmv_dist_dot_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, comm, rowptr, colval_split, nzval, x, n_own, y,
+                                       nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks, n_boundary,
+                                       dot_out_dev, work, stream, cols16, patterns);
 }
 
 // ---- k fused CG iterations in ONE host call ----------------------------------------------------------

@@ -39,10 +39,12 @@
 
 #include "common.h"
 #include "halo_wait.h"
+#include "patterns.h"
 
 namespace hpcla {
 
 constexpr int RPB = 256;      // rows per block == threads per block
+static_assert(RPB == PAT_RPB, "the pattern table is built for this kernel's row blocks");
 constexpr int CHUNK = RPB * 8;           // unaligned fallback kernel: 2048 products parked in LDS per pass (16 KiB)
 constexpr int UNROLL = CHUNK / RPB;      // ... entries per lane per pass
 
@@ -57,13 +59,19 @@ using vec = T __attribute__((ext_vector_type(N)));
 //                       16-byte load (8-byte loads run at 0.54-0.70 x the rate of 16-byte ones on this chip) and the
 //                       position in x is r0 + d.  Only blocks whose columns are all owned and inside the window are
 //                       ever launched in this form; every column is an owned one, so there is no SPLIT form.
+//   Pat16               Cols16 whose row blocks may read their columns and row bounds from the plan's table of repeating
+//                       block patterns (patterns.hip) instead of the cols16 and rowptr streams: PATTERNS.  Per block, by
+//                       its 8-byte record -- a block that is not in the table streams exactly as under Cols16.  The table
+//                       holds col_t entries: a wider-column table is one more specialisation of this policy.
 // A further narrow form (8-bit diagonal codes through a table) is one more specialisation: col_t, VEC and decode().
 struct Cols16 {};
+struct Pat16 {};
 template <typename P>
 struct IndexPolicy {
     using row_t = P;
     using col_t = P;
     static constexpr int VEC = 4;
+    static constexpr bool PATTERNS = false;
     static __device__ __forceinline__ int64_t decode(col_t c, int base, int64_t /*r0*/) { return (int64_t)(P)(c - (P)base); }
     static __device__ __forceinline__ col_t fill(int base) { return (P)base; }
 };
@@ -72,8 +80,13 @@ struct IndexPolicy<Cols16> {
     using row_t = int32_t;
     using col_t = int16_t;
     static constexpr int VEC = 8;
+    static constexpr bool PATTERNS = false;
     static __device__ __forceinline__ int64_t decode(col_t d, int /*base*/, int64_t r0) { return r0 + (int)d; }
     static __device__ __forceinline__ col_t fill(int /*base*/) { return 0; }
+};
+template <>
+struct IndexPolicy<Pat16> : IndexPolicy<Cols16> {
+    static constexpr bool PATTERNS = true;
 };
 
 template <bool SPLIT>
@@ -182,7 +195,7 @@ __global__ __launch_bounds__(RPB) void spmv_rowgather_kernel(
     const typename IndexPolicy<I>::row_t *__restrict__ rowptr, const typename IndexPolicy<I>::col_t *__restrict__ colval,
     const double *__restrict__ nzval, const double *__restrict__ x_own, const double *x_ghost, int64_t n_own,
     double *__restrict__ y, int64_t nrows, int64_t nnz, int base,
-    BlockSel bs, double *__restrict__ dot_partial, HaloWait hw, PushArgs push, int64_t long_min = 0)
+    BlockSel bs, double *__restrict__ dot_partial, HaloWait hw, PushArgs push, int64_t long_min = 0, PatArgs pat = PatArgs{nullptr, nullptr})
 {
     using IP = IndexPolicy<I>;
     using R = typename IP::row_t;                       // row pointers
@@ -226,18 +239,48 @@ __global__ __launch_bounds__(RPB) void spmv_rowgather_kernel(
     const int nrw = nr - wave * 64 < 0 ? 0 : (nr - wave * 64 > 64 ? 64 : nr - wave * 64);
     double acc = 0.0, x_row = 0.0;
     if (nrw > 0) {                                                       // wave-uniform
-        const int64_t p0 = (int64_t)rowptr[rw] - base;
-        const int64_t p1 = (int64_t)rowptr[rw + nrw] - base;
+        // this lane's row bounds, raw and UNCONDITIONAL (lanes past the wave's last row read that row's pair: a predicated
+        // load is a branch whose merge copies the loaded register, i.e. waits for it on the spot); first used behind the A stream
+        const int ll = lane < nrw ? lane : nrw - 1;
+        int64_t p0 = 0, p1 = 0;
+        R rlo = 0, rhi = 0;
+        const C *cols = colval;                                          // where entry j's column is read: cols[j]
+        bool streamed = true;
+        R roff = 0;
+        if constexpr (IP::PATTERNS) {
+            // PATTERNS: the block's record says whether its index pattern is in the plan's table (workgroup-uniform).  If so
+            // the bounds are the block's first entry plus the table's 16-bit relative ones, and the columns are read from
+            // the table, which holds them shifted by the block's (first entry & 7): `cols` is set so that cols[j] is still
+            // entry j's column, and everything below -- the aligned 16-byte loads, the tail pass -- is the code it was.
+            // The wave's own range comes from the pattern's five 32-bit wave bounds (two SCALAR loads behind the record's:
+            // the A stream must not wait for a vector round trip to the table); the lane's pair of 16-bit bounds is ONE raw
+            // dword load that is unpacked where it is first used, behind the A stream, like the streamed row pointers.
+            const int64_t rc64 = *reinterpret_cast<const int64_t *>(pat.rec + blk);      // (one 8-byte scalar load)
+            const PatRec rc{(int32_t)rc64, (int32_t)(rc64 >> 32)};
+            if (rc.id >= 0) {
+                const int16_t *t = pat.table + (int64_t)rc.id * 8;
+                const int32_t *wb = reinterpret_cast<const int32_t *>(t + PAT_WAVE) + wave;
+                p0 = (int64_t)rc.first + wb[0];
+                p1 = (int64_t)rc.first + wb[1];                          // (rows past the block's last repeat the last bound)
+                struct __attribute__((packed, aligned(2))) Pair { uint32_t v; };
+                rlo = (R)reinterpret_cast<const Pair *>(t + wave * 64 + ll)->v;
+                roff = rc.first + base;
+                cols = t + PAT_HEAD - (rc.first & ~7);
+                streamed = false;
+            }
+        }
+        if (streamed) {
+            p0 = (int64_t)rowptr[rw] - base;
+            p1 = (int64_t)rowptr[rw + nrw] - base;
+            rlo = rowptr[rw + ll];
+            rhi = rowptr[rw + ll + 1];
+        }
         // vector-aligned start: <= V - 1 entries of the rows before.  (Cols16: when those rows belong to the row block IN FRONT,
         // their entries hold deltas relative to THAT block's first row -- and the same goes for the entries behind the wave's last
         // row in the pass's last vector.  They are staged and never gathered: a lane only walks [lo, hi) of its own row, and the
         // whole-pass branch only runs when one row of this wave owns every entry of the pass.  So no clamp of r0 + d is needed.)
         const int64_t pa = p0 & ~(int64_t)(V - 1);
         const int64_t total = p1 - pa;
-        // this lane's row bounds, raw and UNCONDITIONAL (lanes past the wave's last row read that row's pair: a predicated
-        // load is a branch whose merge copies the loaded register, i.e. waits for it on the spot); first used behind the A stream
-        const int ll = lane < nrw ? lane : nrw - 1;
-        R rlo = rowptr[rw + ll], rhi = rowptr[rw + ll + 1];
         if (dot_partial) x_row = x_own[rw + ll];                         // the epilogue's x rides along with the stream
         const bool is_long = LONGR && lane < nrw && (int64_t)rhi - (int64_t)rlo >= long_min;
         for (int64_t c = 0; c < total; c += RG_CHW) {
@@ -263,7 +306,7 @@ __global__ __launch_bounds__(RPB) void spmv_rowgather_kernel(
                 for (int u = 0; u < NV; ++u) {
                     const int e0 = (u * 64 + lane) * V;
                     const int ee = e0 < last ? e0 : last;
-                    cq[u] = *reinterpret_cast<const vec<C, V> *>(colval + pa + c + ee);
+                    cq[u] = *reinterpret_cast<const vec<C, V> *>(cols + pa + c + ee);
 #pragma unroll
                     for (int k = 0; k < V / 2; ++k)
                         va[u][k] = *reinterpret_cast<const vec<double, 2> *>(nzval + pa + c + ee + 2 * k);
@@ -283,7 +326,7 @@ __global__ __launch_bounds__(RPB) void spmv_rowgather_kernel(
                 // the padding of a column copy of the plan's own): entry by entry
                 for (int e = lane; e < n; e += 64) {
                     const int64_t g = pa + c + e;
-                    s_col[e] = g < nnz ? colval[g] : IP::fill(base);
+                    s_col[e] = g < nnz ? cols[g] : IP::fill(base);
                     s_val[e] = g < nnz ? nzval[g] : 0.0;
                 }
             }
@@ -294,8 +337,14 @@ __global__ __launch_bounds__(RPB) void spmv_rowgather_kernel(
             asm volatile("" : "+v"(rlo), "+v"(rhi));
             {
                 // (64-bit until clamped: a row of > 2^31 entries may lie in front of or behind this pass)
-                const int64_t lo64 = lane < nrw ? (int64_t)rlo - base - pa - c : 0;
-                const int64_t hi64 = lane < nrw ? (int64_t)rhi - base - pa - c : 0;
+                R blo = rlo, bhi = rhi;
+                if constexpr (IP::PATTERNS)
+                    if (!streamed) {                                     // wave-uniform: the pair of 16-bit bounds, unpacked
+                        blo = roff + (R)((uint32_t)rlo & 0xffffu);
+                        bhi = roff + (R)((uint32_t)rlo >> 16);
+                    }
+                const int64_t lo64 = lane < nrw ? (int64_t)blo - base - pa - c : 0;
+                const int64_t hi64 = lane < nrw ? (int64_t)bhi - base - pa - c : 0;
                 const int lo = lo64 < 0 ? 0 : (lo64 > n ? n : (int)lo64);
                 const int hi = hi64 < 0 ? 0 : (hi64 > n ? n : (int)hi64);
                 // ONE row owns the whole pass (a row of more than a pass's entries: round 5, the arrow matrix's dense row):
@@ -600,7 +649,7 @@ static int spmv_launch(const typename IndexPolicy<I>::row_t *rowptr, const typen
                        const double *nzval, const double *x_own,
                        const double *x_ghost, int64_t n_own, bool split, double *y, int64_t nrows,
                        int64_t nnz, int index_base, const int32_t *block_list, int64_t n_blocks,
-                       void *stream, double *dot_partial = nullptr, int64_t block_base = -1)
+                       void *stream, double *dot_partial = nullptr, int64_t block_base = -1, const PatArgs *pat = nullptr)
 {
     if (nrows < 0 || nnz < 0) return set_error(HPCLA_ERR_INVALID, "spmv: negative size");
     if (index_base != 0 && index_base != 1)
@@ -642,8 +691,12 @@ static int spmv_launch(const typename IndexPolicy<I>::row_t *rowptr, const typen
     if constexpr (std::is_same<I, Cols16>::value) {
         // the narrow form has no fallback kernel of its own: the callers send misaligned arrays down the Int32 path (cols16_usable)
         if (!aligned) return set_error(HPCLA_ERR_INVALID, "spmv: 16-bit columns need a 16-byte aligned copy and 32-byte aligned nzval");
-        spmv_rowgather_kernel<Cols16, false, false><<<grid, block, 0, s>>>(
-            rowptr, colval, nzval, x_own, nullptr, 0, y, nrows, nnz, index_base, bs, dot_partial, nowait, nopush);
+        if (pat)       // the plan holds a table of repeating block patterns: the same launch in the pattern form
+            spmv_rowgather_kernel<Pat16, false, false><<<grid, block, 0, s>>>(
+                rowptr, colval, nzval, x_own, nullptr, 0, y, nrows, nnz, index_base, bs, dot_partial, nowait, nopush, 0, *pat);
+        else
+            spmv_rowgather_kernel<Cols16, false, false><<<grid, block, 0, s>>>(
+                rowptr, colval, nzval, x_own, nullptr, 0, y, nrows, nnz, index_base, bs, dot_partial, nowait, nopush);
     } else if (aligned) {
         if (split)
             spmv_rowgather_kernel<I, true, false><<<grid, block, 0, s>>>(
@@ -781,6 +834,8 @@ int encode_cols16_i32(const int32_t *rowptr, const int32_t *colval, int64_t nrow
     return HPCLA_OK;
 }
 
+int patterns_args(const hpcla_block_patterns *p, int64_t nrows, int64_t nnz, int index_base, PatArgs *out);   // patterns.hip
+
 bool cols16_usable(const int16_t *cols16, const double *nzval)
 {
     return cols16 && reinterpret_cast<uintptr_t>(cols16) % 16 == 0 && reinterpret_cast<uintptr_t>(nzval) % 32 == 0;
@@ -788,10 +843,13 @@ bool cols16_usable(const int16_t *cols16, const double *nzval)
 
 int spmv_cols16_i32(const int32_t *rowptr, const int16_t *cols16, const double *nzval, const double *x, double *y,
                     int64_t nrows, int64_t nnz, int index_base, const int32_t *bl, int64_t nb, void *stream,
-                    double *dot_partial, int64_t block_base)
+                    double *dot_partial, int64_t block_base, const hpcla_block_patterns *patterns)
 {
+    PatArgs pa;
+    if (patterns)
+        if (const int rc = patterns_args(patterns, nrows, nnz, index_base, &pa)) return rc;
     return spmv_launch<Cols16>(rowptr, cols16, nzval, x, nullptr, 0, false, y, nrows, nnz, index_base, bl, nb, stream,
-                               dot_partial, block_base);
+                               dot_partial, block_base, patterns ? &pa : nullptr);
 }
 
 }  // namespace hpcla
@@ -820,7 +878,8 @@ template <typename I>
 static int tune_block_order(const typename IndexPolicy<I>::row_t *rowptr, const typename IndexPolicy<I>::col_t *colval_split,
                             const double *nzval, const double *x_own,
                             const double *x_ghost, int64_t n_own, double *y_scratch, int64_t nrows, int64_t nnz,
-                            int index_base, void *stream, int *chosen_group, int64_t run_base = -1, int64_t run_blocks = 0)
+                            int index_base, void *stream, int *chosen_group, int64_t run_base = -1, int64_t run_blocks = 0,
+                            const PatArgs *pat = nullptr)
 {
     if (chosen_group) *chosen_group = 1;
     if (nrows < 0 || nnz < 0 || !rowptr) return set_error(HPCLA_ERR_INVALID, "spmv_tune_block_order: bad arguments");
@@ -844,7 +903,7 @@ static int tune_block_order(const typename IndexPolicy<I>::row_t *rowptr, const 
             if (hipEventRecord(e0, s) != hipSuccess) { rc = set_error(HPCLA_ERR_HIP, "spmv_tune_block_order: event"); break; }
             for (int i = 0; i < REPS && rc == HPCLA_OK; ++i)
                 rc = spmv_launch<I>(rowptr, colval_split, nzval, x_own, x_ghost, n_own, true, y_scratch, nrows, nnz,
-                                    index_base, nullptr, run_base >= 0 ? run_blocks : 0, stream, nullptr, run_base);
+                                    index_base, nullptr, run_base >= 0 ? run_blocks : 0, stream, nullptr, run_base, pat);
             if (rc != HPCLA_OK) break;
             if (hipEventRecord(e1, s) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
                 hipEventElapsedTime(&ms[c][r], e0, e1) != hipSuccess)
@@ -897,6 +956,21 @@ HPCLA_API int hpcla_spmv_tune_block_order_cols16_f64_i32(const int32_t *rowptr, 
                                     chosen_group, block_base, n_blocks);
 }
 
+HPCLA_API int hpcla_spmv_tune_block_order_patterns_f64_i32(const int32_t *rowptr, const int16_t *cols16,
+                                                           const hpcla_block_patterns_t *patterns, const double *nzval,
+                                                           const double *x_own, double *y_scratch, int64_t nrows, int64_t nnz,
+                                                           int index_base, int64_t block_base, int64_t n_blocks, void *stream,
+                                                           int *chosen_group)
+{
+    if (!cols16_usable(cols16, nzval))
+        return set_error(HPCLA_ERR_INVALID, "spmv_tune_block_order_patterns: null or misaligned column copy / nzval");
+    PatArgs pa;
+    if (patterns)
+        if (const int rc = patterns_args(patterns, nrows, nnz, index_base, &pa)) return rc;
+    return tune_block_order<Cols16>(rowptr, cols16, nzval, x_own, nullptr, 0, y_scratch, nrows, nnz, index_base, stream,
+                                    chosen_group, block_base, n_blocks, patterns ? &pa : nullptr);
+}
+
 // ---- plan-time 16-bit column copy ----------------------------------------------------------------------------------------
 HPCLA_API int64_t hpcla_cols16_padded_len(int64_t nnz) { return cols16_padded_len(nnz > 0 ? nnz : 0); }
 
@@ -925,7 +999,16 @@ HPCLA_API int hpcla_spmv_cols16_f64_i32(const int32_t *rowptr, const int16_t *co
 {
     if (nnz > 0 && !cols16_usable(cols16, nzval))
         return set_error(HPCLA_ERR_INVALID, "spmv_cols16: null or misaligned column copy / nzval (take hpcla_spmv_split_f64_i32)");
-    return spmv_cols16_i32(rowptr, cols16, nzval, x, y, nrows, nnz, index_base, block_list, n_blocks, stream, nullptr, -1);
+    return spmv_cols16_i32(rowptr, cols16, nzval, x, y, nrows, nnz, index_base, block_list, n_blocks, stream, nullptr, -1, nullptr);
+}
+
+HPCLA_API int hpcla_spmv_patterns_f64_i32(const int32_t *rowptr, const int16_t *cols16, const hpcla_block_patterns_t *patterns,
+                                          const double *nzval, const double *x, double *y, int64_t nrows, int64_t nnz,
+                                          int index_base, const int32_t *block_list, int64_t n_blocks, void *stream)
+{
+    if (nnz > 0 && !cols16_usable(cols16, nzval))
+        return set_error(HPCLA_ERR_INVALID, "spmv_patterns: null or misaligned column copy / nzval (take hpcla_spmv_split_f64_i32)");
+    return spmv_cols16_i32(rowptr, cols16, nzval, x, y, nrows, nnz, index_base, block_list, n_blocks, stream, nullptr, -1, patterns);
 }
 
 HPCLA_API int hpcla_spmv_block_order_hint(const void *rowptr, int group)

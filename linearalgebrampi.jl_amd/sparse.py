@@ -199,6 +199,29 @@ def narrow_cols_enabled() -> bool:
     return _os.environ.get("HPCLA_NARROW_COLS", "1").strip().lower() not in ("0", "off", "false", "no")
 
 
+def block_patterns_enabled() -> bool:
+    """``HPCLA_BLOCK_PATTERNS=0`` keeps a plan that holds ``cols16`` on the streamed 16-bit column form (A/B measurements
+    against the table of repeating block patterns, ``VectorPlan.patterns``); ``HPCLA_NARROW_COLS=0`` switches both off."""
+    return narrow_cols_enabled() and _os.environ.get("HPCLA_BLOCK_PATTERNS", "1").strip().lower() not in ("0", "off", "false", "no")
+
+
+def create_block_patterns(rowptr_dev, cols16, nrows: int, nnz: int, block_list, block_base: int, n_blocks: int, flags: int = 0):
+    """Table of the repeating index patterns of the listed row blocks (``block_list`` None: the run of ``n_blocks`` from
+    ``block_base``, or all when ``block_base`` < 0) over ``cols16`` (``hpcla_block_patterns_create_i32``): the opaque handle,
+    or None when fewer than half of the blocks repeat a kept pattern (the library creates nothing then)."""
+    h = ctypes.c_void_p()
+    _capi.call("hpcla_block_patterns_create_i32", ctypes.byref(h), dptr(rowptr_dev), dptr(cols16), nrows, nnz, 0,
+               dptr(block_list) if block_list is not None else None, block_base, n_blocks, flags, current_stream_ptr())
+    return h if h else None
+
+
+def block_patterns_info(handle) -> dict:
+    """``hpcla_block_patterns_info`` as a dict: patterns, table_bytes, candidates, patterned."""
+    v = [ctypes.c_int64() for _ in range(4)]
+    _capi.call("hpcla_block_patterns_info", handle, *[ctypes.byref(c) for c in v])
+    return dict(zip(("patterns", "table_bytes", "candidates", "patterned"), (int(c.value) for c in v)))
+
+
 def encode_cols16(rowptr_dev, colval_split, nrows: int, nnz: int, n_own: int, block_list, n_blocks: int):
     """16-bit block-relative copy of ``colval_split`` for the listed row blocks (``block_list`` None: all), or None when
     the library finds a listed block with a ghost column or a column outside [r0 - 32768, r0 + 32767] of its first row
@@ -333,6 +356,14 @@ class VectorPlan:
                 and (not self.has_halo or self.n_interior > 0)):
             self.cols16 = encode_cols16(self.rowptr_of(A), self.colval_split, A.nrows_local, A.nnz, self.n_own,
                                         self.interior if self.has_halo else None, self.n_interior if self.has_halo else 0)
+        # table of the repeating block patterns behind cols16 (csrc/patterns.hip), same blocks, same conditions: structure
+        # again, nzval stays live.  A block in the table reads columns and row bounds from L2 instead of streaming them.
+        # None: no cols16, HPCLA_BLOCK_PATTERNS=0, or fewer than half of the blocks repeat (unstructured: today's kernels).
+        self.patterns = None
+        if self.cols16 is not None and block_patterns_enabled():
+            self.patterns = create_block_patterns(self.rowptr_of(A), self.cols16, A.nrows_local, A.nnz,
+                                                  self.interior if self.has_halo else None, -1,
+                                                  self.n_interior if self.has_halo else 0)
         # block order of the SpMV launches over this structure: measured once, here (hpcla_spmv_tune_block_order_*, a few
         # dozen launches into a scratch vector); HPCLA_BLOCK_ORDER=natural skips it, =<G> forces groups of G row blocks
         self.block_group = 1
@@ -362,7 +393,11 @@ class VectorPlan:
                     if last - first + 1 == self.n_interior:
                         run = (first, self.n_interior)
             try:
-                if run is not None:
+                if run is not None and self.patterns is not None:
+                    _capi.call("hpcla_spmv_tune_block_order_patterns_f64_i32", dptr(self.rowptr_of(A)), dptr(self.cols16),
+                               self.patterns, dptr(A.nzval), dptr(x.v), dptr(scratch), A.nrows_local, A.nnz, 0, run[0], run[1],
+                               s, ctypes.byref(chosen))
+                elif run is not None:
                     _capi.call("hpcla_spmv_tune_block_order_cols16_f64_i32", dptr(self.rowptr_of(A)), dptr(self.cols16),
                                dptr(A.nzval), dptr(x.v), dptr(scratch), A.nrows_local, A.nnz, 0, run[0], run[1], s,
                                ctypes.byref(chosen))
@@ -402,6 +437,9 @@ class VectorPlan:
         return halo_timed_out(self.halo)
 
     def destroy(self) -> None:
+        if getattr(self, "patterns", None) is not None:
+            _capi.call("hpcla_block_patterns_destroy", self.patterns)
+            self.patterns = None
         if self.halo:
             _capi.call("hpcla_halo_plan_destroy", self.halo)
             self.halo = ctypes.c_void_p()
@@ -418,6 +456,8 @@ def get_vector_plan(A: "HPCSparseMatrix", x: HPCVector) -> VectorPlan:
         key += ("wide",)                       # HPCLA_NARROW_INDICES=0: a plan of its own, on the Int64 kernels
     if not narrow_cols_enabled():
         key += ("cols32",)                     # HPCLA_NARROW_COLS=0: a plan of its own, without the 16-bit column copy
+    elif not block_patterns_enabled():
+        key += ("nopat",)                      # HPCLA_BLOCK_PATTERNS=0: a plan of its own, cols16 streamed, no pattern table
     plan = _vector_plan_cache.get(key)
     if plan is None:
         plan = VectorPlan(A, x)
@@ -816,6 +856,12 @@ def _spmv_into(y: HPCVector, A: HPCSparseMatrix, x: HPCVector, plan: VectorPlan)
                    None, plan.n_own, dptr(y.v), A.nrows_local, A.nnz, 0, dptr(rows), int(rows.numel()), min_len, dptr(work),
                    current_stream_ptr())
         return
+    if plan.patterns is not None:                         # ... the same, blocks that repeat a pattern reading the plan's table
+        _capi.call("hpcla_spmv_dist_patterns_f64_i32", plan.halo if plan.has_halo else None,
+                   dptr(plan.rowptr_of(A)), dptr(plan.colval_split), dptr(plan.cols16), plan.patterns, dptr(A.nzval), dptr(x.v),
+                   plan.n_own, dptr(y.v), A.nrows_local, A.nnz, 0, dptr(plan.interior), plan.n_interior,
+                   dptr(plan.boundary), plan.n_boundary, current_stream_ptr())
+        return
     if plan.cols16 is not None:                           # interior blocks on 16-bit columns, boundary blocks on Int32
         _capi.call("hpcla_spmv_dist_cols16_f64_i32", plan.halo if plan.has_halo else None,
                    dptr(plan.rowptr_of(A)), dptr(plan.colval_split), dptr(plan.cols16), dptr(A.nzval), dptr(x.v), plan.n_own,
@@ -873,6 +919,12 @@ def mul_dot_(y: HPCVector, A: HPCSparseMatrix, x: HPCVector, out) -> HPCVector:
     if pk is not None:
         _capi.call("hpcla_spmv_dist_packed_f64_i32", plan.halo if plan.has_halo else None, A.backend.rccl,
                    pk, dptr(plan.rowptr_of(A)), dptr(plan.colval_split), dptr(A.nzval), dptr(x.v),
+                   plan.n_own, dptr(y.v), A.nrows_local, A.nnz, 0, dptr(plan.interior), plan.n_interior,
+                   dptr(plan.boundary), plan.n_boundary, dptr(out), dptr(work), current_stream_ptr())
+        return y
+    if plan.patterns is not None:
+        _capi.call("hpcla_spmv_dist_dot_patterns_f64_i32", plan.halo if plan.has_halo else None, A.backend.rccl,
+                   dptr(plan.rowptr_of(A)), dptr(plan.colval_split), dptr(plan.cols16), plan.patterns, dptr(A.nzval), dptr(x.v),
                    plan.n_own, dptr(y.v), A.nrows_local, A.nnz, 0, dptr(plan.interior), plan.n_interior,
                    dptr(plan.boundary), plan.n_boundary, dptr(out), dptr(work), current_stream_ptr())
         return y
