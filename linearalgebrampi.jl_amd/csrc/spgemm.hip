@@ -240,8 +240,10 @@ __global__ __launch_bounds__(256) void spgemm_esc_kernel(
             }
         }
     }
-    // combine runs of equal columns in slot (= ascending k) order
-    const bool valid = key != INVALID;
+    // combine runs of equal columns in slot (= ascending k) order.  The row's base_slot products now sit in its first
+    // base_slot lanes.  (Not `key != INVALID`: at L = 64 the key of slot 63 in column 2^58 - 1 IS all ones -- a row with
+    // that product has 64 of them, so no padding lane to confuse it with.)
+    const bool valid = t < base_slot;
     const unsigned long long col = key >> 6;
     const unsigned long long pcol = __shfl_up(col, 1, L);
     const bool pvalid = __shfl_up((int)valid, 1, L) != 0;
