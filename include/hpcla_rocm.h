@@ -219,6 +219,57 @@ int64_t hpcla_poisson3d_nnz(int64_t nx, int64_t ny, int64_t nz, int64_t row_star
 int hpcla_gen_poisson3d(int64_t nx, int64_t ny, int64_t nz, int64_t row_start, int64_t row_end,
                         int64_t *rowptr_out, int64_t *colidx_out, double *vals_out, void *stream);
 
+/* ---- range indexing of a sparse matrix: A[r0:r1, c0:c1] and A[:, k] (csrc/submatrix.hip) ------------------------
+ * Replaces the host walk over `_get_csc(A)` of Base.getindex(A::HPCSparseMatrix, ::UnitRange, ::UnitRange)
+ * (src/indexing.jl:691-840: count and collect :775-794, per-row sort :796-805, recompression :807-819) and of
+ * Base.getindex(A, :, k) (src/indexing.jl:872-914, the scan :891-908).  No communication, as in the reference
+ * (_compute_subpartition, src/indexing.jl:38-62, stays on the host).
+ *
+ * Relies on the struct's invariants: col_indices sorted, so a global column window is ONE window [j0, j1) of compressed
+ * local columns; columns ascending within a row (src/sparse.jl:288-295), so a row keeps ONE contiguous run of its entries.
+ * The windows are 0-based and half-open whatever `index_base` is: local rows [r0, r1) of [0, nrows], local compressed
+ * columns [j0, j1).  rowptr / colval (in and out) carry `index_base`; src_start is always a 0-based entry position.
+ * Values are moved by size: elem_bytes = 8 (Float64) or 4 (Float32); every bit of a kept entry survives.
+ *
+ * structure: src_start_out[i] / rowptr_out[i] for the r1 - r0 selected rows (rowptr_out has r1 - r0 + 1 entries),
+ *   col_indices_out (device int64, capacity j1 - j0): the kept columns that occur, ascending, as
+ *   col_indices_src[j] - col_shift (col_indices_src: the source's global column ids on the device; NULL: the local j).
+ *   Returns the new nnz and the new compressed column count to the host: synchronises the stream once, like
+ *   hpcla_compress_columns_*.  `work`: hpcla_submatrix_work_bytes(r1 - r0, j1 - j0) device bytes; it holds the column
+ *   look-up table that `fill` reads, so it must live until the fill has run.
+ * fill: colval_out / nzval_out (nnz_out entries each) from the structure pass's outputs.  No synchronisation.
+ * values: nzval_out alone, from the src_start and rowptr_out of an earlier extraction (the source may be any matrix of
+ *   the same structure).  No synchronisation.
+ * hpcla_submatrix_scan_chunk: elements per workgroup of the scan behind rowptr_out and col_indices_out (tests cross it). */
+int64_t hpcla_submatrix_work_bytes(int64_t nsel, int64_t width);
+int64_t hpcla_submatrix_scan_chunk(void);
+int hpcla_submatrix_structure_i32(const int32_t *rowptr, const int32_t *colval, int64_t nrows, int64_t nnz, int64_t r0,
+                                  int64_t r1, int64_t j0, int64_t j1, int index_base, const int64_t *col_indices_src,
+                                  int64_t col_shift, int64_t *src_start_out, int32_t *rowptr_out, int64_t *col_indices_out,
+                                  int64_t *nnz_out_host, int64_t *ncols_out_host, void *work, void *stream);
+int hpcla_submatrix_structure_i64(const int64_t *rowptr, const int64_t *colval, int64_t nrows, int64_t nnz, int64_t r0,
+                                  int64_t r1, int64_t j0, int64_t j1, int index_base, const int64_t *col_indices_src,
+                                  int64_t col_shift, int64_t *src_start_out, int64_t *rowptr_out, int64_t *col_indices_out,
+                                  int64_t *nnz_out_host, int64_t *ncols_out_host, void *work, void *stream);
+int hpcla_submatrix_fill_i32(int elem_bytes, const int32_t *colval, const void *nzval, int64_t nnz_src,
+                             const int64_t *src_start, const int32_t *rowptr_out, int64_t nsel, int64_t nnz_out, int64_t j0,
+                             int64_t j1, int index_base, const void *work, int32_t *colval_out, void *nzval_out, void *stream);
+int hpcla_submatrix_fill_i64(int elem_bytes, const int64_t *colval, const void *nzval, int64_t nnz_src,
+                             const int64_t *src_start, const int64_t *rowptr_out, int64_t nsel, int64_t nnz_out, int64_t j0,
+                             int64_t j1, int index_base, const void *work, int64_t *colval_out, void *nzval_out, void *stream);
+int hpcla_submatrix_values_i32(int elem_bytes, const void *nzval, int64_t nnz_src, const int64_t *src_start,
+                               const int32_t *rowptr_out, int64_t nsel, int64_t nnz_out, int index_base, void *nzval_out,
+                               void *stream);
+int hpcla_submatrix_values_i64(int elem_bytes, const void *nzval, int64_t nnz_src, const int64_t *src_start,
+                               const int64_t *rowptr_out, int64_t nsel, int64_t nnz_out, int index_base, void *nzval_out,
+                               void *stream);
+/* A[:, k] (src/indexing.jl:891-908): out[i] = the stored value of local compressed column jk (0-based) in local row i,
+ * +0.0 where the row stores none.  The caller handles a k that is not among col_indices (all zeros, no kernel). */
+int hpcla_sparse_column_i32(int elem_bytes, const int32_t *rowptr, const int32_t *colval, const void *nzval, int64_t nrows,
+                            int64_t nnz, int64_t jk, int index_base, void *out, void *stream);
+int hpcla_sparse_column_i64(int elem_bytes, const int64_t *rowptr, const int64_t *colval, const void *nzval, int64_t nrows,
+                            int64_t nnz, int64_t jk, int index_base, void *out, void *stream);
+
 /* ---- SpGEMM local product (sparse x sparse): replaces the CPU SparseArrays multiply inside
  * Base.:*(A::HPCSparseMatrix, B::HPCSparseMatrix) (`CT = plan.AT * A_csc`, src/sparse.jl:991-1059).
  * G = the rows of B named by A.col_indices, gathered by the MatrixPlan (src/sparse.jl:554-978), as

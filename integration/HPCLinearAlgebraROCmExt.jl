@@ -996,6 +996,91 @@ function HPCLinearAlgebra.HPCSparseMatrix_local(A_local::HPCLinearAlgebra.Sparse
                                    nothing, nothing, rowptr_target, colval_target, backend)
 end
 
+# ==== A[rows, cols] and A[:, k] on the device  (replace the host walks over `_get_csc(A)` of src/indexing.jl:691-840, 872-914) ==
+# The parent counts, collects, sorts and recompresses the kept entries one by one on the host (:775-819) and scans every row
+# for column k (:891-908): on a device backend that is scalar indexing of device arrays or a round trip of the matrix.  Here:
+# col_indices is sorted, so the column range is ONE window [j0, j1) of compressed local columns (two binary searches on the
+# host); columns ascend within a row (src/sparse.jl:288-295), so a row keeps ONE contiguous run.  hpcla_submatrix_structure_*
+# locates the runs, scans the counts into the new rowptr and a presence bitmap into the column look-up table; one coalesced
+# hpcla_submatrix_fill_* copies nzval and writes the recompressed colval (csrc/submatrix.hip).  No communication, as in the
+# parent: the row partition is _compute_subpartition's.  The values never leave the device; the struct's host fields (rowptr,
+# colval, col_indices: "always CPU") come back once per call -- that is the struct's contract, not staging of the values.
+# The parent's `:` convenience methods (:843-855) land on the first method.  Empty and out-of-bounds ranges, and index types
+# other than Int32 / Int64, are the parent's (its empty matrix has a uniform row partition, :709-724).
+# Mirrors linearalgebrampi.jl_amd/indexing.py, which the GPU tests hold to a numpy restatement bit for bit.
+const _MovedBits = Union{Float32,Float64}         # the kernels move values by size (4 or 8 bytes) and never compute with them
+function Base.getindex(A::HPCSparseMatrix{T,Ti,B}, row_rng::UnitRange{Int}, col_rng::UnitRange{Int}) where {T<:_MovedBits,Ti<:Union{Int32,Int64},B<:ROCBackend}
+    m, n = size(A)
+    (first(row_rng) < 1 || last(row_rng) > m || first(col_rng) < 1 || last(col_rng) > n || isempty(row_rng) || isempty(col_rng)) &&
+        return invoke(Base.getindex, Tuple{HPCSparseMatrix,UnitRange{Int},UnitRange{Int}}, A, row_rng, col_rng)   # PCIe: none -- the parent's error, or its empty matrix (src/indexing.jl:709-724): no stored entry is involved
+    comm = A.backend.comm; rank = comm_rank(comm); nranks = comm_size(comm)
+    new_row_partition = HPCLinearAlgebra._compute_subpartition(A.row_partition, row_rng)
+    new_col_partition = HPCLinearAlgebra.uniform_partition(length(col_rng), nranks)
+    my_start = A.row_partition[rank+1]
+    lo = max(my_start, first(row_rng)); hi = min(A.row_partition[rank+2] - 1, last(row_rng))
+    r0 = lo <= hi ? lo - my_start : 0                       # this rank's rows of the range: local, 0-based, half-open [r0, r1)
+    r1 = lo <= hi ? hi - my_start + 1 : 0
+    j0 = searchsortedfirst(A.col_indices, first(col_rng)) - 1          # compressed local columns [j0, j1), 0-based
+    j1 = searchsortedfirst(A.col_indices, last(col_rng) + 1) - 1
+    nsel = r1 - r0; width = j1 - j0; nnz = length(A.nzval); eb = Cint(T === Float64 ? 8 : 4)
+    work = ROCVector{UInt8}(undef, @ccall LIB.hpcla_submatrix_work_bytes(nsel::Int64, width::Int64)::Int64)
+    src_start = ROCVector{Int64}(undef, nsel); rowptr_target = ROCVector{Ti}(undef, nsel + 1)
+    kept_dev = ROCVector{Int64}(undef, width)
+    new_nnz = Ref{Int64}(0); ncomp = Ref{Int64}(0)
+    # rowptr_target / colval_target are 1-based (index_base = 1); col_indices_src = NULL: the kept LOCAL columns come back
+    if Ti === Int32
+        _check(@ccall(LIB.hpcla_submatrix_structure_i32(_ptr(A.rowptr_target)::Ptr{Cvoid}, _ptr(A.colval_target)::Ptr{Cvoid},
+               A.nrows_local::Int64, nnz::Int64, r0::Int64, r1::Int64, j0::Int64, j1::Int64, 1::Cint, C_NULL::Ptr{Cvoid}, 0::Int64,
+               _ptr(src_start)::Ptr{Cvoid}, _ptr(rowptr_target)::Ptr{Cvoid}, _ptr(kept_dev)::Ptr{Cvoid}, new_nnz::Ptr{Int64},
+               ncomp::Ptr{Int64}, _ptr(work)::Ptr{Cvoid}, _stream()::Ptr{Cvoid})::Cint), "hpcla_submatrix_structure_i32")
+    else
+        _check(@ccall(LIB.hpcla_submatrix_structure_i64(_ptr(A.rowptr_target)::Ptr{Cvoid}, _ptr(A.colval_target)::Ptr{Cvoid},
+               A.nrows_local::Int64, nnz::Int64, r0::Int64, r1::Int64, j0::Int64, j1::Int64, 1::Cint, C_NULL::Ptr{Cvoid}, 0::Int64,
+               _ptr(src_start)::Ptr{Cvoid}, _ptr(rowptr_target)::Ptr{Cvoid}, _ptr(kept_dev)::Ptr{Cvoid}, new_nnz::Ptr{Int64},
+               ncomp::Ptr{Int64}, _ptr(work)::Ptr{Cvoid}, _stream()::Ptr{Cvoid})::Cint), "hpcla_submatrix_structure_i64")
+    end
+    colval_target = ROCVector{Ti}(undef, new_nnz[]); nzval = similar(A.nzval, new_nnz[])
+    if Ti === Int32
+        _check(@ccall(LIB.hpcla_submatrix_fill_i32(eb::Cint, _ptr(A.colval_target)::Ptr{Cvoid}, _ptr(A.nzval)::Ptr{Cvoid}, nnz::Int64,
+               _ptr(src_start)::Ptr{Cvoid}, _ptr(rowptr_target)::Ptr{Cvoid}, nsel::Int64, new_nnz[]::Int64, j0::Int64, j1::Int64,
+               1::Cint, _ptr(work)::Ptr{Cvoid}, _ptr(colval_target)::Ptr{Cvoid}, _ptr(nzval)::Ptr{Cvoid}, _stream()::Ptr{Cvoid})::Cint),
+               "hpcla_submatrix_fill_i32")
+    else
+        _check(@ccall(LIB.hpcla_submatrix_fill_i64(eb::Cint, _ptr(A.colval_target)::Ptr{Cvoid}, _ptr(A.nzval)::Ptr{Cvoid}, nnz::Int64,
+               _ptr(src_start)::Ptr{Cvoid}, _ptr(rowptr_target)::Ptr{Cvoid}, nsel::Int64, new_nnz[]::Int64, j0::Int64, j1::Int64,
+               1::Cint, _ptr(work)::Ptr{Cvoid}, _ptr(colval_target)::Ptr{Cvoid}, _ptr(nzval)::Ptr{Cvoid}, _stream()::Ptr{Cvoid})::Cint),
+               "hpcla_submatrix_fill_i64")
+    end
+    kept = Array(kept_dev[1:ncomp[]])                       # PCIe: 8 B per kept column -- the struct's host col_indices (which local columns occur)
+    col_indices = A.col_indices[kept .+ 1] .- (first(col_rng) - 1)     # global columns of the result, 1-based, ascending (:807-819)
+    rowptr = Array(rowptr_target)                           # PCIe: (rows + 1) index words -- the struct's host rowptr ("always CPU")
+    colval = Array(colval_target)                           # PCIe: one index word per kept entry -- the struct's host colval; nzval stays on the device
+    return HPCSparseMatrix{T,Ti,B}(nothing, new_row_partition, new_col_partition, col_indices, rowptr, colval, nzval, nsel, length(col_indices),
+                                   nothing, nothing, rowptr_target, colval_target, A.backend)
+end
+
+function Base.getindex(A::HPCSparseMatrix{T,Ti,B}, ::Colon, k::Integer) where {T<:_MovedBits,Ti<:Union{Int32,Int64},B<:ROCBackend}
+    m, n = size(A)
+    (k < 1 || k > n) && error("HPCSparseMatrix column index out of bounds: k=$k, ncols=$n")
+    jk = searchsortedfirst(A.col_indices, k)                # 1-based local column, if this rank stores column k at all
+    has_col = jk <= length(A.col_indices) && A.col_indices[jk] == k
+    # not stored on this rank: all zeros, no kernel (:888-894); else one look-up per row writes every element
+    out = (has_col && A.nrows_local > 0) ? similar(A.nzval, A.nrows_local) : AMDGPU.zeros(T, A.nrows_local)
+    if has_col && A.nrows_local > 0
+        nnz = length(A.nzval); eb = Cint(T === Float64 ? 8 : 4)
+        if Ti === Int32
+            _check(@ccall(LIB.hpcla_sparse_column_i32(eb::Cint, _ptr(A.rowptr_target)::Ptr{Cvoid}, _ptr(A.colval_target)::Ptr{Cvoid},
+                   _ptr(A.nzval)::Ptr{Cvoid}, A.nrows_local::Int64, nnz::Int64, (jk - 1)::Int64, 1::Cint, _ptr(out)::Ptr{Cvoid},
+                   _stream()::Ptr{Cvoid})::Cint), "hpcla_sparse_column_i32")
+        else
+            _check(@ccall(LIB.hpcla_sparse_column_i64(eb::Cint, _ptr(A.rowptr_target)::Ptr{Cvoid}, _ptr(A.colval_target)::Ptr{Cvoid},
+                   _ptr(A.nzval)::Ptr{Cvoid}, A.nrows_local::Int64, nnz::Int64, (jk - 1)::Int64, 1::Cint, _ptr(out)::Ptr{Cvoid},
+                   _stream()::Ptr{Cvoid})::Cint), "hpcla_sparse_column_i64")
+        end
+    end
+    return HPCVector{T,B}(_partition_hash(A.row_partition), copy(A.row_partition), out, A.backend)
+end
+
 # ==== sparse A * B  (SURVEY 8f rank 3; replaces the CPU SparseArrays multiply inside src/sparse.jl:991-1059) ===============
 # The parent's memoized MatrixPlan (src/sparse.jl:554-978) keeps gathering the rows of B that A.col_indices names; its
 # execute_plan! takes a device target (:917-975), so the gathered values are written into device memory.  What changes is the

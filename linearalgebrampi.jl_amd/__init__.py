@@ -11,6 +11,7 @@ Layout
   dense.py           HPCMatrix, dense A*x and transpose(A)*x, transpose(X)*Y, X*A and transpose(X)*A
   spmm_plans.py      A*B for a sparse A and a dense B (SpMM): exchange entries, sequential and panel orders
   cg.py              fixed-iteration CG harness
+  indexing.py        v[a:b], X[r, c], A[r, c], A[:, k] and SubmatrixPlan (csrc/submatrix.hip)
   transpose.py matmat.py addition.py repartition.py   the SURVEY 8f "next" rows and their plans
 
 The directory name contains a dot, so it is imported through the top-level alias module
@@ -21,7 +22,7 @@ from .backends import (AbstractComm, AbstractDevice, CommSerial, CommTorch, Devi
                        SolverNone, assert_backends_compatible, backend_rocm_mpi,
                        backend_rocm_serial, backends_compatible, comm_exchange_arrays, comm_rank, comm_size,
                        cpu_version, eltype_backend, indextype_backend)
-from .partition import (compute_partition_hash, compute_structural_hash, owner_of,
+from .partition import (compute_partition_hash, compute_structural_hash, local_window, owner_of, subpartition,
                         uniform_partition)
 from .vectors import HPCVector, HPCVector_local, cg_direction_, cg_residual_, cg_update_, dot, maximum, minimum, norm, prod, vsum
 from .sparse import (HPCSparseMatrix, HPCSparseMatrix_from_global, HPCSparseMatrix_local,
@@ -39,6 +40,7 @@ from .transpose import (HostTransposeStructure, TransposedHPCSparseMatrix, Trans
                         DenseTransposeLists, HostSpmmTPlan, adjoint, clear_transpose_plan_cache, get_transpose_plan,
                         transpose)
 from .addition import add_scaled_identity, sparse_add
+from .indexing import SubmatrixPlan, get_submatrix_plan
 from .repartition import (RangePlan, SparseRepartitionPlan, clear_repartition_cache, exchange_ranges,
                           get_sparse_repartition_plan, get_vector_repartition_plan, repartition)
 

@@ -151,6 +151,17 @@ _SIGNATURES = {
     "hpcla_colspace_work_bytes": [_i64],
     "hpcla_compress_columns_i32": [_vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
     "hpcla_compress_columns_i64": [_vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
+    # range indexing of a sparse matrix (csrc/submatrix.hip)
+    "hpcla_submatrix_work_bytes": [_i64, _i64],
+    "hpcla_submatrix_scan_chunk": [],
+    "hpcla_submatrix_structure_i32": [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "hpcla_submatrix_structure_i64": [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "hpcla_submatrix_fill_i32": [_i32, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp],
+    "hpcla_submatrix_fill_i64": [_i32, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp],
+    "hpcla_submatrix_values_i32": [_i32, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp],
+    "hpcla_submatrix_values_i64": [_i32, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp],
+    "hpcla_sparse_column_i32": [_i32, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp],
+    "hpcla_sparse_column_i64": [_i32, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp],
     "hpcla_digest_i32": [_vp, _i64, _vp, _vp],
     "hpcla_digest_i64": [_vp, _i64, _vp, _vp],
     "hpcla_poisson2d_nnz": [_i64, _i64, _i64, _i64],
@@ -230,6 +241,8 @@ _RESTYPES = {
     "hpcla_reduce_work_bytes": _i64,
     "hpcla_spmv_dot_work_bytes": _i64,
     "hpcla_colspace_work_bytes": _i64,
+    "hpcla_submatrix_work_bytes": _i64,
+    "hpcla_submatrix_scan_chunk": _i64,
     "hpcla_poisson2d_nnz": _i64,
     "hpcla_poisson3d_nnz": _i64,
     "hpcla_spgemm_bin_cap": _i64,

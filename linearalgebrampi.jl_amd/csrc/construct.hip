@@ -6,12 +6,9 @@
 // Here: a presence bitmap over the column window, one exclusive scan, one emit pass -- O(nnz + window),
 // milliseconds, same result (sorted unique global columns, local = rank in that list).
 #include "common.h"
+#include "scan.h"
 
 namespace hpcla {
-
-constexpr int SCAN_T = 256;
-constexpr int SCAN_E = 4;                       // elements per thread
-constexpr int SCAN_B = SCAN_T * SCAN_E;         // 1024 elements per block
 
 __global__ __launch_bounds__(256) void mark_present_kernel(const int64_t *__restrict__ col,
                                                            int64_t nnz, int64_t lo, int64_t window,
@@ -27,89 +24,22 @@ __global__ __launch_bounds__(256) void mark_present_kernel(const int64_t *__rest
     }
 }
 
-// block-local inclusive scan of SCAN_B flags; writes the block total
-__device__ __forceinline__ int64_t block_exclusive_scan(int64_t v, int64_t *s_warp, int64_t *total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int64_t inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int64_t t = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += t;
+// the scan's functors (scan.h): a present flag counts 1; element i learns its rank among the present columns and a present
+// one writes its global id at that rank
+struct PresentLoad {
+    const unsigned char *flags;
+    __device__ int64_t operator()(int64_t i) const { return flags[i] ? 1 : 0; }
+};
+struct RankEmit {
+    int64_t lo;
+    int64_t *rank;
+    int64_t *col_indices;
+    __device__ void operator()(int64_t i, int64_t before, int64_t present) const
+    {
+        rank[i] = before;
+        if (present && col_indices) col_indices[before] = lo + i;
     }
-    if (lane == 63) s_warp[w] = inc;
-    __syncthreads();
-    int64_t base = 0;
-    for (int k = 0; k < w; ++k) base += s_warp[k];
-    if (total) {
-        int64_t tot = 0;
-        for (int k = 0; k < SCAN_T / 64; ++k) tot += s_warp[k];
-        *total = tot;
-    }
-    __syncthreads();
-    return base + inc - v;
-}
-
-__global__ __launch_bounds__(SCAN_T) void scan_phase1_kernel(const unsigned char *__restrict__ flags,
-                                                             int64_t n, int64_t *__restrict__ block_sums)
-{
-    __shared__ int64_t s_warp[SCAN_T / 64];
-    const int64_t b0 = (int64_t)blockIdx.x * SCAN_B + (int64_t)threadIdx.x * SCAN_E;
-    int64_t v = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_E; ++k)
-        if (b0 + k < n) v += flags[b0 + k] ? 1 : 0;
-    int64_t tot;
-    (void)block_exclusive_scan(v, s_warp, &tot);
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
-}
-
-// one block scans all block sums in place (exclusive), returns the grand total in total[0]
-__global__ __launch_bounds__(SCAN_T) void scan_phase2_kernel(int64_t *__restrict__ block_sums, int64_t nb,
-                                                             int64_t *__restrict__ total)
-{
-    __shared__ int64_t s_warp[SCAN_T / 64];
-    __shared__ int64_t s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (int64_t c = 0; c < nb; c += SCAN_T) {
-        const int64_t i = c + threadIdx.x;
-        const int64_t v = i < nb ? block_sums[i] : 0;
-        int64_t tot;
-        const int64_t ex = block_exclusive_scan(v, s_warp, &tot);
-        const int64_t carry = s_carry;
-        if (i < nb) block_sums[i] = carry + ex;
-        __syncthreads();
-        if (threadIdx.x == 0) s_carry = carry + tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) total[0] = s_carry;
-}
-
-// rank[i] = number of present flags before i (exclusive), for every i in the window
-__global__ __launch_bounds__(SCAN_T) void scan_phase3_kernel(const unsigned char *__restrict__ flags,
-                                                             int64_t n, const int64_t *__restrict__ block_offs,
-                                                             int64_t lo, int64_t *__restrict__ rank,
-                                                             int64_t *__restrict__ col_indices)
-{
-    __shared__ int64_t s_warp[SCAN_T / 64];
-    const int64_t b0 = (int64_t)blockIdx.x * SCAN_B + (int64_t)threadIdx.x * SCAN_E;
-    int f[SCAN_E];
-    int64_t v = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_E; ++k) {
-        f[k] = (b0 + k < n && flags[b0 + k]) ? 1 : 0;
-        v += f[k];
-    }
-    int64_t pos = block_offs[blockIdx.x] + block_exclusive_scan(v, s_warp, nullptr);
-#pragma unroll
-    for (int k = 0; k < SCAN_E; ++k) {
-        if (b0 + k < n) {
-            rank[b0 + k] = pos;
-            if (f[k]) { if (col_indices) col_indices[pos] = lo + b0 + k; ++pos; }
-        }
-    }
-}
+};
 
 template <typename I>
 __global__ __launch_bounds__(256) void emit_colval_kernel(const int64_t *__restrict__ col, int64_t nnz,
@@ -242,12 +172,8 @@ static int colspace_impl(const int64_t *colidx_global, int64_t nnz, int64_t col_
         mark_present_kernel<<<grid_for(nnz), 256, 0, s>>>(colidx_global, nnz, col_lo, window, present, err);
         HPCLA_CHECK_LAUNCH();
     }
-    scan_phase1_kernel<<<(uint32_t)nb, SCAN_T, 0, s>>>(present, window, block_sums);
-    HPCLA_CHECK_LAUNCH();
-    scan_phase2_kernel<<<1, SCAN_T, 0, s>>>(block_sums, nb, total);
-    HPCLA_CHECK_LAUNCH();
-    scan_phase3_kernel<<<(uint32_t)nb, SCAN_T, 0, s>>>(present, window, block_sums, col_lo, rank, col_indices_out);
-    HPCLA_CHECK_LAUNCH();
+    if (int rc = exclusive_scan(PresentLoad{present}, window, RankEmit{col_lo, rank, col_indices_out}, block_sums, total, s))
+        return rc;
     if (nnz > 0) {
         emit_colval_kernel<I><<<grid_for(nnz), 256, 0, s>>>(colidx_global, nnz, col_lo, rank, colval_out, index_base);
         HPCLA_CHECK_LAUNCH();

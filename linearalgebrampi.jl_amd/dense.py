@@ -88,10 +88,14 @@ class HPCMatrix:
 
     def __getitem__(self, key):
         """``A[:, k]`` (src/indexing.jl:385-393): column k (0-based here) as an HPCVector on A's row
-        partition -- the operand of the reference's SpMM column loop.  Stays on the device."""
+        partition -- the operand of the reference's SpMM column loop.  Stays on the device.  Two ranges,
+        ``A[r0:r1, c0:c1]`` and the ``:`` forms (src/indexing.jl:300-369), give the block as an HPCMatrix (indexing.py)."""
         from .vectors import HPCVector
         if not (isinstance(key, tuple) and len(key) == 2 and key[0] == slice(None) and isinstance(key[1], (int, np.integer))):
-            raise TypeError("HPCMatrix indexing supports A[:, k] only")
+            if isinstance(key, tuple) and len(key) == 2 and isinstance(key[0], slice) and isinstance(key[1], slice):
+                from .indexing import dense_getitem
+                return dense_getitem(self, key)
+            raise TypeError("HPCMatrix indexing supports A[:, k] and A[rows, cols] with unit-step ranges only")
         k, n = int(key[1]), int(self.A.shape[1])
         if k < 0 or k >= n:
             raise IndexError(f"HPCMatrix column index out of bounds: k={k}, ncols={n}")

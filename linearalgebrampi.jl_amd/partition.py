@@ -101,3 +101,24 @@ def owner_of(partition: np.ndarray, gidx: np.ndarray) -> np.ndarray:
     nranks = len(partition) - 1
     own = np.searchsorted(partition, gidx, side="right") - 1
     return np.minimum(own, nranks - 1)
+
+
+def local_window(partition: np.ndarray, rank: int, start: int, stop: int):
+    """Rank ``rank``'s part of the global range ``[start, stop)`` as LOCAL offsets ``(lo, hi)`` into its slice
+    (src/indexing.jl:100-115: ``intersect_start - my_start``); ``lo == hi`` when the rank owns nothing of the range."""
+    my_start, my_end = int(partition[rank]), int(partition[rank + 1])
+    lo, hi = max(my_start, int(start)), min(my_end, int(stop))
+    if lo >= hi:
+        return 0, 0
+    return lo - my_start, hi - my_start
+
+
+def subpartition(partition: np.ndarray, start: int, stop: int) -> np.ndarray:
+    """``_compute_subpartition(partition, rng)`` (src/indexing.jl:38-62) for the 0-based half-open range
+    ``[start, stop)``: every rank keeps the intersection of its slice with the range; no communication."""
+    nranks = len(partition) - 1
+    new = np.zeros(nranks + 1, dtype=np.int64)
+    for r in range(nranks):
+        lo, hi = local_window(partition, r, start, stop)
+        new[r + 1] = new[r] + (hi - lo)
+    return new

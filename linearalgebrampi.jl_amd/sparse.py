@@ -821,6 +821,12 @@ class HPCSparseMatrix:
         part = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         return vnorm(HPCVector(compute_partition_hash(part), part, self.nzval, self.backend), p)
 
+    def __getitem__(self, key):
+        """``A[r0:r1, c0:c1]`` (and the ``:`` forms) as an HPCSparseMatrix, ``A[:, k]`` as an HPCVector
+        (src/indexing.jl:691-914), cut on the device (indexing.py, csrc/submatrix.hip)."""
+        from .indexing import sparse_getitem
+        return sparse_getitem(self, key)
+
     def __add__(self, other):
         if isinstance(other, HPCSparseMatrix):
             from .addition import sparse_add

@@ -127,6 +127,11 @@ class HPCVector:
     def local_length(self) -> int:
         return int(self.v.numel())
 
+    def __getitem__(self, key):
+        """``v[a:b]`` (src/indexing.jl:79-121): the sub-vector on the sub-partition, copied on the device."""
+        from .indexing import vector_getitem
+        return vector_getitem(self, key)
+
     # -- host views (parity checks only) -------------------------------------------------------------
     def local_values(self) -> np.ndarray:
         """test/test_utils.jl:235-243 ``local_values``: Array(v.v)."""
