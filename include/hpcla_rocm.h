@@ -269,6 +269,17 @@ int hpcla_sparse_column_i32(int elem_bytes, const int32_t *rowptr, const int32_t
                             int64_t nnz, int64_t jk, int index_base, void *out, void *stream);
 int hpcla_sparse_column_i64(int elem_bytes, const int64_t *rowptr, const int64_t *colval, const void *nzval, int64_t nrows,
                             int64_t nnz, int64_t jk, int index_base, void *out, void *stream);
+/* diag(A) (LinearAlgebra.diag on a square HPCSparseMatrix): out[i] = the stored value of (i, row_start + i) bit for bit,
+ * +0.0 where the row stores none; i is the local row, row_start this rank's first global row (0-based), col_indices
+ * (n_col_indices sorted global column ids, 0-based, device memory) the matrix's compressed-column table.  One lane per
+ * row, the look-up of hpcla_sparse_column_* with a per-row key.  reciprocal != 0 writes 1 / value instead (the Jacobi
+ * preconditioner of hp.cg; a missing entry gives +inf).  Float64 values. */
+int hpcla_sparse_diag_f64_i32(const int32_t *rowptr, const int32_t *colval, const double *nzval, int64_t nrows, int64_t nnz,
+                              int index_base, const int64_t *col_indices, int64_t n_col_indices, int64_t row_start,
+                              int reciprocal, double *out, void *stream);
+int hpcla_sparse_diag_f64_i64(const int64_t *rowptr, const int64_t *colval, const double *nzval, int64_t nrows, int64_t nnz,
+                              int index_base, const int64_t *col_indices, int64_t n_col_indices, int64_t row_start,
+                              int reciprocal, double *out, void *stream);
 
 /* ---- SpGEMM local product (sparse x sparse): replaces the CPU SparseArrays multiply inside
  * Base.:*(A::HPCSparseMatrix, B::HPCSparseMatrix) (`CT = plan.AT * A_csc`, src/sparse.jl:991-1059).
@@ -918,6 +929,51 @@ int hpcla_cg_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, con
                                 const int32_t *boundary_blocks, int64_t n_boundary, double *x, double *r,
                                 double *p, double *Ap, double *rr_hist_dev, double *pAp_dev, void *dot_work,
                                 void *reduce_work, int iters, void *stream);
+/* ---- a converging CG solver: gated, diagonally preconditioned iterations (no reference counterpart: the reference's
+ * only solver is MUMPS on the host).  The solve's state is device memory, so the host looks once per chunk of
+ * iterations and the iterations already enqueued behind the deciding one are no-ops:
+ *   state_dev[0] done_iter  the iteration the solve ended on (meaningful once status != 0)
+ *   state_dev[1] status     0 running, 1 converged, 2 breakdown
+ *   state_dev[2] thr        a double: max(rtol |b|, atol)^2, written by the caller       state_dev[3] reserved
+ * Iteration `iter` is 1-based over the whole solve.
+ *   residual:  while status == 0.  !(*den_dev > 0) (pAp; catches NaN): status = 2, done_iter = iter - 1, nothing else
+ *              written.  Else a = *num_dev / *den_dev;  r -= a*Ap;  pair_out_dev[0] = allreduce(sum r^2),
+ *              pair_out_dev[1] = allreduce(sum r*(dinv*r)) -- ONE all-reduce of the two doubles;  then
+ *              pair_out_dev[0] <= thr: status = 1, done_iter = iter.
+ *   direction: while status == 0, and once more when status == 1 and done_iter >= iter (the x update of the converging
+ *              iteration is deferred into it).  a = *a_num_dev / *a_den_dev, b = *b_num_dev / *b_den_dev;
+ *              x += a*p;  p = dinv*r + b*p   (z = dinv*r is never stored).
+ * dinv == NULL is the identity: no load, no multiply, and the bits of hpcla_cg_residual_f64 / hpcla_cg_direction_f64 on
+ * the same operands (same grid, body, tail, accumulation order, HPCLA_CG_NT policy).  Separate multiply and add.
+ * work: hpcla_pcg_work_bytes() bytes -- two arrays of partials, then 32 bytes that hpcla_pcg_iterations_* uses as the
+ * state (at work + hpcla_pcg_work_bytes() - 32).  Vectors 16-byte aligned. */
+int64_t hpcla_pcg_work_bytes(void);
+int hpcla_pcg_residual_f64(hpcla_comm_t *comm, const double *num_dev, const double *den_dev, const double *Ap,
+                           const double *dinv, double *r, int64_t n, int64_t iter, int64_t *state_dev,
+                           double *pair_out_dev, void *work, void *stream);
+int hpcla_pcg_direction_f64(const double *a_num_dev, const double *a_den_dev, const double *b_num_dev,
+                            const double *b_den_dev, const double *r, const double *dinv, double *x, double *p,
+                            int64_t n, int64_t iter, const int64_t *state_dev, void *stream);
+/* Iterations first_iter .. first_iter + iters - 1 of that solve enqueued by ONE host call: per iteration
+ * hpcla_spmv_dist_dot_* (Ap = A*p, pAp; always executed), hpcla_pcg_residual_f64 (num = rz_{j-1}, den = pAp) and
+ * hpcla_pcg_direction_f64 (b = rz_j / rz_{j-1}).  hist_dev: pairs, [2j] = sum r_j^2 and [2j+1] = sum r_j*(dinv*r_j);
+ * pair 0 on entry of the first chunk, pair j written by iteration j; pairs beyond done_iter are unspecified.  The state
+ * (see above) lives in the last 32 bytes of pcg_work and is set up by the caller.  cols16 / patterns: the plan's 16-bit
+ * column copy and pattern table as for hpcla_spmv_dist_dot_patterns_f64_i32, NULL allowed.  Everything else as for
+ * hpcla_cg_iterations_*.  Only enqueues. */
+int hpcla_pcg_iterations_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int32_t *rowptr,
+                                 const int32_t *colval_split, const int16_t *cols16,
+                                 const hpcla_block_patterns_t *patterns, const double *nzval, int64_t nrows,
+                                 int64_t nnz, int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                 const int32_t *boundary_blocks, int64_t n_boundary, const double *dinv, double *x,
+                                 double *r, double *p, double *Ap, double *hist_dev, double *pAp_dev, void *dot_work,
+                                 void *pcg_work, int64_t first_iter, int iters, void *stream);
+int hpcla_pcg_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int64_t *rowptr,
+                                 const int64_t *colval_split, const double *nzval, int64_t nrows, int64_t nnz,
+                                 int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                 const int32_t *boundary_blocks, int64_t n_boundary, const double *dinv, double *x,
+                                 double *r, double *p, double *Ap, double *hist_dev, double *pAp_dev, void *dot_work,
+                                 void *pcg_work, int64_t first_iter, int iters, void *stream);
 int hpcla_divide_f64(const double *x, double a_host, double *y, int64_t n, void *stream);
 int hpcla_axpby_f64(double a, const double *x, double b, const double *y, double *z, int64_t n,
                     void *stream);

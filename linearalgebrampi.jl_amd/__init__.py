@@ -10,8 +10,8 @@ Layout
   sparse.py          HPCSparseMatrix, VectorPlan (host lists + device plan), A*x, mul!
   dense.py           HPCMatrix, dense A*x and transpose(A)*x, transpose(X)*Y, X*A and transpose(X)*A
   spmm_plans.py      A*B for a sparse A and a dense B (SpMM): exchange entries, sequential and panel orders
-  cg.py              fixed-iteration CG harness
-  indexing.py        v[a:b], X[r, c], A[r, c], A[:, k] and SubmatrixPlan (csrc/submatrix.hip)
+  cg.py              fixed-iteration CG harness; cg(): the converging solver (Jacobi preconditioner, device-side stop)
+  indexing.py        v[a:b], X[r, c], A[r, c], A[:, k], diag(A) and SubmatrixPlan (csrc/submatrix.hip)
   transpose.py matmat.py addition.py repartition.py   the SURVEY 8f "next" rows and their plans
 
 The directory name contains a dot, so it is imported through the top-level alias module
@@ -34,13 +34,13 @@ from .dense import (HPCMatrix, HPCMatrix_local, TransposedHPCMatrix, clear_dense
                     dense_matvec_t, dense_sparse_matmat, dense_sparse_matmat_t)
 from .spmm_plans import clear_spmm_cache, spmm, spmm_block_order_of, spmm_exchange_bytes, spmm_runs_fit_of
 from .matmat import clear_matrix_plan_cache, get_matrix_plan, spgemm
-from .cg import CGGraphPair, CGWorkspace, cg_fixed_iterations, cg_iterate, cg_setup
+from .cg import CGGraphPair, CGInfo, CGWorkspace, PCGWorkspace, cg, cg_fixed_iterations, cg_iterate, cg_setup
 from .convert import to_backend
 from .transpose import (HostTransposeStructure, TransposedHPCSparseMatrix, TransposedHPCVector, TransposePlan,
                         DenseTransposeLists, HostSpmmTPlan, adjoint, clear_transpose_plan_cache, get_transpose_plan,
                         transpose)
 from .addition import add_scaled_identity, sparse_add
-from .indexing import SubmatrixPlan, get_submatrix_plan
+from .indexing import SubmatrixPlan, diag, get_submatrix_plan
 from .repartition import (RangePlan, SparseRepartitionPlan, clear_repartition_cache, exchange_ranges,
                           get_sparse_repartition_plan, get_vector_repartition_plan, repartition)
 

@@ -148,6 +148,14 @@ _SIGNATURES = {
                                     _vp, _vp, _vp, _i32, _vp],
     "hpcla_cg_iterations_f64_i64": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _vp, _i32, _vp],
+    # the converging solver (hp.cg): gated, diagonally preconditioned iterations
+    "hpcla_pcg_work_bytes": [],
+    "hpcla_pcg_residual_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp],
+    "hpcla_pcg_direction_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp],
+    "hpcla_pcg_iterations_f64_i32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
+    "hpcla_pcg_iterations_f64_i64": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
     "hpcla_colspace_work_bytes": [_i64],
     "hpcla_compress_columns_i32": [_vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
     "hpcla_compress_columns_i64": [_vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
@@ -162,6 +170,8 @@ _SIGNATURES = {
     "hpcla_submatrix_values_i64": [_i32, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp],
     "hpcla_sparse_column_i32": [_i32, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp],
     "hpcla_sparse_column_i64": [_i32, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp],
+    "hpcla_sparse_diag_f64_i32": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _vp],
+    "hpcla_sparse_diag_f64_i64": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _vp],
     "hpcla_digest_i32": [_vp, _i64, _vp, _vp],
     "hpcla_digest_i64": [_vp, _i64, _vp, _vp],
     "hpcla_poisson2d_nnz": [_i64, _i64, _i64, _i64],
@@ -252,6 +262,7 @@ _RESTYPES = {
     "hpcla_spmm_runs_desc_bytes": _i64,
     "hpcla_spmv_longrows_work_bytes": _i64,
     "hpcla_cols16_padded_len": _i64,
+    "hpcla_pcg_work_bytes": _i64,
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -20,10 +20,15 @@ Forms, identical arithmetic per element (only the reduction trees differ):
 The solve is split into ``cg_setup`` (x = 0, r = p = b, sum r0^2 -- allocation lives in a reusable
 ``CGWorkspace``) and ``cg_iterate`` (exactly k iterations, enqueue only), so a benchmark can time the
 iterations and nothing else; ``cg_fixed_iterations`` is the two together plus the history read-back.
+
+``cg`` is the solver built from the same launches: a stop rule, an optional diagonal preconditioner and a breakdown
+check, all decided on the device (csrc/vecops.hip, ``hpcla_pcg_iterations_f64_*``); the host reads 16 bytes of state once
+per ``check_every`` iterations, and the iterations enqueued behind the deciding one are no-ops.
 """
 from __future__ import annotations
 
 import math
+from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -208,3 +213,174 @@ def _cg_graph_replay(A, ws: CGWorkspace, plan, fused: bool, iters: int) -> None:
     g.replay((iters - 2) // 2)
     if ws.done < iters:
         cg_iterate(A, ws, plan, fused, iters - ws.done, native_loop=False)
+
+
+# ---- the converging solver ---------------------------------------------------------------------------------------------
+_STATUS = {0: "maxiter", 1: "converged", 2: "breakdown"}
+
+
+@dataclass
+class CGInfo:
+    """What ``cg`` reports: ``iterations`` is the iteration the device stopped on (``maxiter`` when it did not stop),
+    ``residual_norms`` holds ||r_0|| ... ||r_iterations|| of the recurrence residual."""
+    converged: bool
+    iterations: int
+    status: str
+    residual_norms: List[float]
+
+
+class PCGWorkspace:
+    """What a ``cg`` solve allocates: x, r, p, Ap, the history of (sum r_j^2, sum r_j.(dinv r_j)) pairs (it IS the scalar
+    storage of the iterations; it grows by doubling between chunks), pAp, and the scratch of the gated kernels whose last
+    32 bytes are the solve's device state (done_iter, status, thr).  Reusable: every solve resets all of it."""
+
+    def __init__(self, b: HPCVector, hist_iters: int = 254):
+        torch = _torch()
+        dev = b.v.device
+        self.x = HPCVector.zeros(b.partition, b.backend)
+        self.r = b.similar()
+        self.p = b.similar()
+        self.Ap = b.similar()
+        self.hist = torch.zeros(2 * (int(hist_iters) + 2), dtype=torch.float64, device=dev)
+        self.pAp = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.tmp = torch.ones(2, dtype=torch.float64, device=dev)      # [0]: |b|^2 for a given x0; [1]: the constant 1
+        self.work = torch.zeros(_capi.load().hpcla_pcg_work_bytes() // 8, dtype=torch.float64, device=dev)
+        self.state = self.work[-4:].view(torch.int64)                  # done_iter, status, thr (a double), reserved
+
+    def fits(self, b: HPCVector) -> bool:
+        return self.x.structural_hash == b.structural_hash and self.x.v.device == b.v.device
+
+    def hist_capacity(self) -> int:
+        return self.hist.numel() // 2 - 1                              # the last iteration whose pair fits
+
+    def grow_hist(self, upto: int) -> None:
+        torch = _torch()
+        cap = self.hist.numel() // 2
+        while cap - 1 < upto:
+            cap *= 2
+        new = torch.zeros(2 * cap, dtype=torch.float64, device=self.hist.device)
+        new[:self.hist.numel()].copy_(self.hist)
+        self.hist = new
+
+
+def _cg_dinv(A, b: HPCVector, M) -> Optional[HPCVector]:
+    if M is None:
+        return None
+    if isinstance(M, str):
+        if M != "jacobi":
+            raise ValueError(f"cg: unknown preconditioner {M!r} (None, 'jacobi' or an HPCVector of 1 ./ diagonal)")
+        from .indexing import diag
+        from .vectors import minimum
+        if not (minimum(diag(A)) > 0):
+            raise ValueError("cg: M='jacobi' needs a positive diagonal (minimum(diag(A)) > 0)")
+        return diag(A, reciprocal=True)
+    if not isinstance(M, HPCVector):
+        raise ValueError("cg: M must be None, 'jacobi' or an HPCVector on A's row partition")
+    b._same_partition(M)
+    return M
+
+
+def cg(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, atol: float = 0.0,
+       maxiter: Optional[int] = None, M=None, check_every: int = 8,
+       workspace: Optional[PCGWorkspace] = None) -> Tuple[HPCVector, CGInfo]:
+    """Solve ``A x = b`` for a symmetric positive definite ``A`` by (preconditioned) conjugate gradients.
+
+    Stops at the first iteration with ``||r_k|| <= max(rtol * ||b||, atol)`` (scipy's rule; r_k is the recurrence residual),
+    after ``maxiter`` iterations (default ``10 n``), or on a breakdown (``p.Ap <= 0`` or NaN: A is not positive definite
+    along p).  ``M``: ``None``, ``"jacobi"`` (``1 ./ diag(A)``, formed on the device; the diagonal must be positive) or an
+    HPCVector holding the inverse diagonal to apply.  ``x0`` defaults to zero.  Returns ``(x, CGInfo)``; x is the
+    workspace's vector.
+
+    The stop test and the breakdown test run on the device.  The host enqueues ``check_every`` iterations in one library
+    call and then reads the 16-byte state (the only synchronisation); iterations enqueued behind the one that decided are
+    no-ops, so the answer does not depend on ``check_every``.  With ``M=None`` the iterations produce the bits of
+    ``cg_fixed_iterations``."""
+    from .backends import comm_allgather, comm_size
+    from .vectors import f64_only
+    f64_only(A.backend, "cg")
+    torch = _torch()
+    if A.shape[0] != A.shape[1]:
+        raise ValueError(f"cg: the matrix must be square, got {A.shape[0]} x {A.shape[1]}")
+    check_every = int(check_every)
+    if check_every < 1:
+        raise ValueError("cg: check_every must be at least 1")
+    if not (rtol >= 0 and atol >= 0):
+        raise ValueError("cg: rtol and atol must be non-negative")
+    n = int(A.shape[0])
+    maxiter = 10 * n if maxiter is None else int(maxiter)
+    if maxiter < 0:
+        raise ValueError("cg: maxiter must be non-negative")
+    ws = workspace if workspace is not None and workspace.fits(b) else PCGWorkspace(b)
+    plan = get_vector_plan(A, ws.p)
+    if plan.result_partition_hash != ws.p.structural_hash:
+        raise ValueError("cg: b must be partitioned like the rows of A")
+    dinv = _cg_dinv(A, b, M)
+    if getattr(plan, "_dot_work", None) is None:
+        nbytes = _capi.load().hpcla_spmv_dot_work_bytes(A.nrows_local)
+        plan._dot_work = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=ws.p.v.device)
+
+    # -- setup: r0 = b - A x0, p0 = dinv r0, pair 0, the state ----------------------------------------------------------
+    ws.hist.zero_()
+    ws.work.zero_()                                              # done_iter = 0, status = running, thr = 0
+    ws.tmp.fill_(1.0)
+    ws.r.v.copy_(b.v)
+    if x0 is None:
+        ws.x.v.zero_()
+    else:
+        b._same_partition(x0)
+        ws.x.v.copy_(x0.v)
+        mul_(ws.Ap, A, ws.x)
+        ws.r.axpy_(-1.0, ws.Ap)
+        norm(b, 2, out=ws.tmp[0:1])
+    norm(ws.r, 2, out=ws.hist[0:1])
+    one = ws.tmp[1:2]
+    if dinv is None:
+        ws.p.v.copy_(ws.r.v)
+        ws.hist[1:2].copy_(ws.hist[0:1])
+    else:                                                        # p = dinv r + 1 * 0 through the direction kernel (x += 1 * 0)
+        ws.p.v.zero_()
+        _capi.call("hpcla_pcg_direction_f64", dptr(one), dptr(one), dptr(one), dptr(one), dptr(ws.r.v), dptr(dinv.v),
+                   dptr(ws.x.v), dptr(ws.p.v), ws.x.local_length, 1, dptr(ws.state), current_stream_ptr())
+        dot(ws.r, ws.p, out=ws.hist[1:2])
+    rr0 = float(ws.hist[0].item())                               # the setup's one read-back
+    bb = rr0 if x0 is None else float(ws.tmp[0].item())
+    if bb == 0.0:                                                # b = 0: x = 0
+        ws.x.v.zero_()
+        return ws.x, CGInfo(True, 0, "converged", [0.0])
+    thr = max(rtol * math.sqrt(bb), atol) ** 2
+    if rr0 <= thr or maxiter == 0:
+        if rr0 != rr0:
+            from .sparse import check_exchange_health
+            check_exchange_health(b.backend)
+        return ws.x, CGInfo(rr0 <= thr, 0, "converged" if rr0 <= thr else "maxiter", [math.sqrt(rr0)])
+    ws.work[-2:-1].fill_(thr)
+
+    # -- chunks of check_every iterations; one 16-byte read-back each ---------------------------------------------------------
+    sfx = "i64" if plan.is_i64 else "i32"
+    narrow = () if plan.is_i64 else (dptr(plan.cols16), plan.patterns)
+    multi = comm_size(A.backend.comm) > 1
+    j, done_iter, status = 1, 0, 0
+    while j <= maxiter:
+        k = min(check_every, maxiter - j + 1)
+        if j + k - 1 > ws.hist_capacity():
+            ws.grow_hist(min(maxiter, 2 * (j + k)))
+        _capi.call(f"hpcla_pcg_iterations_f64_{sfx}", plan.halo if plan.has_halo else None, A.backend.rccl,
+                   dptr(plan.rowptr_of(A)), dptr(plan.colval_split), *narrow, dptr(A.nzval), A.nrows_local, A.nnz, 0,
+                   dptr(plan.interior), plan.n_interior, dptr(plan.boundary), plan.n_boundary,
+                   dptr(dinv.v) if dinv is not None else None, dptr(ws.x.v), dptr(ws.r.v), dptr(ws.p.v), dptr(ws.Ap.v),
+                   dptr(ws.hist), dptr(ws.pAp), dptr(plan._dot_work), dptr(ws.work), j, int(k), current_stream_ptr())
+        j += k
+        done_iter, status = (int(v) for v in ws.state[:2].cpu().tolist())
+        if multi:                                                # no rank leaves the loop alone, whatever produced its scalars
+            every = comm_allgather(A.backend.comm, np.array([done_iter, status], dtype=np.int64)).reshape(-1, 2)
+            stopped = every[every[:, 1] != 0]
+            if len(stopped):
+                done_iter, status = int(stopped[:, 0].min()), int(stopped[0, 1])
+        if status != 0:
+            break
+    iterations = done_iter if status != 0 else maxiter
+    h = ws.hist[0:2 * (iterations + 1):2].sqrt().cpu().tolist()
+    if h[-1] != h[-1]:                         # NaN: the poison of an expired exchange wait -- ask
+        from .sparse import check_exchange_health
+        check_exchange_health(b.backend)
+    return ws.x, CGInfo(status == 1, iterations, _STATUS[status], h)

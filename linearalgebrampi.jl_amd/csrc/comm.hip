@@ -1118,3 +1118,67 @@ HPCLA_API int hpcla_cg_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t 
                                        nnz, index_base, interior_blocks, n_interior, boundary_blocks, n_boundary, x, r,
                                        p, Ap, rr_hist_dev, pAp_dev, dot_work, reduce_work, iters, stream);
 }
+
+// ---- a chunk of gated, diagonally preconditioned CG iterations in ONE host call (the solver, hp.cg) -------------
+// Iteration j = first_iter .. first_iter + iters - 1 (1-based over the whole solve), in this order:
+//   1. Ap = A p, pAp      hpcla_spmv_dist_dot_* -- always executed, not gated (the SpMV kernels know nothing of the solve)
+//   2. gate A             running and !(pAp > 0): status = breakdown, done_iter = j - 1
+//   3. r -= a Ap          gated; partials of sum r^2 and sum r (dinv r), their second stage, ONE all-reduce of the pair
+//   4. gate B             running and sum r_j^2 <= thr: status = converged, done_iter = j
+//   5. x += a p, p = dinv r + b p    gated, still runs for done_iter == j (the deferred x update)
+// Gate A is the residual kernel's own predicate and is recorded by the single-workgroup second stage; gate B is folded
+// into that second stage where no all-reduce follows it (comm == NULL), else it is one 64-lane launch behind the
+// all-reduce.  hist_dev[2 j], hist_dev[2 j + 1] = sum r_j^2, sum r_j (dinv r_j): the pair is all-reduced in place.
+template <typename I, typename F, typename G>
+static int pcg_iterations_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const I *rowptr,
+                               const I *colval, const int16_t *cols16, const hpcla_block_patterns *patterns,
+                               const double *nzval, int64_t nrows, int64_t nnz, int index_base, const int32_t *interior,
+                               int64_t n_interior, const int32_t *boundary, int64_t n_boundary, const double *dinv, double *x,
+                               double *r, double *p, double *Ap, double *hist_dev, double *pAp_dev, void *dot_work,
+                               void *pcg_work, int64_t first_iter, int iters, void *stream)
+{
+    if (iters < 0 || first_iter < 1) return set_error(HPCLA_ERR_INVALID, "pcg_iterations: negative count or first_iter < 1");
+    if (!hist_dev || !pAp_dev || !dot_work || !pcg_work)
+        return set_error(HPCLA_ERR_INVALID, "pcg_iterations: null scalar / work buffer");
+    if (nrows > 0 && (!x || !r || !p || !Ap)) return set_error(HPCLA_ERR_INVALID, "pcg_iterations: null vector");
+    int64_t *state = reinterpret_cast<int64_t *>(static_cast<char *>(pcg_work) + hpcla_pcg_work_bytes()) - 4;
+    for (int64_t j = first_iter; j < first_iter + iters; ++j) {
+        double *prev = hist_dev + 2 * (j - 1), *cur = hist_dev + 2 * j;
+        int rc = spmv_dist_dot_impl<I>(split_fn, fused_fn, plan, comm, rowptr, colval, nzval, p, nrows, Ap, nrows, nnz,
+                                       index_base, interior, n_interior, boundary, n_boundary, pAp_dev, dot_work,
+                                       stream, cols16, patterns);
+        if (rc) return rc;
+        rc = hpcla_pcg_residual_f64(comm, prev + 1, pAp_dev, Ap, dinv, r, nrows, j, state, cur, pcg_work, stream);
+        if (rc) return rc;
+        rc = hpcla_pcg_direction_f64(prev + 1, pAp_dev, cur + 1, prev + 1, r, dinv, x, p, nrows, j, state, stream);
+        if (rc) return rc;
+    }
+    return HPCLA_OK;
+}
+
+HPCLA_API int hpcla_pcg_iterations_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int32_t *rowptr,
+                                           const int32_t *colval_split, const int16_t *cols16,
+                                           const hpcla_block_patterns_t *patterns, const double *nzval, int64_t nrows,
+                                           int64_t nnz, int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                           const int32_t *boundary_blocks, int64_t n_boundary, const double *dinv, double *x,
+                                           double *r, double *p, double *Ap, double *hist_dev, double *pAp_dev,
+                                           void *dot_work, void *pcg_work, int64_t first_iter, int iters, void *stream)
+{
+    return pcg_iterations_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, comm, rowptr, colval_split, cols16, patterns,
+                                        nzval, nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks,
+                                        n_boundary, dinv, x, r, p, Ap, hist_dev, pAp_dev, dot_work, pcg_work, first_iter,
+                                        iters, stream);
+}
+
+HPCLA_API int hpcla_pcg_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int64_t *rowptr,
+                                           const int64_t *colval_split, const double *nzval, int64_t nrows, int64_t nnz,
+                                           int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                           const int32_t *boundary_blocks, int64_t n_boundary, const double *dinv, double *x,
+                                           double *r, double *p, double *Ap, double *hist_dev, double *pAp_dev,
+                                           void *dot_work, void *pcg_work, int64_t first_iter, int iters, void *stream)
+{
+    return pcg_iterations_impl<int64_t>(spmv_split_i64, spmv_fused_i64, plan, comm, rowptr, colval_split, nullptr, nullptr,
+                                        nzval, nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks,
+                                        n_boundary, dinv, x, r, p, Ap, hist_dev, pAp_dev, dot_work, pcg_work, first_iter,
+                                        iters, stream);
+}

@@ -204,6 +204,35 @@ __global__ __launch_bounds__(256) void sparse_column_kernel(const I *__restrict_
     out[i] = v;
 }
 
+// main diagonal: one lane per local row i, a lower-bound search over the row's entries for the GLOBAL column row_start + i
+// (col_indices is sorted and compressed columns ascend within a row, so col_indices[colval[.]] ascends too); the stored
+// value bit for bit -- or its reciprocal -- and +0.0 (1 / +0.0 = inf) where nothing is stored
+template <typename I>
+__global__ __launch_bounds__(256) void sparse_diag_kernel(const I *__restrict__ rowptr, const I *__restrict__ colval,
+                                                          const double *__restrict__ nzval, int64_t nrows, int64_t nnz, int base,
+                                                          const int64_t *__restrict__ col_indices, int64_t ncomp,
+                                                          int64_t row_start, int reciprocal, double *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nrows) return;
+    const int64_t key = row_start + i;
+    int64_t a = (int64_t)rowptr[i] - base, b = (int64_t)rowptr[i + 1] - base;
+    if (a < 0) a = 0;
+    if (b > nnz) b = nnz;
+    const int64_t end = b;
+    auto global_col = [&](int64_t m) -> int64_t {
+        const int64_t c = (int64_t)colval[m] - base;
+        return (c >= 0 && c < ncomp) ? col_indices[c] : INT64_MAX;    // an id outside the table sorts last, is never read
+    };
+    while (a < b) {
+        const int64_t m = a + ((b - a) >> 1);
+        if (global_col(m) < key) a = m + 1; else b = m;
+    }
+    double v = 0.0;
+    if (a < end && global_col(a) == key) v = nzval[a];
+    out[i] = reciprocal ? 1.0 / v : v;
+}
+
 // work buffer: presence bitmap (width bytes, padded to 16) | lut (width words) | counts (nsel) | block sums of the two scans |
 // the two totals
 static int64_t work_bytes_of(int64_t nsel, int64_t width)
@@ -356,6 +385,23 @@ static int column_impl(int elem_bytes, const I *rowptr, const I *colval, const v
     return HPCLA_OK;
 }
 
+template <typename I>
+static int diag_impl(const I *rowptr, const I *colval, const double *nzval, int64_t nrows, int64_t nnz, int base,
+                     const int64_t *col_indices, int64_t ncomp, int64_t row_start, int reciprocal, double *out, void *stream)
+{
+    if (nrows < 0 || nnz < 0 || ncomp < 0 || row_start < 0) return set_error(HPCLA_ERR_INVALID, "sparse_diag: negative size or row_start");
+    if (base != 0 && base != 1) return set_error(HPCLA_ERR_INVALID, "sparse_diag: index_base must be 0 or 1");
+    if (nrows == 0) return HPCLA_OK;
+    if (!rowptr || !out || (nnz > 0 && (!colval || !nzval || !col_indices)))
+        return set_error(HPCLA_ERR_INVALID, "sparse_diag: null array with a non-zero size");
+    HPCLA_CHECK_GRID((nrows + 255) / 256, "sparse_diag");
+    sparse_diag_kernel<I><<<(uint32_t)((nrows + 255) / 256), 256, 0, as_stream(stream)>>>(rowptr, colval, nzval, nrows, nnz, base,
+                                                                                         col_indices, ncomp, row_start,
+                                                                                         reciprocal, out);
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
 }  // namespace hpcla
 
 using namespace hpcla;
@@ -426,4 +472,19 @@ HPCLA_API int hpcla_sparse_column_i64(int elem_bytes, const int64_t *rowptr, con
                                       int64_t nrows, int64_t nnz, int64_t jk, int index_base, void *out, void *stream)
 {
     return column_impl<int64_t>(elem_bytes, rowptr, colval, nzval, nrows, nnz, jk, index_base, out, stream);
+}
+
+HPCLA_API int hpcla_sparse_diag_f64_i32(const int32_t *rowptr, const int32_t *colval, const double *nzval, int64_t nrows,
+                                        int64_t nnz, int index_base, const int64_t *col_indices, int64_t n_col_indices,
+                                        int64_t row_start, int reciprocal, double *out, void *stream)
+{
+    return diag_impl<int32_t>(rowptr, colval, nzval, nrows, nnz, index_base, col_indices, n_col_indices, row_start, reciprocal,
+                              out, stream);
+}
+HPCLA_API int hpcla_sparse_diag_f64_i64(const int64_t *rowptr, const int64_t *colval, const double *nzval, int64_t nrows,
+                                        int64_t nnz, int index_base, const int64_t *col_indices, int64_t n_col_indices,
+                                        int64_t row_start, int reciprocal, double *out, void *stream)
+{
+    return diag_impl<int64_t>(rowptr, colval, nzval, nrows, nnz, index_base, col_indices, n_col_indices, row_start, reciprocal,
+                              out, stream);
 }

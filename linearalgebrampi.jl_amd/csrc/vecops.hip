@@ -294,6 +294,158 @@ __global__ __launch_bounds__(256) void cg_direction_kernel(double alpha, const d
     }
 }
 
+// ---- gated, diagonally preconditioned forms of the pair above (the solver hpcla_pcg_iterations_*) ----------------
+// Iteration j (1-based over the whole solve) of preconditioned CG with z = dinv .* r NEVER stored:
+//   residual:  a = *num / *den (rz_{j-1} / pAp) ;  r -= a*Ap ;  partials of sum r^2 and sum r*(dinv*r)
+//   direction: a as above, b = *bnum / *bden (rz_j / rz_{j-1}) ;  x += a*p ;  p = dinv*r + b*p
+// 32 (residual) + 48 (direction) = 80 B per row against the plain pair's 64: dinv is read twice, like a stored z would be
+// written once and read once.  PRECOND = false (dinv == NULL, the identity) has no dinv load and no multiply: grid, body,
+// tail, accumulation order and cache policy are those of cg_residual_kernel / cg_direction_kernel, hence their bits.
+//
+// The solve's state lives on the device so that the host looks at it once per chunk of iterations, and the iterations
+// already enqueued behind the deciding one are no-ops (continuing at full accuracy drives rz and pAp to 0/0):
+//   state[0] done_iter   the iteration the solve ended on (meaningful once status != 0)
+//   state[1] status      0 running, 1 converged (sum r_j^2 <= thr at j = done_iter), 2 breakdown (!(pAp > 0) at done_iter + 1)
+//   state[2] thr         max(rtol |b|, atol)^2 as a double, written by the caller
+// The residual kernel runs while status == 0 and pAp > 0; the direction kernel while status == 0, and once more for
+// done_iter >= j: the x update of the converging iteration is deferred into it.  One uniform load per workgroup.
+constexpr int64_t PCG_RUNNING = 0, PCG_CONVERGED = 1, PCG_BREAKDOWN = 2;
+constexpr int PCG_STATE_WORDS = 4;
+
+template <bool NTQ, bool PRECOND>
+__global__ __launch_bounds__(RT) void pcg_residual_kernel(const double *__restrict__ num, const double *__restrict__ den,
+                                                          const double *__restrict__ Ap, const double *__restrict__ dinv,
+                                                          double *__restrict__ r, int64_t n, const int64_t *__restrict__ state,
+                                                          double *__restrict__ partial_rr, double *__restrict__ partial_rz)
+{
+    if (state[1] != PCG_RUNNING || !(den[0] > 0.0)) return;      // frozen, or gate A (recorded by pcg_stage2_kernel)
+    const double a = dev_scalar(1.0, num, den);
+    const int64_t n2 = n / 2;
+    const double2 *q2 = reinterpret_cast<const double2 *>(Ap);
+    const double2 *d2 = reinterpret_cast<const double2 *>(dinv);
+    double2 *r2 = reinterpret_cast<double2 *>(r);
+    double acc = 0.0, acz = 0.0;
+    int64_t i = (int64_t)blockIdx.x * RT + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * RT;
+    for (; i < n2; i += stride) {
+        const double2 qv = NTQ ? nt_load2(q2 + i) : q2[i];
+        double2 rv = r2[i];
+        rv.x = rv.x - a * qv.x;
+        rv.y = rv.y - a * qv.y;
+        r2[i] = rv;
+        acc = acc + rv.x * rv.x;
+        acc = acc + rv.y * rv.y;
+        if (PRECOND) {
+            const double2 dv = d2[i];
+            acz = acz + rv.x * (dv.x * rv.x);
+            acz = acz + rv.y * (dv.y * rv.y);
+        }
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t j = n - 1;
+        const double rn = r[j] - a * Ap[j];
+        r[j] = rn;
+        acc = acc + rn * rn;
+        if (PRECOND) acz = acz + rn * (dinv[j] * rn);
+    }
+    const double s = block_reduce<RED_SUM>(acc);
+    if (threadIdx.x == 0) partial_rr[blockIdx.x] = s;
+    if (PRECOND) {
+        __syncthreads();                                         // block_reduce's LDS slots are reused
+        const double z = block_reduce<RED_SUM>(acz);
+        if (threadIdx.x == 0) partial_rz[blockIdx.x] = z;
+    }
+}
+
+__device__ __forceinline__ void pcg_gate_b(const double *pair, int64_t iter, int64_t *state)
+{
+    if (pair[0] <= reinterpret_cast<const double *>(state)[2]) {
+        state[0] = iter;
+        state[1] = PCG_CONVERGED;
+    }
+}
+
+// second stage of both sums (reduce_stage2<RED_SUM>'s order), one workgroup; records gate A, and gate B where no
+// all-reduce stands between this kernel and the pair (gate_b != 0)
+template <bool PRECOND>
+__global__ __launch_bounds__(RT) void pcg_stage2_kernel(const double *__restrict__ partial_rr,
+                                                        const double *__restrict__ partial_rz, int np,
+                                                        const double *__restrict__ den, int64_t iter, int gate_b,
+                                                        int64_t *__restrict__ state, double *__restrict__ pair)
+{
+    if (state[1] != PCG_RUNNING) return;
+    if (!(den[0] > 0.0)) {                                       // gate A: also catches a NaN pAp
+        if (threadIdx.x == 0) {
+            state[0] = iter - 1;
+            state[1] = PCG_BREAKDOWN;
+        }
+        return;
+    }
+    double acc = 0.0, acz = 0.0;
+    for (int i = threadIdx.x; i < np; i += RT) acc = acc + partial_rr[i];
+    const double rr = block_reduce<RED_SUM>(acc);
+    double rz = rr;
+    if (PRECOND) {
+        for (int i = threadIdx.x; i < np; i += RT) acz = acz + partial_rz[i];
+        __syncthreads();
+        rz = block_reduce<RED_SUM>(acz);
+    }
+    if (threadIdx.x == 0) {
+        pair[0] = rr;
+        pair[1] = rz;
+        if (gate_b) pcg_gate_b(pair, iter, state);
+    }
+}
+
+__global__ void pcg_gate_b_kernel(const double *__restrict__ pair, int64_t iter, int64_t *__restrict__ state)
+{
+    if (threadIdx.x == 0 && state[1] == PCG_RUNNING) pcg_gate_b(pair, iter, state);
+}
+
+template <bool NTX, bool NTR, bool PRECOND>
+__global__ __launch_bounds__(256) void pcg_direction_kernel(const double *__restrict__ num, const double *__restrict__ den,
+                                                            const double *__restrict__ bnum, const double *__restrict__ bden,
+                                                            const double *__restrict__ r, const double *__restrict__ dinv,
+                                                            double *__restrict__ x, double *__restrict__ p, int64_t n,
+                                                            int64_t iter, const int64_t *__restrict__ state)
+{
+    const int64_t status = state[1];
+    if (!(status == PCG_RUNNING || (status == PCG_CONVERGED && state[0] >= iter))) return;
+    const double a = dev_scalar(1.0, num, den);
+    const double b = dev_scalar(1.0, bnum, bden);
+    const int64_t n2 = n / 2;
+    const double2 *r2 = reinterpret_cast<const double2 *>(r);
+    const double2 *d2 = reinterpret_cast<const double2 *>(dinv);
+    double2 *x2 = reinterpret_cast<double2 *>(x);
+    double2 *p2 = reinterpret_cast<double2 *>(p);
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (; i < n2; i += stride) {
+        double2 rv = NTR ? nt_load2(r2 + i) : r2[i];
+        const double2 pv0 = p2[i];
+        double2 xv = NTX ? nt_load2(x2 + i) : x2[i], pv = pv0;
+        if (PRECOND) {
+            const double2 dv = d2[i];
+            rv.x = dv.x * rv.x;
+            rv.y = dv.y * rv.y;
+        }
+        xv.x = xv.x + a * pv.x;
+        xv.y = xv.y + a * pv.y;
+        pv.x = rv.x + b * pv.x;
+        pv.y = rv.y + b * pv.y;
+        if (NTX) nt_store2(xv, x2 + i); else x2[i] = xv;
+        p2[i] = pv;
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t j = n - 1;
+        const double pj = p[j];
+        double zj = r[j];
+        if (PRECOND) zj = dinv[j] * zj;
+        x[j] = x[j] + a * pj;
+        p[j] = zj + b * pj;
+    }
+}
+
 // MODE 0: y = y + a*x   MODE 1: y = x + a*y   MODE 2: y = a*x   MODE 3: y = x / a
 template <int MODE>
 __global__ __launch_bounds__(256) void update_kernel(double alpha, const double *__restrict__ num,
@@ -528,6 +680,75 @@ HPCLA_API int hpcla_cg_direction_f64(double alpha_host, const double *a_num_dev,
     else if (m & 2) HPCLA_CG_DIR(false, true);
     else HPCLA_CG_DIR(false, false);
 #undef HPCLA_CG_DIR
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
+// scratch of the gated pair: two arrays of stage-1 partials, then the solve's state (its last 32 bytes)
+HPCLA_API int64_t hpcla_pcg_work_bytes(void)
+{
+    return (int64_t)(2 * MAX_PARTIALS + PCG_STATE_WORDS) * (int64_t)sizeof(double);
+}
+
+HPCLA_API int hpcla_pcg_residual_f64(hpcla_comm_t *comm, const double *num_dev, const double *den_dev, const double *Ap,
+                                     const double *dinv, double *r, int64_t n, int64_t iter, int64_t *state_dev,
+                                     double *pair_out_dev, void *work, void *stream)
+{
+    if (n < 0 || iter < 1) return set_error(HPCLA_ERR_INVALID, "pcg_residual: negative size or iteration < 1");
+    if (!num_dev || !den_dev || !state_dev || !pair_out_dev || !work)
+        return set_error(HPCLA_ERR_INVALID, "pcg_residual: null scalar / state / out / work");
+    if (n > 0 && (!Ap || !r)) return set_error(HPCLA_ERR_INVALID, "pcg_residual: null vector");
+    if ((reinterpret_cast<uintptr_t>(Ap) | reinterpret_cast<uintptr_t>(r) | reinterpret_cast<uintptr_t>(dinv)) & 15)
+        return set_error(HPCLA_ERR_INVALID, "pcg_residual: vectors must be 16-byte aligned");
+    double *partial_rr = reinterpret_cast<double *>(work), *partial_rz = partial_rr + MAX_PARTIALS;
+    const int g = reduce_grid(n);
+    hipStream_t s = as_stream(stream);
+    const bool nt = (cg_nt_mask() & 4) != 0;
+#define HPCLA_PCG_RES(NT, PC) \
+    pcg_residual_kernel<NT, PC><<<g, RT, 0, s>>>(num_dev, den_dev, Ap, dinv, r, n, state_dev, partial_rr, partial_rz)
+    if (dinv) { if (nt) HPCLA_PCG_RES(true, true); else HPCLA_PCG_RES(false, true); }
+    else      { if (nt) HPCLA_PCG_RES(true, false); else HPCLA_PCG_RES(false, false); }
+#undef HPCLA_PCG_RES
+    HPCLA_CHECK_LAUNCH();
+    const int gate_b = comm ? 0 : 1;
+    if (dinv) pcg_stage2_kernel<true><<<1, RT, 0, s>>>(partial_rr, partial_rz, g, den_dev, iter, gate_b, state_dev, pair_out_dev);
+    else pcg_stage2_kernel<false><<<1, RT, 0, s>>>(partial_rr, partial_rz, g, den_dev, iter, gate_b, state_dev, pair_out_dev);
+    HPCLA_CHECK_LAUNCH();
+    if (!comm) return HPCLA_OK;
+    const int rc = allreduce_on(comm, pair_out_dev, 2, 0, stream);   // rr and rz travel as ONE pair
+    if (rc) return rc;
+    pcg_gate_b_kernel<<<1, 64, 0, s>>>(pair_out_dev, iter, state_dev);
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
+HPCLA_API int hpcla_pcg_direction_f64(const double *a_num_dev, const double *a_den_dev, const double *b_num_dev,
+                                      const double *b_den_dev, const double *r, const double *dinv, double *x, double *p,
+                                      int64_t n, int64_t iter, const int64_t *state_dev, void *stream)
+{
+    if (n < 0 || iter < 1) return set_error(HPCLA_ERR_INVALID, "pcg_direction: negative size or iteration < 1");
+    if (!a_num_dev || !a_den_dev || !b_num_dev || !b_den_dev || !state_dev)
+        return set_error(HPCLA_ERR_INVALID, "pcg_direction: null scalar / state");
+    if (n == 0) return HPCLA_OK;
+    if (!r || !x || !p) return set_error(HPCLA_ERR_INVALID, "pcg_direction: null vector");
+    if ((reinterpret_cast<uintptr_t>(r) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(p) |
+         reinterpret_cast<uintptr_t>(dinv)) & 15)
+        return set_error(HPCLA_ERR_INVALID, "pcg_direction: vectors must be 16-byte aligned");
+    const int m = cg_nt_mask();
+#define HPCLA_PCG_DIR(NX, NR)                                                                                          \
+    do {                                                                                                               \
+        if (dinv)                                                                                                      \
+            pcg_direction_kernel<NX, NR, true><<<ew_grid(n / 2), 256, 0, as_stream(stream)>>>(                         \
+                a_num_dev, a_den_dev, b_num_dev, b_den_dev, r, dinv, x, p, n, iter, state_dev);                        \
+        else                                                                                                           \
+            pcg_direction_kernel<NX, NR, false><<<ew_grid(n / 2), 256, 0, as_stream(stream)>>>(                        \
+                a_num_dev, a_den_dev, b_num_dev, b_den_dev, r, dinv, x, p, n, iter, state_dev);                        \
+    } while (0)
+    if ((m & 1) && (m & 2)) HPCLA_PCG_DIR(true, true);
+    else if (m & 1) HPCLA_PCG_DIR(true, false);
+    else if (m & 2) HPCLA_PCG_DIR(false, true);
+    else HPCLA_PCG_DIR(false, false);
+#undef HPCLA_PCG_DIR
     HPCLA_CHECK_LAUNCH();
     return HPCLA_OK;
 }

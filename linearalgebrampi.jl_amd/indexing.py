@@ -165,6 +165,30 @@ def sparse_column(A, k: int) -> HPCVector:
     return HPCVector(compute_partition_hash(A.row_partition), A.row_partition, out, A.backend)
 
 
+def diag(A, reciprocal: bool = False) -> HPCVector:
+    """``diag(A)``: the main diagonal of a square Float64 HPCSparseMatrix as an HPCVector on ``A.row_partition``, looked up on
+    the device (one lane per local row): the stored value bit for bit, +0.0 where nothing is stored.  ``reciprocal=True``
+    returns ``1 ./ diag(A)`` from the same pass (``hp.cg``'s Jacobi preconditioner).  Off-diagonals are not offered."""
+    from .sparse import HPCSparseMatrix
+    if not isinstance(A, HPCSparseMatrix):
+        raise ValueError("diag: an HPCSparseMatrix is required")
+    if A.shape[0] != A.shape[1]:
+        raise ValueError(f"diag: the matrix must be square, got {A.shape[0]} x {A.shape[1]}")
+    if A.backend.T != np.dtype(np.float64):
+        raise ValueError("diag: offered for Float64 backends only")
+    require_device(A.backend, "diag(A)")
+    torch = _torch()
+    out = torch.zeros(A.nrows_local, dtype=A.nzval.dtype, device=A.backend.torch_device)
+    if A.nrows_local > 0:
+        sfx = "i64" if A.Ti == np.dtype(np.int64) else "i32"
+        ci = _col_indices_dev(A)
+        row_start = int(A.row_partition[comm_rank(A.backend.comm)])
+        _capi.call(f"hpcla_sparse_diag_f64_{sfx}", dptr(A.rowptr_target), dptr(A.colval_target()), dptr(A.nzval), A.nrows_local,
+                   A.nnz, 0, dptr(ci) if A.nnz else None, int(ci.numel()), row_start, int(bool(reciprocal)), dptr(out),
+                   current_stream_ptr())
+    return HPCVector(compute_partition_hash(A.row_partition), A.row_partition, out, A.backend)
+
+
 def sparse_getitem(A, key):
     if isinstance(key, tuple) and len(key) == 2 and _is_int(key[1]):
         if not (isinstance(key[0], slice) and key[0] == slice(None)):
