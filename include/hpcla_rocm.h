@@ -974,6 +974,64 @@ int hpcla_pcg_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, co
                                  const int32_t *boundary_blocks, int64_t n_boundary, const double *dinv, double *x,
                                  double *r, double *p, double *Ap, double *hist_dev, double *pAp_dev, void *dot_work,
                                  void *pcg_work, int64_t first_iter, int iters, void *stream);
+/* ---- BiCGStab for nonsymmetric A: gated steps of right-preconditioned BiCGStab, K = identity or dinv .* (no reference
+ * counterpart: the reference solves a general A \ b through MUMPS on the host; a caller of its operators composes the
+ * method from A*p, src/sparse.jl:2096-2128, dot, src/vectors.jl:798-812, and the broadcasts, src/vectors.jl:1203-1226).
+ * The state is the CG solver's (done_iter, status, thr, reserved) with one more status:
+ *   3 converged at the half step (sum s^2 <= thr at done_iter): x = x + a*ph only, r untouched; callers report "converged".
+ * Iteration `iter` is 1-based over the whole solve; every entry is a no-op writing no byte once status != 0 (bicg_xr runs
+ * once more, in its half-step form, when status == 3 and done_iter == iter).  a = *rho_dev / *rv_dev, w = ts / tt with
+ * triple_dev = (ts, tt, ss), b = (*rho_new_dev / *rho_dev) * (a / w): formed in every kernel from the same doubles.
+ * Each reduction is all-reduced once (comm != NULL) and followed by its gates, in this order:
+ *   bicg_dot  (stands for dot)              *rv_out_dev = rhat.v.  Gate A: !(rho != 0 && rv != 0), NaN included:
+ *                                           status = 2, done_iter = iter - 1.
+ *   bicg_s    (one broadcast, two with dinv) s = r - a*v;  sh = dinv .* s when dinv != NULL (sh may be NULL otherwise).  Also
+ *                                           a no-op under gate A's predicate.
+ *   bicg_tts  (three dots)                  triple_out_dev = (t.s, t.t, s.s), one pass.  Gate S: ss <= thr: status = 3,
+ *                                           done_iter = iter.  Gate T: !(tt > 0): status = 2, done_iter = iter - 1.
+ *   bicg_xr   (two broadcasts, dot, norm)   x = (x + a*ph) + w*sh;  r = s - w*t;  pair_out_dev = (sum r^2, rhat.r).  sh == NULL
+ *                                           means sh is s (the identity).  Gate B: sum r^2 <= thr: status = 1, done_iter =
+ *                                           iter.  Gate O: ts == 0: status = 2, done_iter = iter.  In the half-step form
+ *                                           pair_out_dev[0] = ss (triple_dev[2]), stored behind the pair's all-reduce so
+ *                                           that N ranks do not sum the already global value; pair_out_dev[1] unspecified.
+ *   bicg_p    (two broadcasts, three with dinv) p = r + b*(p - w*v);  ph = dinv .* p when dinv != NULL.
+ * Separate multiply and add, in the order written.  work: the byte count of hpcla_bicgstab_work_bytes -- three arrays of
+ * partials, then the 32 bytes the iterations entry uses as the state.  Vectors 16-byte aligned. */
+int64_t hpcla_bicgstab_work_bytes(void);
+int hpcla_bicg_dot_f64(hpcla_comm_t *comm, const double *rhat, const double *v, int64_t n, int64_t iter,
+                       const double *rho_dev, int64_t *state_dev, double *rv_out_dev, void *work, void *stream);
+int hpcla_bicg_s_f64(const double *rho_dev, const double *rv_dev, const double *r, const double *v, const double *dinv,
+                     double *s, double *sh, int64_t n, int64_t iter, const int64_t *state_dev, void *stream);
+int hpcla_bicg_tts_f64(hpcla_comm_t *comm, const double *t, const double *s, int64_t n, int64_t iter, int64_t *state_dev,
+                       double *triple_out_dev, void *work, void *stream);
+int hpcla_bicg_xr_f64(hpcla_comm_t *comm, const double *rho_dev, const double *rv_dev, const double *triple_dev,
+                      const double *ph, const double *sh, const double *s, const double *t, const double *rhat, double *x,
+                      double *r, int64_t n, int64_t iter, int64_t *state_dev, double *pair_out_dev, void *work,
+                      void *stream);
+int hpcla_bicg_p_f64(const double *rho_new_dev, const double *rho_dev, const double *rv_dev, const double *triple_dev,
+                     const double *r, const double *v, const double *dinv, double *p, double *ph, int64_t n, int64_t iter,
+                     const int64_t *state_dev, void *stream);
+/* Iterations first_iter .. first_iter + iters - 1 enqueued by ONE host call: per iteration v = A*ph and t = A*sh through
+ * hpcla_spmv_dist_* (always executed, no dot partials) and the five steps above.  dinv == NULL: ph and sh are not used
+ * (p and s are the SpMV's inputs) and may be NULL.  hist_dev: pairs, [2j] = sum r_j^2 (sum s_j^2 for a half-step stop),
+ * [2j+1] = rhat.r_j, the rho of iteration j + 1; pair 0 on entry of the first chunk.  scal_dev: 4 doubles (rv, ts, tt, ss).
+ * The state lives in the last 32 bytes of work and is set up by the caller.  Everything else as for
+ * hpcla_pcg_iterations_*.  Only enqueues. */
+int hpcla_bicgstab_iterations_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int32_t *rowptr,
+                                      const int32_t *colval_split, const int16_t *cols16,
+                                      const hpcla_block_patterns_t *patterns, const double *nzval, int64_t nrows,
+                                      int64_t nnz, int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                      const int32_t *boundary_blocks, int64_t n_boundary, const double *dinv, double *x,
+                                      double *r, const double *rhat, double *p, double *ph, double *v, double *s,
+                                      double *sh, double *t, double *hist_dev, double *scal_dev, void *work,
+                                      int64_t first_iter, int iters, void *stream);
+int hpcla_bicgstab_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int64_t *rowptr,
+                                      const int64_t *colval_split, const double *nzval, int64_t nrows, int64_t nnz,
+                                      int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                      const int32_t *boundary_blocks, int64_t n_boundary, const double *dinv, double *x,
+                                      double *r, const double *rhat, double *p, double *ph, double *v, double *s,
+                                      double *sh, double *t, double *hist_dev, double *scal_dev, void *work,
+                                      int64_t first_iter, int iters, void *stream);
 int hpcla_divide_f64(const double *x, double a_host, double *y, int64_t n, void *stream);
 int hpcla_axpby_f64(double a, const double *x, double b, const double *y, double *z, int64_t n,
                     void *stream);

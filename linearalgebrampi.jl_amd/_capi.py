@@ -156,6 +156,17 @@ _SIGNATURES = {
                                      _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
     "hpcla_pcg_iterations_f64_i64": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
                                      _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
+    # BiCGStab for nonsymmetric A (hp.bicgstab): the gated steps and the chunk of iterations
+    "hpcla_bicgstab_work_bytes": [],
+    "hpcla_bicg_dot_f64": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
+    "hpcla_bicg_s_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp],
+    "hpcla_bicg_tts_f64": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp],
+    "hpcla_bicg_xr_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp],
+    "hpcla_bicg_p_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp],
+    "hpcla_bicgstab_iterations_f64_i32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
+                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
+    "hpcla_bicgstab_iterations_f64_i64": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
+                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
     "hpcla_colspace_work_bytes": [_i64],
     "hpcla_compress_columns_i32": [_vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
     "hpcla_compress_columns_i64": [_vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
@@ -263,6 +274,7 @@ _RESTYPES = {
     "hpcla_spmv_longrows_work_bytes": _i64,
     "hpcla_cols16_padded_len": _i64,
     "hpcla_pcg_work_bytes": _i64,
+    "hpcla_bicgstab_work_bytes": _i64,
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -229,7 +229,91 @@ class CGInfo:
     residual_norms: List[float]
 
 
-class PCGWorkspace:
+class _PairHistory:
+    """The history of a chunked solve (``cg``, ``bicgstab``): pairs of doubles, pair j written by iteration j; it IS the
+    scalar storage of the iterations and grows by doubling between chunks."""
+
+    def hist_capacity(self) -> int:
+        return self.hist.numel() // 2 - 1                              # the last iteration whose pair fits
+
+    def grow_hist(self, upto: int) -> None:
+        torch = _torch()
+        cap = self.hist.numel() // 2
+        while cap - 1 < upto:
+            cap *= 2
+        new = torch.zeros(2 * cap, dtype=torch.float64, device=self.hist.device)
+        new[:self.hist.numel()].copy_(self.hist)
+        self.hist = new
+
+
+def _solver_arguments(name: str, A, rtol: float, atol: float, maxiter: Optional[int], check_every: int) -> Tuple[int, int]:
+    """The argument rules ``cg`` and ``bicgstab`` share.  Returns (maxiter, check_every)."""
+    from .vectors import f64_only
+    f64_only(A.backend, name)
+    if A.shape[0] != A.shape[1]:
+        raise ValueError(f"{name}: the matrix must be square, got {A.shape[0]} x {A.shape[1]}")
+    check_every = int(check_every)
+    if check_every < 1:
+        raise ValueError(f"{name}: check_every must be at least 1")
+    if not (rtol >= 0 and atol >= 0):
+        raise ValueError(f"{name}: rtol and atol must be non-negative")
+    maxiter = 10 * int(A.shape[0]) if maxiter is None else int(maxiter)
+    if maxiter < 0:
+        raise ValueError(f"{name}: maxiter must be non-negative")
+    return maxiter, check_every
+
+
+def _stop_rule_or_done(ws, b, have_x0: bool, rtol: float, atol: float, maxiter: int) -> Optional["CGInfo"]:
+    """After the setup (hist[0] = sum r_0^2, tmp[0] = |b|^2 when x0 was given): the setup's one read-back.  Returns the result
+    of a solve that needs no iteration (b = 0, r_0 within the stop rule, maxiter = 0), else writes thr into the state."""
+    rr0 = float(ws.hist[0].item())
+    bb = float(ws.tmp[0].item()) if have_x0 else rr0
+    if bb == 0.0:                                                # b = 0: x = 0
+        ws.x.v.zero_()
+        return CGInfo(True, 0, "converged", [0.0])
+    thr = max(rtol * math.sqrt(bb), atol) ** 2
+    if rr0 <= thr or maxiter == 0:
+        if rr0 != rr0:
+            from .sparse import check_exchange_health
+            check_exchange_health(b.backend)
+        return CGInfo(rr0 <= thr, 0, "converged" if rr0 <= thr else "maxiter", [math.sqrt(rr0)])
+    ws.work[-2:-1].fill_(thr)
+    return None
+
+
+def _run_chunks(ws, backend, maxiter: int, check_every: int, enqueue) -> Tuple[int, int]:
+    """Chunks of ``check_every`` iterations, ``enqueue(first_iter, count)`` each, one 16-byte read-back of the state per chunk.
+    Returns (iterations, status); a status other than 0 is the device's, 0 means ``maxiter`` iterations ran."""
+    from .backends import comm_allgather, comm_size
+    multi = comm_size(backend.comm) > 1
+    j, done_iter, status = 1, 0, 0
+    while j <= maxiter:
+        k = min(check_every, maxiter - j + 1)
+        if j + k - 1 > ws.hist_capacity():
+            ws.grow_hist(min(maxiter, 2 * (j + k)))
+        enqueue(j, int(k))
+        j += k
+        done_iter, status = (int(v) for v in ws.state[:2].cpu().tolist())
+        if multi:                                                # no rank leaves the loop alone, whatever produced its scalars
+            every = comm_allgather(backend.comm, np.array([done_iter, status], dtype=np.int64)).reshape(-1, 2)
+            stopped = every[every[:, 1] != 0]
+            if len(stopped):
+                done_iter, status = int(stopped[:, 0].min()), int(stopped[0, 1])
+        if status != 0:
+            break
+    return (done_iter if status != 0 else maxiter), status
+
+
+def _residual_norms(ws, backend, iterations: int) -> List[float]:
+    """sqrt of the first entries of pairs 0 .. iterations, read back once."""
+    h = ws.hist[0:2 * (iterations + 1):2].sqrt().cpu().tolist()
+    if h[-1] != h[-1]:                         # NaN: the poison of an expired exchange wait -- ask
+        from .sparse import check_exchange_health
+        check_exchange_health(backend)
+    return h
+
+
+class PCGWorkspace(_PairHistory):
     """What a ``cg`` solve allocates: x, r, p, Ap, the history of (sum r_j^2, sum r_j.(dinv r_j)) pairs (it IS the scalar
     storage of the iterations; it grows by doubling between chunks), pAp, and the scratch of the gated kernels whose last
     32 bytes are the solve's device state (done_iter, status, thr).  Reusable: every solve resets all of it."""
@@ -249,18 +333,6 @@ class PCGWorkspace:
 
     def fits(self, b: HPCVector) -> bool:
         return self.x.structural_hash == b.structural_hash and self.x.v.device == b.v.device
-
-    def hist_capacity(self) -> int:
-        return self.hist.numel() // 2 - 1                              # the last iteration whose pair fits
-
-    def grow_hist(self, upto: int) -> None:
-        torch = _torch()
-        cap = self.hist.numel() // 2
-        while cap - 1 < upto:
-            cap *= 2
-        new = torch.zeros(2 * cap, dtype=torch.float64, device=self.hist.device)
-        new[:self.hist.numel()].copy_(self.hist)
-        self.hist = new
 
 
 def _cg_dinv(A, b: HPCVector, M) -> Optional[HPCVector]:
@@ -295,21 +367,8 @@ def cg(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, atol
     call and then reads the 16-byte state (the only synchronisation); iterations enqueued behind the one that decided are
     no-ops, so the answer does not depend on ``check_every``.  With ``M=None`` the iterations produce the bits of
     ``cg_fixed_iterations``."""
-    from .backends import comm_allgather, comm_size
-    from .vectors import f64_only
-    f64_only(A.backend, "cg")
+    maxiter, check_every = _solver_arguments("cg", A, rtol, atol, maxiter, check_every)
     torch = _torch()
-    if A.shape[0] != A.shape[1]:
-        raise ValueError(f"cg: the matrix must be square, got {A.shape[0]} x {A.shape[1]}")
-    check_every = int(check_every)
-    if check_every < 1:
-        raise ValueError("cg: check_every must be at least 1")
-    if not (rtol >= 0 and atol >= 0):
-        raise ValueError("cg: rtol and atol must be non-negative")
-    n = int(A.shape[0])
-    maxiter = 10 * n if maxiter is None else int(maxiter)
-    if maxiter < 0:
-        raise ValueError("cg: maxiter must be non-negative")
     ws = workspace if workspace is not None and workspace.fits(b) else PCGWorkspace(b)
     plan = get_vector_plan(A, ws.p)
     if plan.result_partition_hash != ws.p.structural_hash:
@@ -342,45 +401,21 @@ def cg(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, atol
         _capi.call("hpcla_pcg_direction_f64", dptr(one), dptr(one), dptr(one), dptr(one), dptr(ws.r.v), dptr(dinv.v),
                    dptr(ws.x.v), dptr(ws.p.v), ws.x.local_length, 1, dptr(ws.state), current_stream_ptr())
         dot(ws.r, ws.p, out=ws.hist[1:2])
-    rr0 = float(ws.hist[0].item())                               # the setup's one read-back
-    bb = rr0 if x0 is None else float(ws.tmp[0].item())
-    if bb == 0.0:                                                # b = 0: x = 0
-        ws.x.v.zero_()
-        return ws.x, CGInfo(True, 0, "converged", [0.0])
-    thr = max(rtol * math.sqrt(bb), atol) ** 2
-    if rr0 <= thr or maxiter == 0:
-        if rr0 != rr0:
-            from .sparse import check_exchange_health
-            check_exchange_health(b.backend)
-        return ws.x, CGInfo(rr0 <= thr, 0, "converged" if rr0 <= thr else "maxiter", [math.sqrt(rr0)])
-    ws.work[-2:-1].fill_(thr)
+    done = _stop_rule_or_done(ws, b, x0 is not None, rtol, atol, maxiter)
+    if done is not None:
+        return ws.x, done
 
     # -- chunks of check_every iterations; one 16-byte read-back each ---------------------------------------------------------
     sfx = "i64" if plan.is_i64 else "i32"
     narrow = () if plan.is_i64 else (dptr(plan.cols16), plan.patterns)
-    multi = comm_size(A.backend.comm) > 1
-    j, done_iter, status = 1, 0, 0
-    while j <= maxiter:
-        k = min(check_every, maxiter - j + 1)
-        if j + k - 1 > ws.hist_capacity():
-            ws.grow_hist(min(maxiter, 2 * (j + k)))
+
+    def enqueue(first, count):
         _capi.call(f"hpcla_pcg_iterations_f64_{sfx}", plan.halo if plan.has_halo else None, A.backend.rccl,
                    dptr(plan.rowptr_of(A)), dptr(plan.colval_split), *narrow, dptr(A.nzval), A.nrows_local, A.nnz, 0,
                    dptr(plan.interior), plan.n_interior, dptr(plan.boundary), plan.n_boundary,
                    dptr(dinv.v) if dinv is not None else None, dptr(ws.x.v), dptr(ws.r.v), dptr(ws.p.v), dptr(ws.Ap.v),
-                   dptr(ws.hist), dptr(ws.pAp), dptr(plan._dot_work), dptr(ws.work), j, int(k), current_stream_ptr())
-        j += k
-        done_iter, status = (int(v) for v in ws.state[:2].cpu().tolist())
-        if multi:                                                # no rank leaves the loop alone, whatever produced its scalars
-            every = comm_allgather(A.backend.comm, np.array([done_iter, status], dtype=np.int64)).reshape(-1, 2)
-            stopped = every[every[:, 1] != 0]
-            if len(stopped):
-                done_iter, status = int(stopped[:, 0].min()), int(stopped[0, 1])
-        if status != 0:
-            break
-    iterations = done_iter if status != 0 else maxiter
-    h = ws.hist[0:2 * (iterations + 1):2].sqrt().cpu().tolist()
-    if h[-1] != h[-1]:                         # NaN: the poison of an expired exchange wait -- ask
-        from .sparse import check_exchange_health
-        check_exchange_health(b.backend)
+                   dptr(ws.hist), dptr(ws.pAp), dptr(plan._dot_work), dptr(ws.work), first, count, current_stream_ptr())
+
+    iterations, status = _run_chunks(ws, A.backend, maxiter, check_every, enqueue)
+    h = _residual_norms(ws, b.backend, iterations)
     return ws.x, CGInfo(status == 1, iterations, _STATUS[status], h)

@@ -1182,3 +1182,92 @@ HPCLA_API int hpcla_pcg_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t
                                         n_boundary, dinv, x, r, p, Ap, hist_dev, pAp_dev, dot_work, pcg_work, first_iter,
                                         iters, stream);
 }
+
+// ---- a chunk of gated BiCGStab iterations in ONE host call (the solver, hp.bicgstab) ------------------------------
+// Right-preconditioned BiCGStab, K = identity (dinv == NULL: ph is p, sh is s) or dinv .*.  Iteration j = first_iter ..
+// first_iter + iters - 1 (1-based over the whole solve), in this order (the gates and the bytes: csrc/vecops.hip):
+//   1. v = A ph                     hpcla_spmv_dist_* -- always executed, not gated, no dot partials
+//   2. rv = rhat.v, gate A          hpcla_bicg_dot_f64: one all-reduce [rv]
+//   3. s = r - a v  [sh = dinv s]   hpcla_bicg_s_f64
+//   4. t = A sh                     the SpMV again
+//   5. ts, tt, ss, gates S and T    hpcla_bicg_tts_f64: one all-reduce of the triple
+//   6. x, r, rr, rho', gates B, O   hpcla_bicg_xr_f64: one all-reduce of the pair (the half-step form behind gate S; its gate,
+//                                   behind the all-reduce, then stores ss as the pair's first entry)
+//   7. p = r + b (p - w v)  [ph]    hpcla_bicg_p_f64
+// One rank: 2 SpMV + 8 launches (every gate is folded into a second stage).  N ranks: + 3 window all-reduces and 3 64-lane
+// gate launches.  hist_dev[2 j], hist_dev[2 j + 1] = sum r_j^2 (sum s_j^2 for a half-step stop), rhat.r_j: the pair is
+// all-reduced in place and its second entry is the rho of iteration j + 1.  scal_dev: rv, ts, tt, ss.
+template <typename I, typename F, typename G>
+static int bicgstab_iterations_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const I *rowptr,
+                                    const I *colval, const int16_t *cols16, const hpcla_block_patterns *patterns,
+                                    const double *nzval, int64_t nrows, int64_t nnz, int index_base, const int32_t *interior,
+                                    int64_t n_interior, const int32_t *boundary, int64_t n_boundary, const double *dinv,
+                                    double *x, double *r, const double *rhat, double *p, double *ph, double *v, double *s,
+                                    double *sh, double *t, double *hist_dev, double *scal_dev, void *work, int64_t first_iter,
+                                    int iters, void *stream)
+{
+    if (iters < 0 || first_iter < 1)
+        return set_error(HPCLA_ERR_INVALID, "bicgstab_iterations: negative count or first_iter < 1");
+    if (nrows < 0 || nnz < 0) return set_error(HPCLA_ERR_INVALID, "bicgstab_iterations: negative size");
+    if (!hist_dev || !scal_dev || !work) return set_error(HPCLA_ERR_INVALID, "bicgstab_iterations: null scalar / work buffer");
+    if (nrows > 0 && (!x || !r || !rhat || !p || !v || !s || !t || (dinv && (!ph || !sh))))
+        return set_error(HPCLA_ERR_INVALID, "bicgstab_iterations: null vector");
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(r) | reinterpret_cast<uintptr_t>(rhat) |
+         reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(s) |
+         reinterpret_cast<uintptr_t>(t) | reinterpret_cast<uintptr_t>(dinv) |
+         (dinv ? reinterpret_cast<uintptr_t>(ph) | reinterpret_cast<uintptr_t>(sh) : 0)) & 15)
+        return set_error(HPCLA_ERR_INVALID, "bicgstab_iterations: vectors must be 16-byte aligned");
+    int64_t *state = reinterpret_cast<int64_t *>(static_cast<char *>(work) + hpcla_bicgstab_work_bytes()) - 4;
+    double *in1 = dinv ? ph : p, *in2 = dinv ? sh : s;
+    double *rv = scal_dev, *triple = scal_dev + 1;
+    for (int64_t j = first_iter; j < first_iter + iters; ++j) {
+        double *prev = hist_dev + 2 * (j - 1), *cur = hist_dev + 2 * j;
+        int rc = spmv_dist_impl<I>(split_fn, fused_fn, plan, rowptr, colval, nzval, in1, nrows, v, nrows, nnz, index_base,
+                                   interior, n_interior, boundary, n_boundary, stream, nullptr, cols16, patterns);
+        if (rc) return rc;
+        rc = hpcla_bicg_dot_f64(comm, rhat, v, nrows, j, prev + 1, state, rv, work, stream);
+        if (rc) return rc;
+        rc = hpcla_bicg_s_f64(prev + 1, rv, r, v, dinv, s, dinv ? sh : nullptr, nrows, j, state, stream);
+        if (rc) return rc;
+        rc = spmv_dist_impl<I>(split_fn, fused_fn, plan, rowptr, colval, nzval, in2, nrows, t, nrows, nnz, index_base,
+                               interior, n_interior, boundary, n_boundary, stream, nullptr, cols16, patterns);
+        if (rc) return rc;
+        rc = hpcla_bicg_tts_f64(comm, t, s, nrows, j, state, triple, work, stream);
+        if (rc) return rc;
+        rc = hpcla_bicg_xr_f64(comm, prev + 1, rv, triple, in1, dinv ? sh : nullptr, s, t, rhat, x, r, nrows, j, state, cur,
+                               work, stream);
+        if (rc) return rc;
+        rc = hpcla_bicg_p_f64(cur + 1, prev + 1, rv, triple, r, v, dinv, p, dinv ? ph : nullptr, nrows, j, state, stream);
+        if (rc) return rc;
+    }
+    return HPCLA_OK;
+}
+
+HPCLA_API int hpcla_bicgstab_iterations_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int32_t *rowptr,
+                                                const int32_t *colval_split, const int16_t *cols16,
+                                                const hpcla_block_patterns_t *patterns, const double *nzval, int64_t nrows,
+                                                int64_t nnz, int index_base, const int32_t *interior_blocks,
+                                                int64_t n_interior, const int32_t *boundary_blocks, int64_t n_boundary,
+                                                const double *dinv, double *x, double *r, const double *rhat, double *p,
+                                                double *ph, double *v, double *s, double *sh, double *t, double *hist_dev,
+                                                double *scal_dev, void *work, int64_t first_iter, int iters, void *stream)
+{
+    return bicgstab_iterations_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, comm, rowptr, colval_split, cols16,
+                                             patterns, nzval, nrows, nnz, index_base, interior_blocks, n_interior,
+                                             boundary_blocks, n_boundary, dinv, x, r, rhat, p, ph, v, s, sh, t, hist_dev,
+                                             scal_dev, work, first_iter, iters, stream);
+}
+
+HPCLA_API int hpcla_bicgstab_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int64_t *rowptr,
+                                                const int64_t *colval_split, const double *nzval, int64_t nrows, int64_t nnz,
+                                                int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                                const int32_t *boundary_blocks, int64_t n_boundary, const double *dinv,
+                                                double *x, double *r, const double *rhat, double *p, double *ph, double *v,
+                                                double *s, double *sh, double *t, double *hist_dev, double *scal_dev,
+                                                void *work, int64_t first_iter, int iters, void *stream)
+{
+    return bicgstab_iterations_impl<int64_t>(spmv_split_i64, spmv_fused_i64, plan, comm, rowptr, colval_split, nullptr,
+                                             nullptr, nzval, nrows, nnz, index_base, interior_blocks, n_interior,
+                                             boundary_blocks, n_boundary, dinv, x, r, rhat, p, ph, v, s, sh, t, hist_dev,
+                                             scal_dev, work, first_iter, iters, stream);
+}

@@ -8,6 +8,8 @@
 // Bytes per element: dot 16 (8 for x.x), nrm2sq/asum/amax 8, axpy/xpay 24, scale 16, axpby 24.
 #include <stdlib.h>
 
+#include <initializer_list>
+
 #include "common.h"
 
 namespace hpcla {
@@ -446,6 +448,368 @@ __global__ __launch_bounds__(256) void pcg_direction_kernel(const double *__rest
     }
 }
 
+// ---- gated BiCGStab steps (the solver hpcla_bicgstab_iterations_*; right preconditioning, K = identity or dinv .*) ----
+// Iteration j (1-based over the whole solve); v = A ph and t = A sh are the SpMV's, ungated.  Bytes per row, plain / with dinv:
+//   bicg_dot   rv = rhat.v                                               read rhat, v                            16 / 16
+//   bicg_s     a = rho/rv;  s = r - a*v  [sh = dinv*s]                   read r, v [dinv], write s [sh]          24 / 40
+//   bicg_tts   ts = t.s, tt = t.t, ss = s.s in ONE pass                  read t, s                               16 / 16
+//   bicg_xr    w = ts/tt;  x = (x + a*ph) + w*sh;  r = s - w*t;          read x, ph, s [sh], t, rhat, write x, r 56 / 64
+//              rho' = rhat.r, rr = r.r      (half-step form: x = x + a*ph only, 24 B)
+//   bicg_p     b = (rho'/rho)*(a/w);  p = r + b*(p - w*v)  [ph = dinv*p] read r, p, v [dinv], write p [ph]       32 / 48
+// 144 B per row and iteration next to the two SpMVs (184 with dinv); composed from dot / axpy / xpay it is about 216 B, five
+// host read-backs and about 13 launches.  PRECOND = false has no dinv load and no multiply: ph IS p and sh IS s (one load).
+// Every kernel forms a, w, b from the same device doubles with the expressions above, so each has the same bits wherever it
+// is used; multiplies and adds are rounded separately, in the order written.
+//
+// The state is PCG's (done_iter, status, thr, reserved) with one more status, set by gate S and reported as converged:
+//   3 converged at the half step: ss_j <= thr at j = done_iter; bicg_xr of that iteration then runs in its half-step form
+// Gates, in this order (each needs status == 0):
+//   A  after rv:            !(rho != 0 && rv != 0), NaN included      -> breakdown, done_iter = j - 1
+//   S  after (ts, tt, ss):  ss <= thr                                 -> status 3, done_iter = j; the history pair's first entry
+//                                                                        receives ss from bicg_xr's gate, BEHIND the pair's
+//                                                                        all-reduce (written before it, N ranks would sum it)
+//   T                       !(tt > 0)                                 -> breakdown, done_iter = j - 1 (x and r untouched)
+//   B  after (rr, rho'):    rr <= thr                                 -> converged, done_iter = j
+//   O                       ts == 0 (w = 0: the next direction is 0/0) -> breakdown, done_iter = j (x and r are updated)
+// Cache policy: x in bicg_xr (HPCLA_CG_NT bit 0) and t in bicg_xr (bit 2: its last use) are not touched again within the
+// iteration and go non-temporally, as x and Ap do in the CG pair; every other vector is re-read by the next kernels.
+constexpr int64_t BICG_CONVERGED_HALF = 3;
+constexpr int BICG_PARTIAL_ARRAYS = 3;
+
+__device__ __forceinline__ bool bicg_nonzero(double a) { return fabs(a) > 0.0; }     // false for +-0 and for NaN
+
+__device__ __forceinline__ void bicg_gate_a(double rho, double rv, int64_t iter, int64_t *state)
+{
+    if (!(bicg_nonzero(rho) && bicg_nonzero(rv))) {
+        state[0] = iter - 1;
+        state[1] = PCG_BREAKDOWN;
+    }
+}
+
+__device__ __forceinline__ void bicg_gate_st(const double *triple, int64_t iter, int64_t *state)
+{
+    if (triple[2] <= reinterpret_cast<const double *>(state)[2]) {
+        state[0] = iter;
+        state[1] = BICG_CONVERGED_HALF;
+    } else if (!(triple[1] > 0.0)) {
+        state[0] = iter - 1;
+        state[1] = PCG_BREAKDOWN;
+    }
+}
+
+// also the half step's history entry: triple[2] = ss, already all-reduced, stored where no all-reduce follows
+__device__ __forceinline__ void bicg_gate_bo(double *pair, const double *triple, int64_t iter, int64_t *state)
+{
+    if (state[1] == BICG_CONVERGED_HALF && state[0] == iter) {
+        pair[0] = triple[2];
+        return;
+    }
+    if (state[1] != PCG_RUNNING) return;
+    const double ts = triple[0];
+    if (pair[0] <= reinterpret_cast<const double *>(state)[2]) {
+        state[0] = iter;
+        state[1] = PCG_CONVERGED;
+    } else if (ts == 0.0) {
+        state[0] = iter;
+        state[1] = PCG_BREAKDOWN;
+    }
+}
+
+// step 2, first stage: reduce_stage1<RED_DOT>'s grid, body, tail and order, gated
+__global__ __launch_bounds__(RT) void bicg_dot_kernel(const double *__restrict__ rhat, const double *__restrict__ v, int64_t n,
+                                                      const int64_t *__restrict__ state, double *__restrict__ partial)
+{
+    if (state[1] != PCG_RUNNING) return;
+    const int64_t n2 = n / 2;
+    const double2 *a2 = reinterpret_cast<const double2 *>(rhat);
+    const double2 *b2 = reinterpret_cast<const double2 *>(v);
+    double acc = 0.0;
+    int64_t i = (int64_t)blockIdx.x * RT + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * RT;
+    for (; i < n2; i += stride) {
+        const double2 a = a2[i], b = b2[i];
+        acc = acc + a.x * b.x;
+        acc = acc + a.y * b.y;
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) acc = acc + rhat[n - 1] * v[n - 1];
+    const double r = block_reduce<RED_SUM>(acc);
+    if (threadIdx.x == 0) partial[blockIdx.x] = r;
+}
+
+// second stage of rv (reduce_stage2<RED_SUM>'s order), one workgroup; records gate A where no all-reduce follows (gate != 0)
+__global__ __launch_bounds__(RT) void bicg_dot_stage2_kernel(const double *__restrict__ partial, int np,
+                                                             const double *__restrict__ rho, int64_t iter, int gate,
+                                                             int64_t *__restrict__ state, double *__restrict__ rv_out)
+{
+    if (state[1] != PCG_RUNNING) return;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < np; i += RT) acc = acc + partial[i];
+    const double rv = block_reduce<RED_SUM>(acc);
+    if (threadIdx.x == 0) {
+        rv_out[0] = rv;
+        if (gate) bicg_gate_a(rho[0], rv, iter, state);
+    }
+}
+
+__global__ void bicg_gate_a_kernel(const double *__restrict__ rho, const double *__restrict__ rv, int64_t iter,
+                                   int64_t *__restrict__ state)
+{
+    if (threadIdx.x == 0 && state[1] == PCG_RUNNING) bicg_gate_a(rho[0], rv[0], iter, state);
+}
+
+// step 3
+template <bool PRECOND>
+__global__ __launch_bounds__(256) void bicg_s_kernel(const double *__restrict__ rho, const double *__restrict__ rv,
+                                                     const double *__restrict__ r, const double *__restrict__ v,
+                                                     const double *__restrict__ dinv, double *__restrict__ s,
+                                                     double *__restrict__ sh, int64_t n, const int64_t *__restrict__ state)
+{
+    if (state[1] != PCG_RUNNING) return;
+    const double rh = rho[0], den = rv[0];
+    if (!(bicg_nonzero(rh) && bicg_nonzero(den))) return;         // gate A (recorded by the second stage of rv)
+    const double a = rh / den;
+    const int64_t n2 = n / 2;
+    const double2 *r2 = reinterpret_cast<const double2 *>(r);
+    const double2 *v2 = reinterpret_cast<const double2 *>(v);
+    const double2 *d2 = reinterpret_cast<const double2 *>(dinv);
+    double2 *s2 = reinterpret_cast<double2 *>(s);
+    double2 *h2 = reinterpret_cast<double2 *>(sh);
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (; i < n2; i += stride) {
+        const double2 rw = r2[i], vv = v2[i];
+        double2 sv;
+        sv.x = rw.x - a * vv.x;
+        sv.y = rw.y - a * vv.y;
+        s2[i] = sv;
+        if (PRECOND) {
+            const double2 dv = d2[i];
+            double2 hv;
+            hv.x = dv.x * sv.x;
+            hv.y = dv.y * sv.y;
+            h2[i] = hv;
+        }
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t j = n - 1;
+        const double sj = r[j] - a * v[j];
+        s[j] = sj;
+        if (PRECOND) sh[j] = dinv[j] * sj;
+    }
+}
+
+// step 5, first stage: the three sums in one pass over t and s
+__global__ __launch_bounds__(RT) void bicg_tts_kernel(const double *__restrict__ t, const double *__restrict__ s, int64_t n,
+                                                      const int64_t *__restrict__ state, double *__restrict__ partial_ts,
+                                                      double *__restrict__ partial_tt, double *__restrict__ partial_ss)
+{
+    if (state[1] != PCG_RUNNING) return;
+    const int64_t n2 = n / 2;
+    const double2 *t2 = reinterpret_cast<const double2 *>(t);
+    const double2 *s2 = reinterpret_cast<const double2 *>(s);
+    double ats = 0.0, att = 0.0, ass = 0.0;
+    int64_t i = (int64_t)blockIdx.x * RT + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * RT;
+    for (; i < n2; i += stride) {
+        const double2 tv = t2[i], sv = s2[i];
+        ats = ats + tv.x * sv.x;
+        ats = ats + tv.y * sv.y;
+        att = att + tv.x * tv.x;
+        att = att + tv.y * tv.y;
+        ass = ass + sv.x * sv.x;
+        ass = ass + sv.y * sv.y;
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const double tj = t[n - 1], sj = s[n - 1];
+        ats = ats + tj * sj;
+        att = att + tj * tj;
+        ass = ass + sj * sj;
+    }
+    const double a = block_reduce<RED_SUM>(ats);
+    if (threadIdx.x == 0) partial_ts[blockIdx.x] = a;
+    __syncthreads();                                             // block_reduce's LDS slots are reused
+    const double b = block_reduce<RED_SUM>(att);
+    if (threadIdx.x == 0) partial_tt[blockIdx.x] = b;
+    __syncthreads();
+    const double c = block_reduce<RED_SUM>(ass);
+    if (threadIdx.x == 0) partial_ss[blockIdx.x] = c;
+}
+
+// second stage of the triple, one workgroup; records gates S and T where no all-reduce follows (gate != 0)
+__global__ __launch_bounds__(RT) void bicg_tts_stage2_kernel(const double *__restrict__ partial_ts,
+                                                             const double *__restrict__ partial_tt,
+                                                             const double *__restrict__ partial_ss, int np, int64_t iter,
+                                                             int gate, int64_t *__restrict__ state,
+                                                             double *__restrict__ triple)
+{
+    if (state[1] != PCG_RUNNING) return;
+    double ats = 0.0, att = 0.0, ass = 0.0;
+    for (int i = threadIdx.x; i < np; i += RT) ats = ats + partial_ts[i];
+    const double ts = block_reduce<RED_SUM>(ats);
+    for (int i = threadIdx.x; i < np; i += RT) att = att + partial_tt[i];
+    __syncthreads();
+    const double tt = block_reduce<RED_SUM>(att);
+    for (int i = threadIdx.x; i < np; i += RT) ass = ass + partial_ss[i];
+    __syncthreads();
+    const double ss = block_reduce<RED_SUM>(ass);
+    if (threadIdx.x == 0) {
+        triple[0] = ts;
+        triple[1] = tt;
+        triple[2] = ss;
+        if (gate) bicg_gate_st(triple, iter, state);
+    }
+}
+
+__global__ void bicg_gate_st_kernel(const double *__restrict__ triple, int64_t iter, int64_t *__restrict__ state)
+{
+    if (threadIdx.x == 0 && state[1] == PCG_RUNNING) bicg_gate_st(triple, iter, state);
+}
+
+// step 6, first stage.  PRECOND = false: sh is s, loaded once
+template <bool NTX, bool NTT, bool PRECOND>
+__global__ __launch_bounds__(RT) void bicg_xr_kernel(const double *__restrict__ rho, const double *__restrict__ rv,
+                                                     const double *__restrict__ ts, const double *__restrict__ tt,
+                                                     const double *__restrict__ ph, const double *__restrict__ sh,
+                                                     const double *__restrict__ s, const double *__restrict__ t,
+                                                     const double *__restrict__ rhat, double *__restrict__ x,
+                                                     double *__restrict__ r, int64_t n, int64_t iter,
+                                                     const int64_t *__restrict__ state, double *__restrict__ partial_rr,
+                                                     double *__restrict__ partial_rho)
+{
+    const int64_t status = state[1];
+    const bool half = status == BICG_CONVERGED_HALF && state[0] == iter;
+    if (!(status == PCG_RUNNING || half)) return;
+    const double a = rho[0] / rv[0];
+    const int64_t n2 = n / 2;
+    const double2 *p2 = reinterpret_cast<const double2 *>(ph);
+    double2 *x2 = reinterpret_cast<double2 *>(x);
+    int64_t i = (int64_t)blockIdx.x * RT + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * RT;
+    if (half) {                                                  // gate S fired at this iteration: x = x + a*ph, nothing else
+        for (; i < n2; i += stride) {
+            const double2 pv = p2[i];
+            double2 xv = NTX ? nt_load2(x2 + i) : x2[i];
+            xv.x = xv.x + a * pv.x;
+            xv.y = xv.y + a * pv.y;
+            if (NTX) nt_store2(xv, x2 + i); else x2[i] = xv;
+        }
+        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) x[n - 1] = x[n - 1] + a * ph[n - 1];
+        return;
+    }
+    const double w = ts[0] / tt[0];
+    const double2 *h2 = reinterpret_cast<const double2 *>(sh);
+    const double2 *s2 = reinterpret_cast<const double2 *>(s);
+    const double2 *t2 = reinterpret_cast<const double2 *>(t);
+    const double2 *q2 = reinterpret_cast<const double2 *>(rhat);
+    double2 *r2 = reinterpret_cast<double2 *>(r);
+    double arr = 0.0, arho = 0.0;
+    for (; i < n2; i += stride) {
+        const double2 pv = p2[i], sv = s2[i], qv = q2[i];
+        const double2 tv = NTT ? nt_load2(t2 + i) : t2[i];
+        double2 hv = sv;
+        if (PRECOND) hv = h2[i];
+        double2 xv = NTX ? nt_load2(x2 + i) : x2[i], rw;
+        xv.x = (xv.x + a * pv.x) + w * hv.x;
+        xv.y = (xv.y + a * pv.y) + w * hv.y;
+        rw.x = sv.x - w * tv.x;
+        rw.y = sv.y - w * tv.y;
+        if (NTX) nt_store2(xv, x2 + i); else x2[i] = xv;
+        r2[i] = rw;
+        arr = arr + rw.x * rw.x;
+        arr = arr + rw.y * rw.y;
+        arho = arho + qv.x * rw.x;
+        arho = arho + qv.y * rw.y;
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t j = n - 1;
+        const double sj = s[j];
+        const double hj = PRECOND ? sh[j] : sj;
+        x[j] = (x[j] + a * ph[j]) + w * hj;
+        const double rn = sj - w * t[j];
+        r[j] = rn;
+        arr = arr + rn * rn;
+        arho = arho + rhat[j] * rn;
+    }
+    const double c = block_reduce<RED_SUM>(arr);
+    if (threadIdx.x == 0) partial_rr[blockIdx.x] = c;
+    __syncthreads();                                             // block_reduce's LDS slots are reused
+    const double d = block_reduce<RED_SUM>(arho);
+    if (threadIdx.x == 0) partial_rho[blockIdx.x] = d;
+}
+
+// second stage of (rr, rho'), one workgroup; records gates B and O where no all-reduce follows (gate != 0).  For the half
+// step of this iteration there are no sums: the gate only stores ss as the pair's first entry
+__global__ __launch_bounds__(RT) void bicg_xr_stage2_kernel(const double *__restrict__ partial_rr,
+                                                            const double *__restrict__ partial_rho, int np,
+                                                            const double *__restrict__ triple, int64_t iter, int gate,
+                                                            int64_t *__restrict__ state, double *__restrict__ pair)
+{
+    if (state[1] != PCG_RUNNING) {
+        if (gate && threadIdx.x == 0) bicg_gate_bo(pair, triple, iter, state);
+        return;
+    }
+    double arr = 0.0, arho = 0.0;
+    for (int i = threadIdx.x; i < np; i += RT) arr = arr + partial_rr[i];
+    const double rr = block_reduce<RED_SUM>(arr);
+    for (int i = threadIdx.x; i < np; i += RT) arho = arho + partial_rho[i];
+    __syncthreads();
+    const double rho_new = block_reduce<RED_SUM>(arho);
+    if (threadIdx.x == 0) {
+        pair[0] = rr;
+        pair[1] = rho_new;
+        if (gate) bicg_gate_bo(pair, triple, iter, state);
+    }
+}
+
+__global__ void bicg_gate_bo_kernel(double *__restrict__ pair, const double *__restrict__ triple, int64_t iter,
+                                    int64_t *__restrict__ state)
+{
+    if (threadIdx.x == 0) bicg_gate_bo(pair, triple, iter, state);
+}
+
+// step 7
+template <bool PRECOND>
+__global__ __launch_bounds__(256) void bicg_p_kernel(const double *__restrict__ rho_new, const double *__restrict__ rho,
+                                                     const double *__restrict__ rv, const double *__restrict__ ts,
+                                                     const double *__restrict__ tt, const double *__restrict__ r,
+                                                     const double *__restrict__ v, const double *__restrict__ dinv,
+                                                     double *__restrict__ p, double *__restrict__ ph, int64_t n,
+                                                     const int64_t *__restrict__ state)
+{
+    if (state[1] != PCG_RUNNING) return;
+    const double a = rho[0] / rv[0];
+    const double w = ts[0] / tt[0];
+    const double b = (rho_new[0] / rho[0]) * (a / w);
+    const int64_t n2 = n / 2;
+    const double2 *r2 = reinterpret_cast<const double2 *>(r);
+    const double2 *v2 = reinterpret_cast<const double2 *>(v);
+    const double2 *d2 = reinterpret_cast<const double2 *>(dinv);
+    double2 *p2 = reinterpret_cast<double2 *>(p);
+    double2 *h2 = reinterpret_cast<double2 *>(ph);
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (; i < n2; i += stride) {
+        const double2 rw = r2[i], vv = v2[i];
+        double2 pv = p2[i];
+        pv.x = rw.x + b * (pv.x - w * vv.x);
+        pv.y = rw.y + b * (pv.y - w * vv.y);
+        p2[i] = pv;
+        if (PRECOND) {
+            const double2 dv = d2[i];
+            double2 hv;
+            hv.x = dv.x * pv.x;
+            hv.y = dv.y * pv.y;
+            h2[i] = hv;
+        }
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t j = n - 1;
+        const double pj = r[j] + b * (p[j] - w * v[j]);
+        p[j] = pj;
+        if (PRECOND) ph[j] = dinv[j] * pj;
+    }
+}
+
 // MODE 0: y = y + a*x   MODE 1: y = x + a*y   MODE 2: y = a*x   MODE 3: y = x / a
 template <int MODE>
 __global__ __launch_bounds__(256) void update_kernel(double alpha, const double *__restrict__ num,
@@ -749,6 +1113,143 @@ HPCLA_API int hpcla_pcg_direction_f64(const double *a_num_dev, const double *a_d
     else if (m & 2) HPCLA_PCG_DIR(false, true);
     else HPCLA_PCG_DIR(false, false);
 #undef HPCLA_PCG_DIR
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
+// scratch of the gated BiCGStab steps: three arrays of stage-1 partials, then the solve's state (its last 32 bytes)
+HPCLA_API int64_t hpcla_bicgstab_work_bytes(void)
+{
+    return (int64_t)(BICG_PARTIAL_ARRAYS * MAX_PARTIALS + PCG_STATE_WORDS) * (int64_t)sizeof(double);
+}
+
+static inline bool bicg_misaligned(std::initializer_list<const void *> ptrs)
+{
+    uintptr_t m = 0;
+    for (const void *q : ptrs) m |= reinterpret_cast<uintptr_t>(q);
+    return (m & 15) != 0;
+}
+
+HPCLA_API int hpcla_bicg_dot_f64(hpcla_comm_t *comm, const double *rhat, const double *v, int64_t n, int64_t iter,
+                                 const double *rho_dev, int64_t *state_dev, double *rv_out_dev, void *work, void *stream)
+{
+    if (n < 0 || iter < 1) return set_error(HPCLA_ERR_INVALID, "bicg_dot: negative size or iteration < 1");
+    if (!rho_dev || !state_dev || !rv_out_dev || !work)
+        return set_error(HPCLA_ERR_INVALID, "bicg_dot: null scalar / state / out / work");
+    if (n > 0 && (!rhat || !v)) return set_error(HPCLA_ERR_INVALID, "bicg_dot: null vector");
+    if (bicg_misaligned({rhat, v})) return set_error(HPCLA_ERR_INVALID, "bicg_dot: vectors must be 16-byte aligned");
+    double *partial = reinterpret_cast<double *>(work);
+    const int g = reduce_grid(n);
+    hipStream_t s = as_stream(stream);
+    bicg_dot_kernel<<<g, RT, 0, s>>>(rhat, v, n, state_dev, partial);
+    HPCLA_CHECK_LAUNCH();
+    bicg_dot_stage2_kernel<<<1, RT, 0, s>>>(partial, g, rho_dev, iter, comm ? 0 : 1, state_dev, rv_out_dev);
+    HPCLA_CHECK_LAUNCH();
+    if (!comm) return HPCLA_OK;
+    const int rc = allreduce_on(comm, rv_out_dev, 1, 0, stream);
+    if (rc) return rc;
+    bicg_gate_a_kernel<<<1, 64, 0, s>>>(rho_dev, rv_out_dev, iter, state_dev);
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
+HPCLA_API int hpcla_bicg_s_f64(const double *rho_dev, const double *rv_dev, const double *r, const double *v,
+                               const double *dinv, double *s, double *sh, int64_t n, int64_t iter, const int64_t *state_dev,
+                               void *stream)
+{
+    if (n < 0 || iter < 1) return set_error(HPCLA_ERR_INVALID, "bicg_s: negative size or iteration < 1");
+    if (!rho_dev || !rv_dev || !state_dev) return set_error(HPCLA_ERR_INVALID, "bicg_s: null scalar / state");
+    if (n == 0) return HPCLA_OK;
+    if (!r || !v || !s || (dinv && !sh)) return set_error(HPCLA_ERR_INVALID, "bicg_s: null vector");
+    if (bicg_misaligned({r, v, dinv, s, dinv ? sh : nullptr}))
+        return set_error(HPCLA_ERR_INVALID, "bicg_s: vectors must be 16-byte aligned");
+    hipStream_t st = as_stream(stream);
+    if (dinv) bicg_s_kernel<true><<<ew_grid(n / 2), 256, 0, st>>>(rho_dev, rv_dev, r, v, dinv, s, sh, n, state_dev);
+    else bicg_s_kernel<false><<<ew_grid(n / 2), 256, 0, st>>>(rho_dev, rv_dev, r, v, nullptr, s, nullptr, n, state_dev);
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
+HPCLA_API int hpcla_bicg_tts_f64(hpcla_comm_t *comm, const double *t, const double *s, int64_t n, int64_t iter,
+                                 int64_t *state_dev, double *triple_out_dev, void *work, void *stream)
+{
+    if (n < 0 || iter < 1) return set_error(HPCLA_ERR_INVALID, "bicg_tts: negative size or iteration < 1");
+    if (!state_dev || !triple_out_dev || !work) return set_error(HPCLA_ERR_INVALID, "bicg_tts: null state / out / work");
+    if (n > 0 && (!t || !s)) return set_error(HPCLA_ERR_INVALID, "bicg_tts: null vector");
+    if (bicg_misaligned({t, s})) return set_error(HPCLA_ERR_INVALID, "bicg_tts: vectors must be 16-byte aligned");
+    double *p_ts = reinterpret_cast<double *>(work), *p_tt = p_ts + MAX_PARTIALS, *p_ss = p_tt + MAX_PARTIALS;
+    const int g = reduce_grid(n);
+    hipStream_t st = as_stream(stream);
+    bicg_tts_kernel<<<g, RT, 0, st>>>(t, s, n, state_dev, p_ts, p_tt, p_ss);
+    HPCLA_CHECK_LAUNCH();
+    bicg_tts_stage2_kernel<<<1, RT, 0, st>>>(p_ts, p_tt, p_ss, g, iter, comm ? 0 : 1, state_dev, triple_out_dev);
+    HPCLA_CHECK_LAUNCH();
+    if (!comm) return HPCLA_OK;
+    const int rc = allreduce_on(comm, triple_out_dev, 3, 0, stream);   // ts, tt and ss travel as ONE triple
+    if (rc) return rc;
+    bicg_gate_st_kernel<<<1, 64, 0, st>>>(triple_out_dev, iter, state_dev);
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
+HPCLA_API int hpcla_bicg_xr_f64(hpcla_comm_t *comm, const double *rho_dev, const double *rv_dev, const double *triple_dev,
+                                const double *ph, const double *sh, const double *s, const double *t, const double *rhat,
+                                double *x, double *r, int64_t n, int64_t iter, int64_t *state_dev, double *pair_out_dev,
+                                void *work, void *stream)
+{
+    if (n < 0 || iter < 1) return set_error(HPCLA_ERR_INVALID, "bicg_xr: negative size or iteration < 1");
+    if (!rho_dev || !rv_dev || !triple_dev || !state_dev || !pair_out_dev || !work)
+        return set_error(HPCLA_ERR_INVALID, "bicg_xr: null scalar / state / out / work");
+    if (n > 0 && (!ph || !s || !t || !rhat || !x || !r)) return set_error(HPCLA_ERR_INVALID, "bicg_xr: null vector");
+    if (bicg_misaligned({ph, sh, s, t, rhat, x, r}))
+        return set_error(HPCLA_ERR_INVALID, "bicg_xr: vectors must be 16-byte aligned");
+    double *p_rr = reinterpret_cast<double *>(work), *p_rho = p_rr + MAX_PARTIALS;
+    const int g = reduce_grid(n);
+    hipStream_t st = as_stream(stream);
+    const int m = cg_nt_mask();
+#define HPCLA_BICG_XR(NX, NT)                                                                                          \
+    do {                                                                                                               \
+        if (sh)                                                                                                        \
+            bicg_xr_kernel<NX, NT, true><<<g, RT, 0, st>>>(rho_dev, rv_dev, triple_dev, triple_dev + 1, ph, sh, s, t, rhat, x, \
+                                                           r, n, iter, state_dev, p_rr, p_rho);                        \
+        else                                                                                                           \
+            bicg_xr_kernel<NX, NT, false><<<g, RT, 0, st>>>(rho_dev, rv_dev, triple_dev, triple_dev + 1, ph, nullptr, s, t,  \
+                                                            rhat, x, r, n, iter, state_dev, p_rr, p_rho);              \
+    } while (0)
+    if ((m & 1) && (m & 4)) HPCLA_BICG_XR(true, true);
+    else if (m & 1) HPCLA_BICG_XR(true, false);
+    else if (m & 4) HPCLA_BICG_XR(false, true);
+    else HPCLA_BICG_XR(false, false);
+#undef HPCLA_BICG_XR
+    HPCLA_CHECK_LAUNCH();
+    bicg_xr_stage2_kernel<<<1, RT, 0, st>>>(p_rr, p_rho, g, triple_dev, iter, comm ? 0 : 1, state_dev, pair_out_dev);
+    HPCLA_CHECK_LAUNCH();
+    if (!comm) return HPCLA_OK;
+    const int rc = allreduce_on(comm, pair_out_dev, 2, 0, stream);     // rr and rho' travel as ONE pair
+    if (rc) return rc;
+    bicg_gate_bo_kernel<<<1, 64, 0, st>>>(pair_out_dev, triple_dev, iter, state_dev);
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
+HPCLA_API int hpcla_bicg_p_f64(const double *rho_new_dev, const double *rho_dev, const double *rv_dev,
+                               const double *triple_dev, const double *r, const double *v, const double *dinv, double *p,
+                               double *ph, int64_t n, int64_t iter, const int64_t *state_dev, void *stream)
+{
+    if (n < 0 || iter < 1) return set_error(HPCLA_ERR_INVALID, "bicg_p: negative size or iteration < 1");
+    if (!rho_new_dev || !rho_dev || !rv_dev || !triple_dev || !state_dev)
+        return set_error(HPCLA_ERR_INVALID, "bicg_p: null scalar / state");
+    if (n == 0) return HPCLA_OK;
+    if (!r || !v || !p || (dinv && !ph)) return set_error(HPCLA_ERR_INVALID, "bicg_p: null vector");
+    if (bicg_misaligned({r, v, dinv, p, dinv ? ph : nullptr}))
+        return set_error(HPCLA_ERR_INVALID, "bicg_p: vectors must be 16-byte aligned");
+    hipStream_t st = as_stream(stream);
+    if (dinv)
+        bicg_p_kernel<true><<<ew_grid(n / 2), 256, 0, st>>>(rho_new_dev, rho_dev, rv_dev, triple_dev, triple_dev + 1, r, v, dinv,
+                                                            p, ph, n, state_dev);
+    else
+        bicg_p_kernel<false><<<ew_grid(n / 2), 256, 0, st>>>(rho_new_dev, rho_dev, rv_dev, triple_dev, triple_dev + 1, r, v,
+                                                             nullptr, p, nullptr, n, state_dev);
     HPCLA_CHECK_LAUNCH();
     return HPCLA_OK;
 }
