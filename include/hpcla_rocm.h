@@ -1032,6 +1032,90 @@ int hpcla_bicgstab_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *com
                                       double *r, const double *rhat, double *p, double *ph, double *v, double *s,
                                       double *sh, double *t, double *hist_dev, double *scal_dev, void *work,
                                       int64_t first_iter, int iters, void *stream);
+/* ---- Restarted GMRES(m) for nonsymmetric A: gated steps of right-preconditioned GMRES with twice-applied classical
+ * Gram-Schmidt, K = identity or dinv .* (no reference counterpart; a caller of the reference's operators composes the method
+ * from A*p, src/sparse.jl:2096-2128, dot, src/vectors.jl:798-812, and the broadcasts, src/vectors.jl:1203-1226: 2c dots, 2c
+ * axpys and 2c + 1 host read-backs in the step that orthogonalises against c basis columns).
+ * The basis is V: restart + 1 columns of n doubles at pitch ldv >= n, ldv even, so that every column is 16-byte aligned.
+ * The state is the CG solver's (done_iter, status, thr, reserved) with one more status:
+ *   3 converged at a restart (the true residual's sum of squares <= thr at done_iter); callers report "converged".
+ * The small arrays of a solve live in ONE buffer of hpcla_gmres_small_offset(restart, 10) doubles; the offset of each is
+ * hpcla_gmres_small_offset(restart, which), which = 0 .. 9:  R (restart x restart, column j at R + j*restart), c, s (the
+ * rotations), g (restart + 1), h1, h2 (the two passes' coefficients), col (restart + 1, scratch), y, nn (w.w), hn (the
+ * divisor of hpcla_gmres_next_f64: sqrt(nn), or beta at a restart).  Both return -1 for a restart outside 1..64.
+ * Step `iter` is 1-based over the whole solve; every entry is a no-op writing no byte once status != 0 (solve and xupdate
+ * are ungated when state_dev == NULL).  Each reduction is all-reduced (comm != NULL) before it is used:
+ *   gmres_dots      h_out_dev[i] = V_i . w, i < ncols, all-reduced in slices of at most 8 sums.  A column's sum has the
+ *                   same bits whatever ncols is.  work: hpcla_gmres_work_bytes(restart) bytes with restart >= ncols.
+ *   gmres_update    w = ((w - h_dev[0]*V_0) - h_dev[1]*V_1) - ... in one pass.  small_dev == NULL: nothing else (restart,
+ *                   hist_k_dev and work are not used).  Else also nn = w.w, one all-reduce, and the small step of column
+ *                   j = ncols - 1:  col[i] = h1[i] + h2[i], col[ncols] = hn = sqrt(nn);  the stored rotations i < j
+ *                   (t = c_i*col[i] + s_i*col[i+1];  col[i+1] = (-s_i)*col[i] + c_i*col[i+1];  col[i] = t);
+ *                   d = sqrt(col[j]^2 + col[j+1]^2).  Gate D: !(d > 0), NaN included: status = 2, done_iter = iter - 1,
+ *                   nothing of column j stored.  Else c_j = col[j]/d, s_j = col[j+1]/d, R[0..j, j] = col[0..j-1], d;
+ *                   g[j+1] = (-s_j)*g[j], g[j] = c_j*g[j];  *hist_k_dev = g[j+1]^2.  Gate C: that <= thr: status = 1,
+ *                   done_iter = iter.
+ *   gmres_next      v_next = w / *hn_dev (a division);  z = dinv .* v_next when dinv != NULL (z may be NULL otherwise).
+ *   gmres_solve     y = R^-1 g over ncols columns by back substitution.
+ *   gmres_xupdate   u = y_dev[0]*V_0;  u = u + y_dev[i]*V_i ascending;  x = x + u, or x + dinv .* u.
+ *   gmres_residual  w = b - w (w holds A*x);  rr = w.w, one all-reduce.  Gate R at iter >= 0: rr <= thr: status = 3,
+ *                   done_iter = iter, *hist_k_dev = rr.  Else g = (sqrt(rr), 0, ...), hn = sqrt(rr), and *hist_k_dev = rr
+ *                   when iter == 0.
+ *   gmres_finish    the host's end of an open cycle, ungated: gmres_solve and gmres_xupdate over ncols columns; ncols == 0
+ *                   does nothing.
+ * Separate multiply, add, subtract, divide and sqrt, in the order written.  work: hpcla_gmres_work_bytes(restart) bytes --
+ * one array of partials per column (whole tiles of 8), then the 32 bytes the iterations entry uses as the state.  Vectors
+ * 16-byte aligned. */
+int64_t hpcla_gmres_work_bytes(int restart);
+int64_t hpcla_gmres_small_offset(int restart, int which);
+int hpcla_gmres_dots_f64(hpcla_comm_t *comm, const double *V, int64_t ldv, int ncols, const double *w, int64_t n,
+                         const int64_t *state_dev, double *h_out_dev, void *work, void *stream);
+int hpcla_gmres_update_f64(hpcla_comm_t *comm, const double *V, int64_t ldv, int ncols, const double *h_dev, double *w,
+                           int64_t n, int64_t iter, int restart, double *small_dev, double *hist_k_dev, int64_t *state_dev,
+                           void *work, void *stream);
+int hpcla_gmres_next_f64(const double *w, const double *hn_dev, const double *dinv, double *v_next, double *z, int64_t n,
+                         const int64_t *state_dev, void *stream);
+int hpcla_gmres_solve_f64(int ncols, int restart, double *small_dev, const int64_t *state_dev, void *stream);
+int hpcla_gmres_xupdate_f64(const double *V, int64_t ldv, int ncols, const double *y_dev, const double *dinv, double *x,
+                            int64_t n, const int64_t *state_dev, void *stream);
+int hpcla_gmres_residual_f64(hpcla_comm_t *comm, const double *b, double *w, int64_t n, int64_t iter, int restart,
+                             double *small_dev, double *hist_k_dev, int64_t *state_dev, void *work, void *stream);
+int hpcla_gmres_finish_f64(const double *V, int64_t ldv, int ncols, int restart, double *small_dev, const double *dinv,
+                           double *x, int64_t n, void *stream);
+/* Steps first_iter .. first_iter + iters - 1 enqueued by ONE host call: per step w = A*z through hpcla_spmv_dist_* (always
+ * executed; z is basis column j = (k-1) mod restart when dinv == NULL, and z may then be NULL), dots, update, dots, update
+ * with the small step, and gmres_next while j + 1 < restart; at j + 1 == restart, all gated, gmres_solve, gmres_xupdate and
+ * the restart (below) at iteration k.  hist_dev: pairs as for the other solvers, [2k] = the Givens estimate g[j+1]^2 of
+ * sum r_k^2 (the true one at k = 0 and at a gate R stop), [2k+1] not used.  The state lives in the last 32 bytes of work and
+ * is set up by the caller.  Everything else as for hpcla_bicgstab_iterations_*.  Only enqueues. */
+int hpcla_gmres_iterations_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int32_t *rowptr,
+                                   const int32_t *colval_split, const int16_t *cols16,
+                                   const hpcla_block_patterns_t *patterns, const double *nzval, int64_t nrows, int64_t nnz,
+                                   int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                   const int32_t *boundary_blocks, int64_t n_boundary, const double *dinv, const double *b,
+                                   double *x, double *V, int64_t ldv, double *w, double *z, double *small_dev,
+                                   double *hist_dev, void *work, int restart, int64_t first_iter, int iters, void *stream);
+int hpcla_gmres_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int64_t *rowptr,
+                                   const int64_t *colval_split, const double *nzval, int64_t nrows, int64_t nnz,
+                                   int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                   const int32_t *boundary_blocks, int64_t n_boundary, const double *dinv, const double *b,
+                                   double *x, double *V, int64_t ldv, double *w, double *z, double *small_dev,
+                                   double *hist_dev, void *work, int restart, int64_t first_iter, int iters, void *stream);
+/* The start of a cycle at iteration iter >= 0: w = A*x, gmres_residual, then V_0 = w / beta [z = dinv .* V_0] into the
+ * first column of V.  The solver's setup from a given x0 (iter = 0) and the end of every full cycle. */
+int hpcla_gmres_restart_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int32_t *rowptr,
+                                const int32_t *colval_split, const int16_t *cols16, const hpcla_block_patterns_t *patterns,
+                                const double *nzval, int64_t nrows, int64_t nnz, int index_base,
+                                const int32_t *interior_blocks, int64_t n_interior, const int32_t *boundary_blocks,
+                                int64_t n_boundary, const double *dinv, const double *b, const double *x, double *V,
+                                int64_t ldv, double *w, double *z, double *small_dev, double *hist_dev, void *work,
+                                int restart, int64_t iter, void *stream);
+int hpcla_gmres_restart_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int64_t *rowptr,
+                                const int64_t *colval_split, const double *nzval, int64_t nrows, int64_t nnz, int index_base,
+                                const int32_t *interior_blocks, int64_t n_interior, const int32_t *boundary_blocks,
+                                int64_t n_boundary, const double *dinv, const double *b, const double *x, double *V,
+                                int64_t ldv, double *w, double *z, double *small_dev, double *hist_dev, void *work,
+                                int restart, int64_t iter, void *stream);
 int hpcla_divide_f64(const double *x, double a_host, double *y, int64_t n, void *stream);
 int hpcla_axpby_f64(double a, const double *x, double b, const double *y, double *z, int64_t n,
                     void *stream);

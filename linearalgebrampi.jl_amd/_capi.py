@@ -167,6 +167,24 @@ _SIGNATURES = {
                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
     "hpcla_bicgstab_iterations_f64_i64": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
+    # restarted GMRES (hp.gmres): the gated steps, the chunk of inner steps, the start and the finish of a cycle
+    "hpcla_gmres_work_bytes": [_i32],
+    "hpcla_gmres_small_offset": [_i32, _i32],
+    "hpcla_gmres_dots_f64": [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp],
+    "hpcla_gmres_update_f64": [_vp, _vp, _i64, _i32, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp],
+    "hpcla_gmres_next_f64": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
+    "hpcla_gmres_solve_f64": [_i32, _i32, _vp, _vp, _vp],
+    "hpcla_gmres_xupdate_f64": [_vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp],
+    "hpcla_gmres_residual_f64": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp],
+    "hpcla_gmres_finish_f64": [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp],
+    "hpcla_gmres_iterations_f64_i32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
+                                       _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp],
+    "hpcla_gmres_iterations_f64_i64": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
+                                       _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp],
+    "hpcla_gmres_restart_f64_i32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
+                                    _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp],
+    "hpcla_gmres_restart_f64_i64": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
+                                    _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp],
     "hpcla_colspace_work_bytes": [_i64],
     "hpcla_compress_columns_i32": [_vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
     "hpcla_compress_columns_i64": [_vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
@@ -275,6 +293,8 @@ _RESTYPES = {
     "hpcla_cols16_padded_len": _i64,
     "hpcla_pcg_work_bytes": _i64,
     "hpcla_bicgstab_work_bytes": _i64,
+    "hpcla_gmres_work_bytes": _i64,
+    "hpcla_gmres_small_offset": _i64,
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

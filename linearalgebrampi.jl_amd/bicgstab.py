@@ -64,20 +64,20 @@ class BiCGStabWorkspace(_PairHistory):
             self.ph, self.sh = self.x.similar(), self.x.similar()
 
 
-def _bicgstab_dinv(A, b: HPCVector, M) -> Optional[HPCVector]:
+def _bicgstab_dinv(A, b: HPCVector, M, name: str = "bicgstab") -> Optional[HPCVector]:
     if M is None:
         return None
     if isinstance(M, str):
         if M != "jacobi":
-            raise ValueError(f"bicgstab: unknown preconditioner {M!r} (None, 'jacobi' or an HPCVector of 1 ./ diagonal)")
+            raise ValueError(f"{name}: unknown preconditioner {M!r} (None, 'jacobi' or an HPCVector of 1 ./ diagonal)")
         from .indexing import diag
         dinv = diag(A, reciprocal=True)
         # minimum(abs(diag(A))) > 0  <=>  maximum(abs(1 ./ diag(A))) is finite (a missing or zero entry gives Inf)
         if not math.isfinite(norm(dinv, math.inf)):
-            raise ValueError("bicgstab: M='jacobi' needs a diagonal without zeros (minimum(abs(diag(A))) > 0)")
+            raise ValueError(f"{name}: M='jacobi' needs a diagonal without zeros (minimum(abs(diag(A))) > 0)")
         return dinv
     if not isinstance(M, HPCVector):
-        raise ValueError("bicgstab: M must be None, 'jacobi' or an HPCVector on A's row partition")
+        raise ValueError(f"{name}: M must be None, 'jacobi' or an HPCVector on A's row partition")
     b._same_partition(M)
     return M
 

@@ -1271,3 +1271,158 @@ HPCLA_API int hpcla_bicgstab_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_c
                                              boundary_blocks, n_boundary, dinv, x, r, rhat, p, ph, v, s, sh, t, hist_dev,
                                              scal_dev, work, first_iter, iters, stream);
 }
+
+// ---- a chunk of gated GMRES(m) inner steps in ONE host call (the solver, hp.gmres) -----------------------------------
+// Right-preconditioned restarted GMRES with twice-applied classical Gram-Schmidt, K = identity (dinv == NULL: the SpMV reads
+// the basis column itself) or dinv .*.  Step k = first_iter .. first_iter + iters - 1 (1-based over the whole solve), column
+// j = (k - 1) mod m, c = j + 1 (the gates and the bytes: csrc/vecops.hip):
+//   1. w = A z                      hpcla_spmv_dist_* -- always executed, not gated, no dot partials
+//   2. h1 = V^T w                   hpcla_gmres_dots_f64: ceil(c / 8) all-reduces of at most 8 sums
+//   3. w = w - V h1                 hpcla_gmres_update_f64, first pass
+//   4. h2 = V^T w                   the dots again
+//   5. w = w - V h2, nn = w.w       hpcla_gmres_update_f64, second pass: one all-reduce [nn], the small step, gates D and C
+//   6. V_{j+1} = w / col_c  [z]     hpcla_gmres_next_f64 while c < m
+//   at c == m, every launch gated:  hpcla_gmres_solve_f64, hpcla_gmres_xupdate_f64 and the restart (w = A x, w = b - w, gate R,
+//                                   V_0 = w / beta [z]) -- one more SpMV per cycle
+// One rank: SpMV + 6 + 2 ceil(c / 8) launches per step.  N ranks: + 2 ceil(c / 8) + 1 window all-reduces and one 64-lane
+// small-step launch.  hist_dev[2 k] = g[j+1]^2, the Givens estimate of sum r_k^2 (the true one at a gate R stop and at k = 0);
+// hist_dev[2 k + 1] is not used (the layout is the other solvers' history of pairs).
+template <typename I, typename F, typename G>
+static int gmres_restart_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const I *rowptr,
+                              const I *colval, const int16_t *cols16, const hpcla_block_patterns *patterns, const double *nzval,
+                              int64_t nrows, int64_t nnz, int index_base, const int32_t *interior, int64_t n_interior,
+                              const int32_t *boundary, int64_t n_boundary, const double *dinv, const double *b, const double *x,
+                              double *V, double *w, double *z, double *small_dev, double *hist_dev, int64_t *state, void *work,
+                              int restart, int64_t iter, void *stream)
+{
+    int rc = spmv_dist_impl<I>(split_fn, fused_fn, plan, rowptr, colval, nzval, x, nrows, w, nrows, nnz, index_base, interior,
+                               n_interior, boundary, n_boundary, stream, nullptr, cols16, patterns);
+    if (rc) return rc;
+    rc = hpcla_gmres_residual_f64(comm, b, w, nrows, iter, restart, small_dev, hist_dev + 2 * iter, state, work, stream);
+    if (rc) return rc;
+    const double *hn = small_dev + hpcla_gmres_small_offset(restart, 9);
+    return hpcla_gmres_next_f64(w, hn, dinv, V, dinv ? z : nullptr, nrows, state, stream);
+}
+
+static int gmres_check(const char *who, int64_t nrows, int64_t nnz, int64_t ldv, int restart, const double *dinv, const double *b,
+                       const double *x, const double *V, const double *w, const double *z, const double *small_dev,
+                       const double *hist_dev, const void *work)
+{
+    if (nrows < 0 || nnz < 0) return set_error(HPCLA_ERR_INVALID, "%s: negative size", who);
+    if (restart < 1 || restart > 64) return set_error(HPCLA_ERR_INVALID, "%s: restart must be in 1..64", who);
+    if (ldv < nrows || (ldv & 1)) return set_error(HPCLA_ERR_INVALID, "%s: the pitch must be even and at least nrows", who);
+    if (!small_dev || !hist_dev || !work) return set_error(HPCLA_ERR_INVALID, "%s: null small arrays / history / work", who);
+    if (nrows > 0 && (!b || !x || !V || !w || (dinv && !z))) return set_error(HPCLA_ERR_INVALID, "%s: null vector", who);
+    if ((reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(V) |
+         reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(dinv) | (dinv ? reinterpret_cast<uintptr_t>(z) : 0)) & 15)
+        return set_error(HPCLA_ERR_INVALID, "%s: vectors must be 16-byte aligned", who);
+    return HPCLA_OK;
+}
+
+template <typename I, typename F, typename G>
+static int gmres_iterations_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const I *rowptr,
+                                 const I *colval, const int16_t *cols16, const hpcla_block_patterns *patterns,
+                                 const double *nzval, int64_t nrows, int64_t nnz, int index_base, const int32_t *interior,
+                                 int64_t n_interior, const int32_t *boundary, int64_t n_boundary, const double *dinv,
+                                 const double *b, double *x, double *V, int64_t ldv, double *w, double *z, double *small_dev,
+                                 double *hist_dev, void *work, int restart, int64_t first_iter, int iters, void *stream)
+{
+    if (iters < 0 || first_iter < 1) return set_error(HPCLA_ERR_INVALID, "gmres_iterations: negative count or first_iter < 1");
+    if (int rc = gmres_check("gmres_iterations", nrows, nnz, ldv, restart, dinv, b, x, V, w, z, small_dev, hist_dev, work)) return rc;
+    int64_t *state = reinterpret_cast<int64_t *>(static_cast<char *>(work) + hpcla_gmres_work_bytes(restart)) - 4;
+    double *h1 = small_dev + hpcla_gmres_small_offset(restart, 4), *h2 = small_dev + hpcla_gmres_small_offset(restart, 5);
+    double *y = small_dev + hpcla_gmres_small_offset(restart, 7), *hn = small_dev + hpcla_gmres_small_offset(restart, 9);
+    for (int64_t k = first_iter; k < first_iter + iters; ++k) {
+        const int j = (int)((k - 1) % restart), c = j + 1;
+        const double *in = dinv ? z : V + (int64_t)j * ldv;
+        int rc = spmv_dist_impl<I>(split_fn, fused_fn, plan, rowptr, colval, nzval, in, nrows, w, nrows, nnz, index_base, interior,
+                                   n_interior, boundary, n_boundary, stream, nullptr, cols16, patterns);
+        if (rc) return rc;
+        rc = hpcla_gmres_dots_f64(comm, V, ldv, c, w, nrows, state, h1, work, stream);
+        if (rc) return rc;
+        rc = hpcla_gmres_update_f64(comm, V, ldv, c, h1, w, nrows, k, restart, nullptr, nullptr, state, work, stream);
+        if (rc) return rc;
+        rc = hpcla_gmres_dots_f64(comm, V, ldv, c, w, nrows, state, h2, work, stream);
+        if (rc) return rc;
+        rc = hpcla_gmres_update_f64(comm, V, ldv, c, h2, w, nrows, k, restart, small_dev, hist_dev + 2 * k, state, work, stream);
+        if (rc) return rc;
+        if (c < restart) {
+            rc = hpcla_gmres_next_f64(w, hn, dinv, V + (int64_t)c * ldv, dinv ? z : nullptr, nrows, state, stream);
+            if (rc) return rc;
+            continue;
+        }
+        rc = hpcla_gmres_solve_f64(c, restart, small_dev, state, stream);
+        if (rc) return rc;
+        rc = hpcla_gmres_xupdate_f64(V, ldv, c, y, dinv, x, nrows, state, stream);
+        if (rc) return rc;
+        rc = gmres_restart_impl<I>(split_fn, fused_fn, plan, comm, rowptr, colval, cols16, patterns, nzval, nrows, nnz, index_base,
+                                   interior, n_interior, boundary, n_boundary, dinv, b, x, V, w, z, small_dev, hist_dev, state,
+                                   work, restart, k, stream);
+        if (rc) return rc;
+    }
+    return HPCLA_OK;
+}
+
+HPCLA_API int hpcla_gmres_iterations_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int32_t *rowptr,
+                                             const int32_t *colval_split, const int16_t *cols16,
+                                             const hpcla_block_patterns_t *patterns, const double *nzval, int64_t nrows,
+                                             int64_t nnz, int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                             const int32_t *boundary_blocks, int64_t n_boundary, const double *dinv,
+                                             const double *b, double *x, double *V, int64_t ldv, double *w, double *z,
+                                             double *small_dev, double *hist_dev, void *work, int restart, int64_t first_iter,
+                                             int iters, void *stream)
+{
+    return gmres_iterations_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, comm, rowptr, colval_split, cols16, patterns,
+                                          nzval, nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks,
+                                          n_boundary, dinv, b, x, V, ldv, w, z, small_dev, hist_dev, work, restart, first_iter,
+                                          iters, stream);
+}
+
+HPCLA_API int hpcla_gmres_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int64_t *rowptr,
+                                             const int64_t *colval_split, const double *nzval, int64_t nrows, int64_t nnz,
+                                             int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                             const int32_t *boundary_blocks, int64_t n_boundary, const double *dinv,
+                                             const double *b, double *x, double *V, int64_t ldv, double *w, double *z,
+                                             double *small_dev, double *hist_dev, void *work, int restart, int64_t first_iter,
+                                             int iters, void *stream)
+{
+    return gmres_iterations_impl<int64_t>(spmv_split_i64, spmv_fused_i64, plan, comm, rowptr, colval_split, nullptr, nullptr,
+                                          nzval, nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks,
+                                          n_boundary, dinv, b, x, V, ldv, w, z, small_dev, hist_dev, work, restart, first_iter,
+                                          iters, stream);
+}
+
+// The start of a cycle at iteration iter >= 0 on its own (the solver's setup from a given x0): w = A x, w = b - w, gate R,
+// g = (beta, 0, ...), V_0 = w / beta [z = dinv .* V_0].  hist_dev[2 iter] receives w.w at iter = 0 and at a gate R stop.
+HPCLA_API int hpcla_gmres_restart_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int32_t *rowptr,
+                                          const int32_t *colval_split, const int16_t *cols16,
+                                          const hpcla_block_patterns_t *patterns, const double *nzval, int64_t nrows, int64_t nnz,
+                                          int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                          const int32_t *boundary_blocks, int64_t n_boundary, const double *dinv,
+                                          const double *b, const double *x, double *V, int64_t ldv, double *w, double *z,
+                                          double *small_dev, double *hist_dev, void *work, int restart, int64_t iter,
+                                          void *stream)
+{
+    if (iter < 0) return set_error(HPCLA_ERR_INVALID, "gmres_restart: negative iteration");
+    if (int rc = gmres_check("gmres_restart", nrows, nnz, ldv, restart, dinv, b, x, V, w, z, small_dev, hist_dev, work)) return rc;
+    int64_t *state = reinterpret_cast<int64_t *>(static_cast<char *>(work) + hpcla_gmres_work_bytes(restart)) - 4;
+    return gmres_restart_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, comm, rowptr, colval_split, cols16, patterns, nzval,
+                                       nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks, n_boundary, dinv, b,
+                                       x, V, w, z, small_dev, hist_dev, state, work, restart, iter, stream);
+}
+
+HPCLA_API int hpcla_gmres_restart_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int64_t *rowptr,
+                                          const int64_t *colval_split, const double *nzval, int64_t nrows, int64_t nnz,
+                                          int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                          const int32_t *boundary_blocks, int64_t n_boundary, const double *dinv,
+                                          const double *b, const double *x, double *V, int64_t ldv, double *w, double *z,
+                                          double *small_dev, double *hist_dev, void *work, int restart, int64_t iter,
+                                          void *stream)
+{
+    if (iter < 0) return set_error(HPCLA_ERR_INVALID, "gmres_restart: negative iteration");
+    if (int rc = gmres_check("gmres_restart", nrows, nnz, ldv, restart, dinv, b, x, V, w, z, small_dev, hist_dev, work)) return rc;
+    int64_t *state = reinterpret_cast<int64_t *>(static_cast<char *>(work) + hpcla_gmres_work_bytes(restart)) - 4;
+    return gmres_restart_impl<int64_t>(spmv_split_i64, spmv_fused_i64, plan, comm, rowptr, colval_split, nullptr, nullptr, nzval,
+                                       nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks, n_boundary, dinv, b,
+                                       x, V, w, z, small_dev, hist_dev, state, work, restart, iter, stream);
+}

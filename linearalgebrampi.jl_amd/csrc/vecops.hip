@@ -10,7 +10,7 @@
 
 #include <initializer_list>
 
-#include "common.h"
+#include "comm_internal.h"
 
 namespace hpcla {
 
@@ -810,6 +810,361 @@ __global__ __launch_bounds__(256) void bicg_p_kernel(const double *__restrict__ 
     }
 }
 
+// ---- gated GMRES(m) steps (the solver hpcla_gmres_iterations_*; right preconditioning, K = identity or dinv .*) ---------
+// Inner step k (1-based over the whole solve), column j = (k - 1) mod m, c = j + 1 basis columns V_0 .. V_j at pitch ldv (even,
+// so every column is 16-byte aligned); w = A z is the SpMV's, ungated (z is V_j without a preconditioner).  Classical
+// Gram-Schmidt applied twice (CGS2).  Bytes per row:
+//   gmres_dots     h[i] = V_i . w, i < c, tiles of GMRES_TILE columns        read w once per tile, c columns      8 c + 8 ceil(c/8)
+//   gmres_update   w = ((w - h[0] V_0) - h[1] V_1) - ...  in ONE pass         read c columns, read and write w     8 c + 16
+//                  (the second pass also emits the partials of w.w)
+//   gmres_next     V_{j+1} = w / col_c  [z = dinv .* V_{j+1}]                read w [dinv], write V_{j+1} [z]     16 / 32
+// dots, update, dots, update, next: 32 c + 48 + 16 ceil(c/8) per step (16 more with dinv) in 6 + 2 ceil(c/8) launches and no
+// read-back; composed from dot and axpy it is 2 c dots at 16 and 2 c axpys at 24: 80 c, 4 c launches, 2 c + 1 read-backs.
+//   gmres_xupdate  u = y[0] V_0;  u = u + y[i] V_i;  x = x + u  or  x + dinv .* u    once per cycle: 8 c + 16 [+ 8]
+//   gmres_residual w = b - w (w holds A x), partials of w.w                  once per cycle: 24
+// Every multiply, add, subtract, divide and sqrt is rounded separately, in the order written.  The accumulators of gmres_dots
+// are a compile-time tile held in registers; a column's sum uses the grid, body, tail and order of reduce_stage1 whatever
+// rides along, so it has the same bits for every c.
+//
+// The state is PCG's (done_iter, status, thr, reserved) with one more status, reported as converged:
+//   3 converged at a restart: the true residual's w.w <= thr at k = done_iter (gate R); hist[k] then holds that w.w
+// The small step (one thread, redundantly on every rank from all-reduced values) and its gates, each needing status == 0:
+//   col[i] = h1[i] + h2[i];  col[c] = sqrt(nn);  the stored rotations i < j;  d = sqrt(col[j]^2 + col[j+1]^2)
+//   D  !(d > 0), NaN included           -> breakdown, done_iter = k - 1; nothing of column j is stored
+//   c_j, s_j, R[0..j, j], g[j], g[j+1];  hist[k] = g[j+1]^2
+//   C  hist[k] <= thr                   -> converged, done_iter = k (a lucky breakdown, nn = 0, gives g[j+1] = 0 and ends here)
+// Cache policy: x in gmres_xupdate goes non-temporally under HPCLA_CG_NT bit 0; basis columns are re-read every step and stay
+// plain.
+constexpr int64_t GMRES_CONVERGED_RESTART = 3;
+constexpr int GMRES_TILE = AR_MAX;             // on purpose: one tile of sums is one window all-reduce
+constexpr int GMRES_MAX_RESTART = 64;
+
+// the small arrays of a solve, all in one buffer of gmres_small_layout(m, ...) doubles
+struct GmresSmall {
+    double *R, *cs, *sn, *g, *h1, *h2, *col, *y, *nn, *hn;   // R: m x m, column j at R + j m;  g, col: m + 1;  nn, hn: 1
+};
+
+static void gmres_small_offsets(int m, int64_t off[11])         // off[10]: the buffer's length
+{
+    const int64_t len[10] = {(int64_t)m * m, m, m, m + 1, m, m, m + 1, m, 1, 1};
+    off[0] = 0;
+    for (int i = 0; i < 10; ++i) off[i + 1] = off[i] + len[i];
+}
+
+static void gmres_small_layout(int m, double *base, GmresSmall *q)
+{
+    int64_t off[11];
+    gmres_small_offsets(m, off);
+    *q = GmresSmall{base + off[0], base + off[1], base + off[2], base + off[3], base + off[4],
+                    base + off[5], base + off[6], base + off[7], base + off[8], base + off[9]};
+}
+
+__device__ void gmres_small_step(const GmresSmall &q, int j, int m, double nn, double *hist_k, int64_t iter, int64_t *state)
+{
+    const int c = j + 1;
+    for (int i = 0; i < c; ++i) q.col[i] = q.h1[i] + q.h2[i];
+    const double hn = sqrt(nn);
+    q.col[c] = hn;
+    q.hn[0] = hn;
+    for (int i = 0; i < j; ++i) {
+        const double ci = q.cs[i], si = q.sn[i], a = q.col[i], b = q.col[i + 1];
+        const double t = ci * a + si * b;
+        q.col[i + 1] = (-si) * a + ci * b;
+        q.col[i] = t;
+    }
+    const double a = q.col[j], b = q.col[j + 1];
+    const double d = sqrt(a * a + b * b);
+    if (!(d > 0.0)) {                                            // gate D
+        state[0] = iter - 1;
+        state[1] = PCG_BREAKDOWN;
+        return;
+    }
+    const double cj = a / d, sj = b / d;
+    q.cs[j] = cj;
+    q.sn[j] = sj;
+    double *Rj = q.R + (int64_t)j * m;
+    for (int i = 0; i < j; ++i) Rj[i] = q.col[i];
+    Rj[j] = d;
+    const double gj = q.g[j];
+    const double gn = (-sj) * gj;
+    q.g[j + 1] = gn;
+    q.g[j] = cj * gj;
+    const double e = gn * gn;
+    hist_k[0] = e;
+    if (e <= reinterpret_cast<const double *>(state)[2]) {       // gate C
+        state[0] = iter;
+        state[1] = PCG_CONVERGED;
+    }
+}
+
+// gate R and the start of a cycle: beta = sqrt(rr), g = (beta, 0, ...).  hist[0] is the true residual's whatever the gate says
+__device__ void gmres_restart_gate(const GmresSmall &q, int m, double rr, double *hist_k, int64_t iter, int64_t *state)
+{
+    if (rr <= reinterpret_cast<const double *>(state)[2]) {
+        hist_k[0] = rr;
+        state[0] = iter;
+        state[1] = GMRES_CONVERGED_RESTART;
+        return;
+    }
+    if (iter == 0) hist_k[0] = rr;
+    const double beta = sqrt(rr);
+    q.g[0] = beta;
+    for (int i = 1; i <= m; ++i) q.g[i] = 0.0;
+    q.hn[0] = beta;
+}
+
+// first stage of T <= GMRES_TILE sums V_t . w: reduce_stage1<RED_DOT>'s grid, body, tail and order per column, w loaded once
+template <int T>
+__global__ __launch_bounds__(RT) void gmres_dots_kernel(const double *__restrict__ V, int64_t ldv, const double *__restrict__ w,
+                                                        int64_t n, const int64_t *__restrict__ state,
+                                                        double *__restrict__ partial)
+{
+    if (state[1] != PCG_RUNNING) return;
+    const int64_t n2 = n / 2, ld2 = ldv / 2;
+    const double2 *V2 = reinterpret_cast<const double2 *>(V);
+    const double2 *w2 = reinterpret_cast<const double2 *>(w);
+    double acc[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) acc[t] = 0.0;
+    int64_t i = (int64_t)blockIdx.x * RT + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * RT;
+    for (; i < n2; i += stride) {
+        const double2 wv = w2[i];
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const double2 vv = V2[(int64_t)t * ld2 + i];
+            acc[t] = acc[t] + vv.x * wv.x;
+            acc[t] = acc[t] + vv.y * wv.y;
+        }
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const double wj = w[n - 1];
+#pragma unroll
+        for (int t = 0; t < T; ++t) acc[t] = acc[t] + V[(int64_t)t * ldv + n - 1] * wj;
+    }
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        if (t) __syncthreads();                                  // block_reduce's LDS slots are reused
+        const double r = block_reduce<RED_SUM>(acc[t]);
+        if (threadIdx.x == 0) partial[(int64_t)t * MAX_PARTIALS + blockIdx.x] = r;
+    }
+}
+
+// second stage: workgroup i sums the partials of column i in index order (reduce_stage2<RED_SUM>'s order)
+__global__ __launch_bounds__(RT) void gmres_dots_stage2_kernel(const double *__restrict__ partial, int np,
+                                                               const int64_t *__restrict__ state, double *__restrict__ h_out)
+{
+    if (state[1] != PCG_RUNNING) return;
+    const double *p = partial + (int64_t)blockIdx.x * MAX_PARTIALS;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < np; i += RT) acc = acc + p[i];
+    const double r = block_reduce<RED_SUM>(acc);
+    if (threadIdx.x == 0) h_out[blockIdx.x] = r;
+}
+
+// the running subtraction over all c columns in one pass; SUMSQ also emits the partials of w.w (of the final w)
+template <bool SUMSQ>
+__global__ __launch_bounds__(RT) void gmres_update_kernel(const double *__restrict__ V, int64_t ldv, int c,
+                                                          const double *__restrict__ h, double *__restrict__ w, int64_t n,
+                                                          const int64_t *__restrict__ state, double *__restrict__ partial)
+{
+    if (state[1] != PCG_RUNNING) return;
+    const int64_t n2 = n / 2, ld2 = ldv / 2;
+    const double2 *V2 = reinterpret_cast<const double2 *>(V);
+    double2 *w2 = reinterpret_cast<double2 *>(w);
+    double acc = 0.0;
+    int64_t i = (int64_t)blockIdx.x * RT + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * RT;
+    for (; i < n2; i += stride) {
+        double2 wv = w2[i];
+#pragma unroll 4
+        for (int t = 0; t < c; ++t) {
+            const double ht = h[t];
+            const double2 vv = V2[(int64_t)t * ld2 + i];
+            wv.x = wv.x - ht * vv.x;
+            wv.y = wv.y - ht * vv.y;
+        }
+        w2[i] = wv;
+        if (SUMSQ) {
+            acc = acc + wv.x * wv.x;
+            acc = acc + wv.y * wv.y;
+        }
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        double wj = w[n - 1];
+        for (int t = 0; t < c; ++t) wj = wj - h[t] * V[(int64_t)t * ldv + n - 1];
+        w[n - 1] = wj;
+        if (SUMSQ) acc = acc + wj * wj;
+    }
+    if (SUMSQ) {
+        const double r = block_reduce<RED_SUM>(acc);
+        if (threadIdx.x == 0) partial[blockIdx.x] = r;
+    }
+}
+
+// second stage of w.w, one workgroup; runs the small step where no all-reduce follows (gate != 0)
+__global__ __launch_bounds__(RT) void gmres_update_stage2_kernel(const double *__restrict__ partial, int np, GmresSmall q, int j,
+                                                                 int m, double *__restrict__ hist_k, int64_t iter, int gate,
+                                                                 int64_t *__restrict__ state)
+{
+    if (state[1] != PCG_RUNNING) return;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < np; i += RT) acc = acc + partial[i];
+    const double nn = block_reduce<RED_SUM>(acc);
+    if (threadIdx.x == 0) {
+        q.nn[0] = nn;
+        if (gate) gmres_small_step(q, j, m, nn, hist_k, iter, state);
+    }
+}
+
+__global__ void gmres_small_step_kernel(GmresSmall q, int j, int m, double *__restrict__ hist_k, int64_t iter,
+                                        int64_t *__restrict__ state)
+{
+    if (threadIdx.x == 0 && state[1] == PCG_RUNNING) gmres_small_step(q, j, m, q.nn[0], hist_k, iter, state);
+}
+
+// V_{j+1} = w / col_c: a division, not a multiplication by the reciprocal
+template <bool PRECOND>
+__global__ __launch_bounds__(256) void gmres_next_kernel(const double *__restrict__ w, const double *__restrict__ hn,
+                                                         const double *__restrict__ dinv, double *__restrict__ v,
+                                                         double *__restrict__ z, int64_t n, const int64_t *__restrict__ state)
+{
+    if (state[1] != PCG_RUNNING) return;
+    const double d = hn[0];
+    const int64_t n2 = n / 2;
+    const double2 *w2 = reinterpret_cast<const double2 *>(w);
+    const double2 *d2 = reinterpret_cast<const double2 *>(dinv);
+    double2 *v2 = reinterpret_cast<double2 *>(v);
+    double2 *z2 = reinterpret_cast<double2 *>(z);
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (; i < n2; i += stride) {
+        const double2 wv = w2[i];
+        double2 vv;
+        vv.x = wv.x / d;
+        vv.y = wv.y / d;
+        v2[i] = vv;
+        if (PRECOND) {
+            const double2 dv = d2[i];
+            double2 zv;
+            zv.x = dv.x * vv.x;
+            zv.y = dv.y * vv.y;
+            z2[i] = zv;
+        }
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t l = n - 1;
+        const double vl = w[l] / d;
+        v[l] = vl;
+        if (PRECOND) z[l] = dinv[l] * vl;
+    }
+}
+
+// cycle end: x = x + u or x + dinv .* u with u = y[0] V_0, u = u + y[i] V_i ascending.  state == NULL: the host's ungated finish
+template <bool NTX, bool PRECOND>
+__global__ __launch_bounds__(256) void gmres_xupdate_kernel(const double *__restrict__ V, int64_t ldv, int c,
+                                                            const double *__restrict__ y, const double *__restrict__ dinv,
+                                                            double *__restrict__ x, int64_t n, const int64_t *__restrict__ state)
+{
+    if (state && state[1] != PCG_RUNNING) return;
+    const int64_t n2 = n / 2, ld2 = ldv / 2;
+    const double2 *V2 = reinterpret_cast<const double2 *>(V);
+    const double2 *d2 = reinterpret_cast<const double2 *>(dinv);
+    double2 *x2 = reinterpret_cast<double2 *>(x);
+    const double y0 = y[0];
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (; i < n2; i += stride) {
+        double2 u = V2[i];
+        u.x = y0 * u.x;
+        u.y = y0 * u.y;
+#pragma unroll 4
+        for (int t = 1; t < c; ++t) {
+            const double yt = y[t];
+            const double2 vv = V2[(int64_t)t * ld2 + i];
+            u.x = u.x + yt * vv.x;
+            u.y = u.y + yt * vv.y;
+        }
+        if (PRECOND) {
+            const double2 dv = d2[i];
+            u.x = dv.x * u.x;
+            u.y = dv.y * u.y;
+        }
+        double2 xv = NTX ? nt_load2(x2 + i) : x2[i];
+        xv.x = xv.x + u.x;
+        xv.y = xv.y + u.y;
+        if (NTX) nt_store2(xv, x2 + i); else x2[i] = xv;
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t l = n - 1;
+        double u = y0 * V[l];
+        for (int t = 1; t < c; ++t) u = u + y[t] * V[(int64_t)t * ldv + l];
+        if (PRECOND) u = dinv[l] * u;
+        x[l] = x[l] + u;
+    }
+}
+
+// restart: w = b - w (w holds A x), partials of w.w
+__global__ __launch_bounds__(RT) void gmres_residual_kernel(const double *__restrict__ b, double *__restrict__ w, int64_t n,
+                                                            const int64_t *__restrict__ state, double *__restrict__ partial)
+{
+    if (state[1] != PCG_RUNNING) return;
+    const int64_t n2 = n / 2;
+    const double2 *b2 = reinterpret_cast<const double2 *>(b);
+    double2 *w2 = reinterpret_cast<double2 *>(w);
+    double acc = 0.0;
+    int64_t i = (int64_t)blockIdx.x * RT + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * RT;
+    for (; i < n2; i += stride) {
+        const double2 bv = b2[i];
+        double2 wv = w2[i];
+        wv.x = bv.x - wv.x;
+        wv.y = bv.y - wv.y;
+        w2[i] = wv;
+        acc = acc + wv.x * wv.x;
+        acc = acc + wv.y * wv.y;
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const double wj = b[n - 1] - w[n - 1];
+        w[n - 1] = wj;
+        acc = acc + wj * wj;
+    }
+    const double r = block_reduce<RED_SUM>(acc);
+    if (threadIdx.x == 0) partial[blockIdx.x] = r;
+}
+
+// second stage of the restart's w.w, one workgroup; gate R and the new cycle's g where no all-reduce follows (gate != 0)
+__global__ __launch_bounds__(RT) void gmres_residual_stage2_kernel(const double *__restrict__ partial, int np, GmresSmall q, int m,
+                                                                   double *__restrict__ hist_k, int64_t iter, int gate,
+                                                                   int64_t *__restrict__ state)
+{
+    if (state[1] != PCG_RUNNING) return;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < np; i += RT) acc = acc + partial[i];
+    const double rr = block_reduce<RED_SUM>(acc);
+    if (threadIdx.x == 0) {
+        q.nn[0] = rr;
+        if (gate) gmres_restart_gate(q, m, rr, hist_k, iter, state);
+    }
+}
+
+__global__ void gmres_restart_gate_kernel(GmresSmall q, int m, double *__restrict__ hist_k, int64_t iter,
+                                          int64_t *__restrict__ state)
+{
+    if (threadIdx.x == 0 && state[1] == PCG_RUNNING) gmres_restart_gate(q, m, q.nn[0], hist_k, iter, state);
+}
+
+// y = R^-1 g over c columns by back substitution, one thread.  state == NULL: the host's ungated finish
+__global__ void gmres_solve_kernel(GmresSmall q, int c, int m, const int64_t *__restrict__ state)
+{
+    if (threadIdx.x != 0 || (state && state[1] != PCG_RUNNING)) return;
+    for (int i = c - 1; i >= 0; --i) {
+        double t = q.g[i];
+        for (int l = i + 1; l < c; ++l) t = t - q.R[(int64_t)l * m + i] * q.y[l];
+        q.y[i] = t / q.R[(int64_t)i * m + i];
+    }
+}
+
 // MODE 0: y = y + a*x   MODE 1: y = x + a*y   MODE 2: y = a*x   MODE 3: y = x / a
 template <int MODE>
 __global__ __launch_bounds__(256) void update_kernel(double alpha, const double *__restrict__ num,
@@ -1252,6 +1607,194 @@ HPCLA_API int hpcla_bicg_p_f64(const double *rho_new_dev, const double *rho_dev,
                                                              nullptr, p, nullptr, n, state_dev);
     HPCLA_CHECK_LAUNCH();
     return HPCLA_OK;
+}
+
+// scratch of the gated GMRES steps: one array of stage-1 partials per column of the widest dots call (whole tiles), then the
+// solve's state (its last 32 bytes)
+HPCLA_API int64_t hpcla_gmres_work_bytes(int restart)
+{
+    if (restart < 1 || restart > GMRES_MAX_RESTART) return -1;
+    const int64_t cols = (int64_t)((restart + GMRES_TILE - 1) / GMRES_TILE) * GMRES_TILE;
+    return (cols * MAX_PARTIALS + PCG_STATE_WORDS) * (int64_t)sizeof(double);
+}
+
+// where the small arrays live in the solve's one buffer of doubles: which = 0 .. 9 for R, c, s, g, h1, h2, col, y, nn, hn;
+// which = 10: the buffer's length
+HPCLA_API int64_t hpcla_gmres_small_offset(int restart, int which)
+{
+    if (restart < 1 || restart > GMRES_MAX_RESTART || which < 0 || which > 10) return -1;
+    int64_t off[11];
+    gmres_small_offsets(restart, off);
+    return off[which];
+}
+
+static inline bool gmres_bad_basis(int64_t n, int64_t ldv, int ncols, int restart)
+{
+    return n < 0 || ldv < n || (ldv & 1) || ncols < 1 || restart < 1 || restart > GMRES_MAX_RESTART || ncols > restart;
+}
+
+HPCLA_API int hpcla_gmres_dots_f64(hpcla_comm_t *comm, const double *V, int64_t ldv, int ncols, const double *w, int64_t n,
+                                   const int64_t *state_dev, double *h_out_dev, void *work, void *stream)
+{
+    if (gmres_bad_basis(n, ldv, ncols, GMRES_MAX_RESTART))
+        return set_error(HPCLA_ERR_INVALID, "gmres_dots: negative size, odd or short pitch, or column count outside 1..64");
+    if (!state_dev || !h_out_dev || !work) return set_error(HPCLA_ERR_INVALID, "gmres_dots: null state / out / work");
+    if (n > 0 && (!V || !w)) return set_error(HPCLA_ERR_INVALID, "gmres_dots: null vector");
+    if (bicg_misaligned({V, w})) return set_error(HPCLA_ERR_INVALID, "gmres_dots: vectors must be 16-byte aligned");
+    double *partial = reinterpret_cast<double *>(work);
+    const int g = reduce_grid(n);
+    hipStream_t s = as_stream(stream);
+    for (int c0 = 0; c0 < ncols; c0 += GMRES_TILE) {
+        const double *Vt = V + (int64_t)c0 * ldv;
+        double *pt = partial + (int64_t)c0 * MAX_PARTIALS;
+#define HPCLA_GMRES_DOTS(T) case T: gmres_dots_kernel<T><<<g, RT, 0, s>>>(Vt, ldv, w, n, state_dev, pt); break
+        switch (ncols - c0 < GMRES_TILE ? ncols - c0 : GMRES_TILE) {
+            HPCLA_GMRES_DOTS(1);
+            HPCLA_GMRES_DOTS(2);
+            HPCLA_GMRES_DOTS(3);
+            HPCLA_GMRES_DOTS(4);
+            HPCLA_GMRES_DOTS(5);
+            HPCLA_GMRES_DOTS(6);
+            HPCLA_GMRES_DOTS(7);
+            HPCLA_GMRES_DOTS(8);
+        }
+#undef HPCLA_GMRES_DOTS
+        HPCLA_CHECK_LAUNCH();
+    }
+    static_assert(GMRES_TILE == 8, "the switch above covers tiles of 1 .. 8 columns");
+    gmres_dots_stage2_kernel<<<ncols, RT, 0, s>>>(partial, g, state_dev, h_out_dev);
+    HPCLA_CHECK_LAUNCH();
+    if (!comm) return HPCLA_OK;
+    for (int c0 = 0; c0 < ncols; c0 += AR_MAX) {                 // slices of AR_MAX: each takes the window path
+        const int rc = allreduce_on(comm, h_out_dev + c0, ncols - c0 < AR_MAX ? ncols - c0 : AR_MAX, 0, stream);
+        if (rc) return rc;
+    }
+    return HPCLA_OK;
+}
+
+// small_dev == NULL: the first pass, w only.  Else the second pass: also nn = w.w (one all-reduce), then the small step of
+// column j = ncols - 1 from small's h1, h2 and nn, with gates D and C; hist_k_dev receives g[j+1]^2
+HPCLA_API int hpcla_gmres_update_f64(hpcla_comm_t *comm, const double *V, int64_t ldv, int ncols, const double *h_dev, double *w,
+                                     int64_t n, int64_t iter, int restart, double *small_dev, double *hist_k_dev,
+                                     int64_t *state_dev, void *work, void *stream)
+{
+    if (gmres_bad_basis(n, ldv, ncols, small_dev ? restart : GMRES_MAX_RESTART) || iter < 1)
+        return set_error(HPCLA_ERR_INVALID, "gmres_update: negative size, odd or short pitch, bad column count or iteration < 1");
+    if (!h_dev || !state_dev || (small_dev && (!hist_k_dev || !work)))
+        return set_error(HPCLA_ERR_INVALID, "gmres_update: null coefficients / state / history / work");
+    if (n > 0 && (!V || !w)) return set_error(HPCLA_ERR_INVALID, "gmres_update: null vector");
+    if (bicg_misaligned({V, w})) return set_error(HPCLA_ERR_INVALID, "gmres_update: vectors must be 16-byte aligned");
+    double *partial = reinterpret_cast<double *>(work);
+    const int g = reduce_grid(n);
+    hipStream_t s = as_stream(stream);
+    if (!small_dev) {
+        gmres_update_kernel<false><<<g, RT, 0, s>>>(V, ldv, ncols, h_dev, w, n, state_dev, nullptr);
+        HPCLA_CHECK_LAUNCH();
+        return HPCLA_OK;
+    }
+    GmresSmall q;
+    gmres_small_layout(restart, small_dev, &q);
+    gmres_update_kernel<true><<<g, RT, 0, s>>>(V, ldv, ncols, h_dev, w, n, state_dev, partial);
+    HPCLA_CHECK_LAUNCH();
+    gmres_update_stage2_kernel<<<1, RT, 0, s>>>(partial, g, q, ncols - 1, restart, hist_k_dev, iter, comm ? 0 : 1, state_dev);
+    HPCLA_CHECK_LAUNCH();
+    if (!comm) return HPCLA_OK;
+    const int rc = allreduce_on(comm, q.nn, 1, 0, stream);
+    if (rc) return rc;
+    gmres_small_step_kernel<<<1, 64, 0, s>>>(q, ncols - 1, restart, hist_k_dev, iter, state_dev);
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
+HPCLA_API int hpcla_gmres_next_f64(const double *w, const double *hn_dev, const double *dinv, double *v_next, double *z,
+                                   int64_t n, const int64_t *state_dev, void *stream)
+{
+    if (n < 0) return set_error(HPCLA_ERR_INVALID, "gmres_next: negative size");
+    if (!hn_dev || !state_dev) return set_error(HPCLA_ERR_INVALID, "gmres_next: null scalar / state");
+    if (n == 0) return HPCLA_OK;
+    if (!w || !v_next || (dinv && !z)) return set_error(HPCLA_ERR_INVALID, "gmres_next: null vector");
+    if (bicg_misaligned({w, dinv, v_next, dinv ? z : nullptr}))
+        return set_error(HPCLA_ERR_INVALID, "gmres_next: vectors must be 16-byte aligned");
+    hipStream_t s = as_stream(stream);
+    if (dinv) gmres_next_kernel<true><<<ew_grid(n / 2), 256, 0, s>>>(w, hn_dev, dinv, v_next, z, n, state_dev);
+    else gmres_next_kernel<false><<<ew_grid(n / 2), 256, 0, s>>>(w, hn_dev, nullptr, v_next, nullptr, n, state_dev);
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
+// state_dev == NULL: ungated (the finish of an open cycle)
+HPCLA_API int hpcla_gmres_solve_f64(int ncols, int restart, double *small_dev, const int64_t *state_dev, void *stream)
+{
+    if (restart < 1 || restart > GMRES_MAX_RESTART || ncols < 1 || ncols > restart)
+        return set_error(HPCLA_ERR_INVALID, "gmres_solve: restart outside 1..64 or column count outside 1..restart");
+    if (!small_dev) return set_error(HPCLA_ERR_INVALID, "gmres_solve: null small arrays");
+    GmresSmall q;
+    gmres_small_layout(restart, small_dev, &q);
+    gmres_solve_kernel<<<1, 64, 0, as_stream(stream)>>>(q, ncols, restart, state_dev);
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
+HPCLA_API int hpcla_gmres_xupdate_f64(const double *V, int64_t ldv, int ncols, const double *y_dev, const double *dinv, double *x,
+                                      int64_t n, const int64_t *state_dev, void *stream)
+{
+    if (gmres_bad_basis(n, ldv, ncols, GMRES_MAX_RESTART))
+        return set_error(HPCLA_ERR_INVALID, "gmres_xupdate: negative size, odd or short pitch, or column count outside 1..64");
+    if (!y_dev) return set_error(HPCLA_ERR_INVALID, "gmres_xupdate: null coefficients");
+    if (n == 0) return HPCLA_OK;
+    if (!V || !x) return set_error(HPCLA_ERR_INVALID, "gmres_xupdate: null vector");
+    if (bicg_misaligned({V, dinv, x})) return set_error(HPCLA_ERR_INVALID, "gmres_xupdate: vectors must be 16-byte aligned");
+    hipStream_t s = as_stream(stream);
+    const uint32_t g = ew_grid(n / 2);
+#define HPCLA_GMRES_XUP(NX)                                                                                            \
+    do {                                                                                                               \
+        if (dinv) gmres_xupdate_kernel<NX, true><<<g, 256, 0, s>>>(V, ldv, ncols, y_dev, dinv, x, n, state_dev);       \
+        else gmres_xupdate_kernel<NX, false><<<g, 256, 0, s>>>(V, ldv, ncols, y_dev, nullptr, x, n, state_dev);        \
+    } while (0)
+    if (cg_nt_mask() & 1) HPCLA_GMRES_XUP(true);
+    else HPCLA_GMRES_XUP(false);
+#undef HPCLA_GMRES_XUP
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
+// w = b - w with rr = w.w (one all-reduce), gate R at iteration iter >= 0, else the new cycle's g = (sqrt(rr), 0, ...), hn
+HPCLA_API int hpcla_gmres_residual_f64(hpcla_comm_t *comm, const double *b, double *w, int64_t n, int64_t iter, int restart,
+                                       double *small_dev, double *hist_k_dev, int64_t *state_dev, void *work, void *stream)
+{
+    if (n < 0 || iter < 0 || restart < 1 || restart > GMRES_MAX_RESTART)
+        return set_error(HPCLA_ERR_INVALID, "gmres_residual: negative size or iteration, or restart outside 1..64");
+    if (!small_dev || !hist_k_dev || !state_dev || !work)
+        return set_error(HPCLA_ERR_INVALID, "gmres_residual: null small arrays / history / state / work");
+    if (n > 0 && (!b || !w)) return set_error(HPCLA_ERR_INVALID, "gmres_residual: null vector");
+    if (bicg_misaligned({b, w})) return set_error(HPCLA_ERR_INVALID, "gmres_residual: vectors must be 16-byte aligned");
+    GmresSmall q;
+    gmres_small_layout(restart, small_dev, &q);
+    double *partial = reinterpret_cast<double *>(work);
+    const int g = reduce_grid(n);
+    hipStream_t s = as_stream(stream);
+    gmres_residual_kernel<<<g, RT, 0, s>>>(b, w, n, state_dev, partial);
+    HPCLA_CHECK_LAUNCH();
+    gmres_residual_stage2_kernel<<<1, RT, 0, s>>>(partial, g, q, restart, hist_k_dev, iter, comm ? 0 : 1, state_dev);
+    HPCLA_CHECK_LAUNCH();
+    if (!comm) return HPCLA_OK;
+    const int rc = allreduce_on(comm, q.nn, 1, 0, stream);
+    if (rc) return rc;
+    gmres_restart_gate_kernel<<<1, 64, 0, s>>>(q, restart, hist_k_dev, iter, state_dev);
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
+// the host's finish of an open cycle of ncols columns, ungated: y = R^-1 g, then x = x + K (V y)
+HPCLA_API int hpcla_gmres_finish_f64(const double *V, int64_t ldv, int ncols, int restart, double *small_dev, const double *dinv,
+                                     double *x, int64_t n, void *stream)
+{
+    if (ncols == 0) return HPCLA_OK;
+    int rc = hpcla_gmres_solve_f64(ncols, restart, small_dev, nullptr, stream);
+    if (rc) return rc;
+    GmresSmall q;
+    gmres_small_layout(restart, small_dev, &q);
+    return hpcla_gmres_xupdate_f64(V, ldv, ncols, q.y, dinv, x, n, nullptr, stream);
 }
 
 // merge-combine: the five addition kernels of the reference (_copy_a_only_/_copy_b_only_/

@@ -1,0 +1,464 @@
+"""GPU tests of the restarted GMRES solver: the gated step kernels on their own through the C ABI, ``hp.gmres`` against the numpy
+restatement, independence of the chunk, a dirty workspace, convergence on the convection-diffusion cases, the exact cases,
+stagnation, argument errors and the solve across ranks.  Cases and the restatement: tests/_gmres_cases.py.
+
+Margins (none of them taken from the device's results; tests/test_gmres_cases.py re-measures the CPU figures and prints them):
+  * elements of w, V_{j+1}, z, x (and u inside it), the back substitution's y and the small step's c, s, R, g, hist: bit-equal
+    to numpy's separately rounded expressions (the library is built with -ffp-contract=off; IEEE divide and sqrt);
+  * every sum: 1e-12 of math.fsum relative to the sum of |terms| -- the terms of a dot are signed, so relative to the sum
+    itself would test cancellation and not the kernel; n <= 4.2e6 terms in a two-stage tree of doubles, worst case
+    n * 2^-53 = 4.7e-10, observed growth ~ sqrt(log n) ulps; 1e-12 is the project's margin for its reductions;
+  * histories: HIST_RTOL = 1e-12 (the project's history margin) on the first HEAD = 9 entries at restart = 5, so the head
+    crosses a restart: four summation orders on the CPU spread by <= 9.3e-16 there (1000 times less; the bound on that spread
+    is 1e-13) and by up to 6.2e-3 over a whole history, so only the head is compared;
+  * iteration counts: +-2 of the restatement's (identical across those orders at every size, restart and preconditioner), and
+    fewer with Jacobi than without at restart = 30 (56 / 228, 169 / 297, 262 / 344);
+  * true residual: <= 2 rtol (0.51 - 0.996 rtol across those orders: with the preconditioner on the right the Givens estimate
+    is the norm of the true residual);
+  * the history never rises by more than RISE_RTOL = 1e-12 relative (on the CPU it falls at every step).
+"""
+import math
+import os
+
+import numpy as np
+import pytest
+
+from tests import _bicgstab_cases as bc
+from tests import _gmres_cases as gc
+from tests import _pcg_cases as pc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WORKER = os.path.join(ROOT, "tests", "_multirank_gmres_worker.py")
+
+pytestmark = pytest.mark.gpu
+
+RUNNING, CONVERGED, BREAKDOWN, AT_RESTART = 0, 1, 2, 3
+M_ALONE = 32               # the restart the kernels-alone tests size their small arrays and scratch for (c <= 31)
+SMALL = ("R", "c", "s", "g", "h1", "h2", "col", "y", "nn", "hn")
+
+
+def _matrix(hp, backend, rowptr, colidx, vals, n):
+    return hp.HPCSparseMatrix_local(rowptr, colidx, vals, n, backend)
+
+
+@pytest.fixture(scope="module")
+def cases(orc):
+    """The three convection-diffusion cases with the restatement's results, computed once."""
+    out = {}
+    for nx, ny in gc.SIZES:
+        rowptr, colidx, vals, b = bc.convection_diffusion(orc, nx, ny)
+        d = pc.host_diag(rowptr, colidx, vals)
+        ref = {(name, m): gc.gmres(rowptr, colidx, vals, b, dinv=dinv, rtol=1e-8, restart=m)
+               for name, dinv in (("jacobi", 1.0 / d), ("none", None)) for m in gc.RESTARTS}
+        out[(nx, ny)] = dict(rowptr=rowptr, colidx=colidx, vals=vals, b=b, d=d, ref=ref)
+    return out
+
+
+# ---- 1. the kernels on their own ----------------------------------------------------------------------------------------
+def _sum_err(got, terms):
+    return abs(got - math.fsum(terms.tolist())) / float(np.abs(terms).sum())
+
+
+class _Alone:
+    """Device buffers and the C entries for one (n, c): the basis at an even pitch, the small arrays of restart M_ALONE."""
+
+    def __init__(self, hp, n, c):
+        import torch
+        self.torch, self.lib, self.n, self.c, self.m = torch, hp._capi.load(), n, c, M_ALONE
+        self.f64 = dict(dtype=torch.float64, device="cuda")
+        self.ldv = n + (n & 1)
+        self.off = [self.lib.hpcla_gmres_small_offset(self.m, k) for k in range(11)]
+        self.work = torch.zeros(self.lib.hpcla_gmres_work_bytes(self.m) // 8, **self.f64)
+
+    def dev(self, arr):
+        return self.torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float64)).cuda()
+
+    def basis(self, V_h):
+        """(c + 1) x n host rows -> one device buffer at pitch ldv, the pad (odd n) poisoned with NaN: no kernel may read it."""
+        buf = np.full((V_h.shape[0], self.ldv), np.nan)
+        buf[:, :self.n] = V_h
+        return self.dev(buf.reshape(-1))
+
+    def small(self, **arrays):
+        s = np.zeros(self.off[10])
+        for name, a in arrays.items():
+            k = SMALL.index(name)
+            a = np.asarray(a, dtype=np.float64)
+            s[self.off[k]:self.off[k] + a.size] = a.T.reshape(-1) if name == "R" else a.reshape(-1)   # column j at R + j m
+        return self.dev(s)
+
+    def view(self, small, name):
+        k = SMALL.index(name)
+        a = small[self.off[k]:self.off[k + 1]].cpu().numpy()
+        return a.reshape(self.m, self.m).T.copy() if name == "R" else a
+
+    def state(self, thr=0.0, done=0, status=RUNNING):
+        return self.torch.tensor([done, status, np.float64(thr).view(np.int64), 0], dtype=self.torch.int64, device="cuda")
+
+    @staticmethod
+    def P(t):
+        return t.data_ptr() if t is not None else None
+
+    def dots(self, V, ncols, w, st, out):
+        assert self.lib.hpcla_gmres_dots_f64(None, self.P(V), self.ldv, ncols, self.P(w), self.n, self.P(st), self.P(out),
+                                             self.P(self.work), None) == 0
+
+    def update(self, V, h, w, st, it=1, small=None, hist=None):
+        assert self.lib.hpcla_gmres_update_f64(None, self.P(V), self.ldv, self.c, self.P(h), self.P(w), self.n, it, self.m,
+                                               self.P(small), self.P(hist), self.P(st), self.P(self.work), None) == 0
+
+    def next(self, w, hn, dinv, v, z, st):
+        assert self.lib.hpcla_gmres_next_f64(self.P(w), self.P(hn), self.P(dinv), self.P(v), self.P(z), self.n, self.P(st),
+                                             None) == 0
+
+    def solve(self, small, st):
+        assert self.lib.hpcla_gmres_solve_f64(self.c, self.m, self.P(small), self.P(st), None) == 0
+
+    def xupdate(self, V, y, dinv, x, st):
+        assert self.lib.hpcla_gmres_xupdate_f64(self.P(V), self.ldv, self.c, self.P(y), self.P(dinv), self.P(x), self.n,
+                                                self.P(st), None) == 0
+
+    def residual(self, b, w, it, small, hist, st):
+        assert self.lib.hpcla_gmres_residual_f64(None, self.P(b), self.P(w), self.n, it, self.m, self.P(small), self.P(hist),
+                                                 self.P(st), self.P(self.work), None) == 0
+
+
+def _bits_eq(t, want):
+    got = t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+    return np.array_equal(pc.bits(got), pc.bits(want))
+
+
+def _rotations(rng, j):
+    theta = rng.uniform(0.1, 3.0, j)
+    return np.cos(theta), np.sin(theta)
+
+
+SIZES_ALONE = [(n, c) for n in (1, 2, 511, 515, 2049, 2051) for c in (1, 2, 8, 9, 16, 17, 31)] + [(4194307, 1), (4194307, 9)]
+
+
+@pytest.mark.parametrize("n,c", SIZES_ALONE)
+def test_gated_kernels_alone(hp, n, c):
+    """The reductions (gmres_dots, the second gmres_update, gmres_residual) use the grid of the existing stage-1 reductions,
+    ceil(floor(n / 2) / 1024) capped at 2048: 2049 is the last size on one workgroup with a scalar tail, 2051 the first odd size
+    on two, 4 194 307 = 2 * 256 * 4 * 2048 + 3 caps the grid and is odd.  The elementwise kernels (gmres_next, gmres_xupdate)
+    use ceil(floor(n / 2) / 256) capped at 4096: 511 is the last odd size on one workgroup, 515 the first on two.  c = 8 | 9 and
+    16 | 17 are the edges of the tiles of 8 sums, c = 31 is four tiles with a last one of 7; an odd n makes the pitch n + 1."""
+    import torch
+    K = _Alone(hp, n, c)
+    rng = np.random.default_rng(1000 * c + n % 1000)
+    j, it = c - 1, 7
+    V_h = rng.uniform(-1.0, 1.0, (c + 1, n))
+    w_h, x_h, b_h = (rng.uniform(-1.0, 1.0, n) for _ in range(3))
+    dinv_h = rng.uniform(0.5, 2.0, n) * rng.choice([-1.0, 1.0], n)
+    h1_h, h2_h, y_h = rng.uniform(-1.0, 1.0, c), 1e-3 * rng.uniform(-1.0, 1.0, c), rng.uniform(-1.0, 1.0, c)
+    hn_h = 0.7310585786300049
+    cs_h, sn_h = _rotations(rng, j)
+    R_h = np.triu(rng.uniform(-1.0, 1.0, (K.m, K.m))) + np.diag(rng.uniform(1.0, 2.0, K.m) * rng.choice([-1.0, 1.0], K.m))
+    g_h = np.concatenate([rng.uniform(-1.0, 1.0, c), np.zeros(K.m + 1 - c)])
+    pad = lambda a, k=K.m: np.concatenate([a, np.zeros(k - len(a))])
+    V, dinv, ones = K.basis(V_h), K.dev(dinv_h), torch.ones(n, **K.f64)
+    big = n > 100000                                             # the large size: fsum only where the tiles differ
+    checked = sorted({0, 7, 8} & set(range(c))) if big else range(c)
+
+    # -- dots, first pass, second pass with the small step, next: every step from hand-set scalars, state running
+    st = K.state()
+    small = K.small(R=R_h, c=pad(cs_h), s=pad(sn_h), g=g_h, h1=pad(h1_h), h2=pad(h2_h))
+    h1, h2 = small[K.off[4]:K.off[4] + c], small[K.off[5]:K.off[5] + c]
+    hist = torch.full((2,), 7.0, **K.f64)
+    h_out, w = torch.full((c + 1,), 7.0, **K.f64), K.dev(w_h)
+    K.dots(V, c, w, st, h_out)
+    K.update(V, h1, w, st, it)
+    w1_h = gc.subtract_columns(w_h, V_h, h1_h)
+    torch.cuda.synchronize()
+    assert _bits_eq(w, w1_h) and h_out[c].item() == 7.0
+    errs = {f"V{i}.w": _sum_err(h_out[i].item(), V_h[i] * w_h) for i in checked}
+    K.update(V, h2, w, st, it, small=small, hist=hist)
+    w2_h = gc.subtract_columns(w1_h, V_h, h2_h)
+    torch.cuda.synchronize()
+    assert _bits_eq(w, w2_h)
+    nn = K.view(small, "nn")[0]
+    errs["w.w"] = _sum_err(nn, w2_h * w2_h)
+    cs_r, sn_r, R_r, g_r = pad(cs_h), pad(sn_h), R_h.copy(), g_h.copy()
+    status, e = gc.small_step(j, h1_h, h2_h, nn, cs_r, sn_r, R_r, g_r, 0.0)
+    assert status == "running" and st.cpu().tolist()[:2] == [0, RUNNING]
+    assert _bits_eq(K.view(small, "c"), cs_r) and _bits_eq(K.view(small, "s"), sn_r) and _bits_eq(K.view(small, "g"), g_r)
+    assert _bits_eq(K.view(small, "R"), R_r) and _bits_eq(hist, [e, 7.0])
+    assert _bits_eq(K.view(small, "hn"), [math.sqrt(nn)])
+    hn = K.dev([hn_h])
+    vn, z = V[c * K.ldv:c * K.ldv + n], torch.full((n,), 7.0, **K.f64)
+    K.next(w, hn, dinv, vn, z, st)
+    torch.cuda.synchronize()
+    assert _bits_eq(vn, w2_h / hn_h) and _bits_eq(z, dinv_h * (w2_h / hn_h))
+    if n & 1:
+        assert bool(torch.isnan(V.view(c + 1, K.ldv)[:, n]).all())                       # the pad is never written
+
+    # -- solve and xupdate from hand-set R, g and y; residual and the start of a cycle
+    small2 = K.small(R=R_h, g=g_h)
+    K.solve(small2, st)
+    torch.cuda.synchronize()
+    assert _bits_eq(K.view(small2, "y")[:c], gc.back_substitution(c, R_h, g_h))
+    y, x = K.dev(y_h), K.dev(x_h)
+    K.xupdate(V, y, dinv, x, st)
+    torch.cuda.synchronize()
+    u_h = gc.basis_combination(V_h[:c], y_h)
+    assert _bits_eq(x, x_h + dinv_h * u_h)
+    wr, hist0 = K.dev(w_h), torch.full((2,), 7.0, **K.f64)
+    K.residual(K.dev(b_h), wr, 0, small2, hist0, st)
+    torch.cuda.synchronize()
+    r_h = b_h - w_h
+    rr = K.view(small2, "nn")[0]
+    errs["r.r"] = _sum_err(rr, r_h * r_h)
+    assert _bits_eq(wr, r_h) and _bits_eq(hist0, [rr, 7.0]) and st.cpu().tolist()[:2] == [0, RUNNING]
+    assert _bits_eq(K.view(small2, "g"), pad([math.sqrt(rr)], K.m + 1)) and _bits_eq(K.view(small2, "hn"), [math.sqrt(rr)])
+    print(f"n = {n}, c = {c}: " + ", ".join(f"{k} {v:.2e}" for k, v in errs.items()))
+    assert all(v <= 1e-12 for v in errs.values()), errs
+
+    # -- dinv = NULL and dinv = 1: the same bits
+    runs = []
+    for d_ in (None, ones):
+        v1, z1, x1 = torch.full((n,), 7.0, **K.f64), (torch.full((n,), 7.0, **K.f64) if d_ is not None else None), K.dev(x_h)
+        K.next(w, hn, d_, v1, z1, st)
+        K.xupdate(V, y, d_, x1, st)
+        torch.cuda.synchronize()
+        if d_ is not None:
+            assert torch.equal(z1.view(torch.int64), v1.view(torch.int64))
+        runs.append((v1, x1))
+    assert all(torch.equal(a.view(torch.int64), b_.view(torch.int64)) for a, b_ in zip(*runs))
+    assert _bits_eq(runs[0][1], x_h + u_h)
+
+    if big:
+        return
+    # -- gates: D (a zero column, a NaN column) stores nothing of column j; C and R set (done_iter, status)
+    for h1_bad, w_bad in ((np.zeros(c), np.zeros(n)), (np.full(c, np.nan), w_h)):
+        std = K.state()
+        sm = K.small(R=R_h, c=pad(cs_h), s=pad(sn_h), g=g_h, h1=pad(h1_bad), h2=np.zeros(K.m))
+        before = {k: K.view(sm, k).copy() for k in ("R", "c", "s", "g")}
+        histd = torch.full((2,), 7.0, **K.f64)
+        K.update(V, sm[K.off[5]:K.off[5] + c], K.dev(w_bad), std, it, small=sm, hist=histd)
+        torch.cuda.synchronize()
+        assert std.cpu().tolist()[:2] == [it - 1, BREAKDOWN]
+        assert all(_bits_eq(K.view(sm, k), before[k]) for k in before) and _bits_eq(histd, [7.0, 7.0])
+    stc = K.state(thr=4.0)                                       # |g[j+1]| <= |g[j]| < 1
+    K.update(V, h2, K.dev(w_h), stc, it, small=K.small(g=g_h, c=pad(cs_h), s=pad(sn_h), h1=pad(h1_h), h2=pad(h2_h)), hist=hist)
+    str_ = K.state(thr=4.0 * n)                                  # |b - w| < 2 elementwise
+    histr, smr = torch.full((2,), 7.0, **K.f64), K.small(g=g_h)
+    K.residual(K.dev(b_h), K.dev(w_h), it, smr, histr, str_)
+    torch.cuda.synchronize()
+    assert stc.cpu().tolist()[:2] == [it, CONVERGED] and str_.cpu().tolist()[:2] == [it, AT_RESTART]
+    assert _bits_eq(histr, [K.view(smr, "nn")[0], 7.0]) and _bits_eq(K.view(smr, "g"), g_h)   # g is not restarted behind gate R
+
+    # -- frozen: no kernel writes a byte
+    for frozen in ([it - 1, CONVERGED], [it, CONVERGED], [it - 1, BREAKDOWN], [it, AT_RESTART]):
+        stf = K.state(done=frozen[0], status=frozen[1])
+        smf = K.small(R=R_h, g=g_h, h1=pad(h1_h), h2=pad(h2_h))
+        smf0 = smf.clone()
+        Vf, outs = V.clone(), [torch.full((k,), 7.0, **K.f64) for k in (c, 2)]
+        vecs = [torch.full((n,), 7.0, **K.f64) for _ in range(5)]                        # w, w, z, x, w
+        K.dots(Vf, c, vecs[0], stf, outs[0])
+        K.update(Vf, h1, vecs[0], stf, it)
+        K.update(Vf, h2, vecs[1], stf, it, small=smf, hist=outs[1])
+        K.next(vecs[0], hn, dinv, Vf[c * K.ldv:c * K.ldv + n], vecs[2], stf)
+        K.solve(smf, stf)
+        K.xupdate(Vf, y, dinv, vecs[3], stf)
+        K.residual(K.dev(b_h), vecs[4], it, smf, outs[1], stf)
+        torch.cuda.synchronize()
+        assert all(bool((o == 7.0).all()) for o in outs + vecs), frozen
+        assert torch.equal(smf.view(torch.int64), smf0.view(torch.int64)) and torch.equal(Vf.view(torch.int64), V.view(torch.int64))
+        assert stf.cpu().tolist()[:2] == frozen
+
+
+@pytest.mark.parametrize("n", [515, 2051])
+def test_a_columns_sum_has_the_same_bits_whatever_rides_along(hp, n):
+    """Column i's sum at c = 3 (one tile of 3) and c = 9 (a tile of 8 and a tile of 1; column 8 sits alone in the second)."""
+    import torch
+    rng = np.random.default_rng(n)
+    K = _Alone(hp, n, 9)
+    V, w, st = K.basis(rng.uniform(-1.0, 1.0, (9, n))), K.dev(rng.uniform(-1.0, 1.0, n)), K.state()
+    out = {}
+    for c in (1, 3, 9):
+        out[c] = torch.zeros(c, **K.f64)
+        K.dots(V, c, w, st, out[c])
+    last = torch.zeros(1, **K.f64)
+    K.dots(V[8 * K.ldv:], 1, w, st, last)                        # column 8 as the only column of a call
+    torch.cuda.synchronize()
+    assert _bits_eq(out[9][:3], out[3].cpu().numpy()) and _bits_eq(out[9][:1], out[1].cpu().numpy())
+    assert _bits_eq(out[9][8:], last.cpu().numpy())
+
+
+# ---- 2. the head of the history against the restatement -------------------------------------------------------------------
+@pytest.mark.parametrize("which", ["i32", "i64", "i64wide"])
+def test_history_head_matches_the_restatement(hp, cases, gpu_backend_i32, gpu_backend_i64, which, monkeypatch):
+    """First HEAD = 9 entries within HIST_RTOL = 1e-12 at restart = 5, so the head crosses a restart (entry 5 is the last of a
+    cycle, entry 6 the first of the next): 1000 times the spread of four summation orders on the CPU (9.3e-16,
+    tests/test_gmres_cases.py prints it and bounds it by 1e-13)."""
+    monkeypatch.setenv("HPCLA_NARROW_INDICES", "0" if which == "i64wide" else "1")
+    backend = gpu_backend_i32 if which == "i32" else gpu_backend_i64
+    c = cases[(24, 20)]
+    n, its = len(c["b"]), gc.HEAD + 3
+    A = _matrix(hp, backend, c["rowptr"], c["colidx"], c["vals"], n)
+    b = hp.HPCVector.from_global(c["b"], backend)
+    for name, M, dinv in (("jacobi", "jacobi", 1.0 / c["d"]), ("none", None, None)):
+        _, its_ref, status_ref, h_ref = gc.gmres(c["rowptr"], c["colidx"], c["vals"], c["b"], dinv=dinv, rtol=0.0, atol=0.0,
+                                                 restart=gc.HEAD_RESTART, maxiter=its)
+        assert (its_ref, status_ref, len(h_ref)) == (its, "maxiter", its + 1)
+        x, info = hp.gmres(A, b, rtol=0.0, atol=0.0, restart=gc.HEAD_RESTART, maxiter=its, M=M, check_every=8)
+        assert (info.iterations, info.status, info.converged) == (its, "maxiter", False)
+        assert len(info.residual_norms) == its + 1
+        head = max(abs(g - w_) / w_ for g, w_ in zip(info.residual_norms[:gc.HEAD], h_ref[:gc.HEAD]))
+        print(f"{which} {name}: head deviation {head:.2e}")
+        assert head <= gc.HIST_RTOL, (name, head)
+    hp.clear_plan_cache()
+
+
+# ---- 3. the chunk -----------------------------------------------------------------------------------------------------------
+def test_answer_does_not_depend_on_the_chunk(hp, cases, gpu_backend_i32):
+    """restart = 5 on 24 x 20: chunks of 1, 3, 8 and 64 end before, on and after cycle ends.  Without a preconditioner the solve
+    converges (488 steps in the restatement); with Jacobi GMRES(5) stagnates on this case, which gives the maxiter end with an
+    open cycle (23 = 4 * 5 + 3)."""
+    c = cases[(24, 20)]
+    A = _matrix(hp, gpu_backend_i32, c["rowptr"], c["colidx"], c["vals"], len(c["b"]))
+    b = hp.HPCVector.from_global(c["b"], gpu_backend_i32)
+    for kw, status in ((dict(M=None, rtol=1e-8), "converged"), (dict(M="jacobi", rtol=1e-8, maxiter=23), "maxiter")):
+        runs = []
+        for chunk in (1, 3, 8, 64):
+            x, info = hp.gmres(A, b, restart=5, check_every=chunk, **kw)
+            assert info.status == status
+            runs.append((info.iterations, pc.bits(x.local_values()).copy(), pc.bits(info.residual_norms).copy()))
+        for its, xb, hb in runs[1:]:
+            assert its == runs[0][0] and np.array_equal(xb, runs[0][1]) and np.array_equal(hb, runs[0][2])
+    hp.clear_plan_cache()
+
+
+# ---- 4. a dirty workspace ---------------------------------------------------------------------------------------------------
+def test_a_dirty_workspace_gives_a_fresh_ones_bits(hp, cases, gpu_backend_i32):
+    c = cases[(16, 16)]
+    A = _matrix(hp, gpu_backend_i32, c["rowptr"], c["colidx"], c["vals"], len(c["b"]))
+    b = hp.HPCVector.from_global(c["b"], gpu_backend_i32)
+    x, info = hp.gmres(A, b, M="jacobi", restart=8)
+    xv = x.local_values().copy()
+    ws = hp.GMRESWorkspace(b, restart=8)
+    other = hp.HPCVector.from_global(c["b"][::-1].copy(), gpu_backend_i32)
+    hp.gmres(A, other, M=None, rtol=0.0, maxiter=13, restart=8, workspace=ws)           # a different solve, left mid-cycle
+    x2, info2 = hp.gmres(A, b, M="jacobi", restart=8, workspace=ws)
+    assert x2 is ws.x and info2 == info and np.array_equal(pc.bits(x2.local_values()), pc.bits(xv))
+    x3, info3 = hp.gmres(A, b, M="jacobi", restart=8, workspace=ws)                     # and on its own leftovers
+    assert info3 == info and np.array_equal(pc.bits(x3.local_values()), pc.bits(xv))
+    x4, _ = hp.gmres(A, b, M="jacobi", restart=30, workspace=ws)                        # another restart: a workspace of its own
+    assert x4 is not ws.x
+    hp.clear_plan_cache()
+
+
+# ---- 5. convergence ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("size", gc.SIZES)
+def test_convergence_on_the_convection_diffusion_cases(hp, cases, gpu_backend_i32, size):
+    c = cases[size]
+    n = len(c["b"])
+    A = _matrix(hp, gpu_backend_i32, c["rowptr"], c["colidx"], c["vals"], n)
+    b = hp.HPCVector.from_global(c["b"], gpu_backend_i32)
+    bnorm = hp.norm(b)
+    its = {}
+    for m in gc.RESTARTS:
+        for name, M in (("jacobi", "jacobi"), ("none", None)):
+            _, its_ref, status_ref, _ = c["ref"][name, m]
+            x, info = hp.gmres(A, b, rtol=1e-8, restart=m, M=M)
+            true = hp.norm(b - A @ x) / bnorm
+            h = np.array(info.residual_norms)
+            rise = float(np.max((h[1:] - h[:-1]) / h[:-1]))
+            print(f"{size} {name} restart {m}: iterations {info.iterations} (restatement {its_ref}), true residual {true:.3e}, "
+                  f"largest relative rise {rise:.2e}")
+            assert info.converged and info.status == "converged" and status_ref == "converged"
+            assert len(info.residual_norms) == info.iterations + 1
+            assert true <= 2e-8
+            assert abs(info.iterations - its_ref) <= 2
+            assert rise <= gc.RISE_RTOL
+            its[name, m] = info.iterations
+    assert its["jacobi", 30] < its["none", 30], its
+    x0 = hp.HPCVector.from_global(np.full(n, 1e-3), gpu_backend_i32)
+    x, info = hp.gmres(A, b, x0=x0, rtol=1e-8, M="jacobi")
+    assert info.converged and hp.norm(b - A @ x) / bnorm <= 2e-8
+    hp.clear_plan_cache()
+
+
+# ---- 6. the exact cases -----------------------------------------------------------------------------------------------------
+def test_exact_cases(hp, orc, gpu_backend_i32):
+    B = gpu_backend_i32
+    vec = lambda a: hp.HPCVector.from_global(np.asarray(a, dtype=np.float64), B)
+    # restart >= n: -I in one step, ROT in two, where hp.bicgstab reports a breakdown
+    bi = orc.fill_uniform(0, 5, pc.SEED_RHS)
+    x, info = hp.gmres(_matrix(hp, B, *pc.diag_matrix(-np.ones(5)), 5), vec(bi))
+    assert (info.converged, info.iterations, info.status, len(info.residual_norms)) == (True, 1, "converged", 2)
+    assert info.residual_norms[1] == 0.0 and np.allclose(x.local_values(), -bi, rtol=1e-14, atol=0)
+    Arot = _matrix(hp, B, *gc.ROT, 2)
+    assert hp.bicgstab(Arot, vec(gc.ROT_B))[1].status == "breakdown"
+    x, info = hp.gmres(Arot, vec(gc.ROT_B))
+    assert (info.converged, info.iterations, info.status) == (True, 2, "converged")
+    assert np.allclose(x.local_values(), [0.0, 1.0], rtol=1e-14, atol=1e-14) and len(info.residual_norms) == 3
+    # ZERO and NILP: exact breakdowns with the restatement's iterations, history and a finite x
+    for mat, bg in ((gc.ZERO, gc.ZERO_B), (gc.NILP, gc.NILP_B)):
+        x_ref, its_ref, status_ref, h_ref = gc.gmres(*mat, bg)
+        assert status_ref == "breakdown"
+        x, info = hp.gmres(_matrix(hp, B, *mat, 2), vec(bg))
+        assert (info.converged, info.iterations, info.status) == (False, its_ref, "breakdown")
+        assert len(info.residual_norms) == len(h_ref) == its_ref + 1
+        xv = x.local_values()
+        assert np.all(np.isfinite(xv)) and np.array_equal(xv, x_ref)
+        assert np.allclose(info.residual_norms, h_ref, rtol=1e-14, atol=0)
+    # the diagonal case under Jacobi: one step, within the stop rule
+    rowptr, colidx, d, bg = pc.diagonal_case(orc)
+    b = vec(bg)
+    x, info = hp.gmres(_matrix(hp, B, rowptr, colidx, d, len(bg)), b, M="jacobi", rtol=1e-8, maxiter=50)
+    assert (info.converged, info.iterations, info.status, len(info.residual_norms)) == (True, 1, "converged", 2)
+    assert info.residual_norms[1] <= 1e-8 * hp.norm(b)
+    xv = x.local_values()
+    assert np.all(np.isfinite(xv)) and np.all(np.abs(xv - bg / d) <= 4 * np.spacing(np.abs(bg / d)))
+    # b = 0: x = 0 without an iteration
+    x, info = hp.gmres(_matrix(hp, B, *pc.diag_matrix(np.ones(5)), 5), vec(np.zeros(5)))
+    assert (info.converged, info.iterations, info.status, info.residual_norms) == (True, 0, "converged", [0.0])
+    assert not x.local_values().any()
+
+
+# ---- 7. stagnation ------------------------------------------------------------------------------------------------------------
+def test_a_short_restart_stagnates_to_maxiter(hp, cases, gpu_backend_i32):
+    c = cases[(16, 16)]
+    A = _matrix(hp, gpu_backend_i32, c["rowptr"], c["colidx"], c["vals"], len(c["b"]))
+    b = hp.HPCVector.from_global(c["b"], gpu_backend_i32)
+    x, info = hp.gmres(A, b, M="jacobi", restart=1, maxiter=40)
+    assert (info.converged, info.iterations, info.status, len(info.residual_norms)) == (False, 40, "maxiter", 41)
+    assert np.all(np.isfinite(x.local_values())) and np.all(np.isfinite(info.residual_norms))
+    hp.clear_plan_cache()
+
+
+# ---- 8. argument errors -------------------------------------------------------------------------------------------------------
+def test_gmres_argument_errors(hp, cases, gpu_backend_i32):
+    c = cases[(16, 16)]
+    n = len(c["b"])
+    A = _matrix(hp, gpu_backend_i32, c["rowptr"], c["colidx"], c["vals"], n)
+    b = hp.HPCVector.from_global(c["b"], gpu_backend_i32)
+    for bad in (dict(restart=0), dict(restart=65), dict(M="ilu"), dict(check_every=0)):
+        with pytest.raises(ValueError):
+            hp.gmres(A, b, **bad)
+    with pytest.raises(ValueError):
+        hp.GMRESWorkspace(b, restart=65)
+    rect = hp.HPCSparseMatrix_local(c["rowptr"], c["colidx"], c["vals"], n + 7, gpu_backend_i32)
+    with pytest.raises(ValueError):
+        hp.gmres(rect, b)
+    d0 = np.ones(n)
+    d0[n // 2] = 0.0
+    with pytest.raises(ValueError):
+        hp.gmres(_matrix(hp, gpu_backend_i32, *pc.diag_matrix(d0), n), b, M="jacobi")     # minimum(abs(diag)) > 0 is required
+    with pytest.raises(ValueError):                                                      # b on another partition
+        hp.gmres(A, hp.HPCVector.from_global(np.ones(n + 2), gpu_backend_i32))
+    b32 = hp.backend_rocm_serial(np.float32, np.int32)
+    A32 = hp.HPCSparseMatrix_local(c["rowptr"], c["colidx"], c["vals"].astype(np.float32), n, b32)
+    with pytest.raises(TypeError):
+        hp.gmres(A32, hp.HPCVector.from_global(c["b"], b32))
+
+
+# ---- 9. ranks -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("nranks", [2, 3])
+def test_gmres_across_ranks(nranks):
+    """The ranks share the one GPU (peer-window push transport, like tests/test_gpu_multirank.py); checks in the worker."""
+    from hpcla_amd.launch import spawn_ranks
+    env = {"HPCLA_PUSH_TIMEOUT_S": "30"}
+    os.environ.pop("HPCLA_HALO_MODE", None)
+    assert spawn_ranks([WORKER], nranks, env_extra=env, timeout=120, forward_rank0_stdout=False) == 0
