@@ -1032,6 +1032,73 @@ int hpcla_bicgstab_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *com
                                       double *r, const double *rhat, double *p, double *ph, double *v, double *s,
                                       double *sh, double *t, double *hist_dev, double *scal_dev, void *work,
                                       int64_t first_iter, int iters, void *stream);
+/* ---- LSQR for a rectangular A (m x n): min |A x - b|^2 + damp^2 |x|^2 by Golub-Kahan bidiagonalisation on A and its
+ * materialised transpose At (no reference counterpart: A \ b goes through MUMPS on the host and needs a square A; a caller of
+ * the reference's operators composes the method from A*v, src/sparse.jl:2096-2128, transpose(A)*u, src/sparse.jl:2136-2142,
+ * norm, src/vectors.jl:758-780, and the broadcasts, src/vectors.jl:1203-1226: two normalisation passes and four host
+ * read-backs per iteration).  No vector is normalised in memory: uh and vh are kept unnormalised next to their norms beta
+ * and alpha, and the scalings ride in the passes below.
+ * The state is the CG solver's (done_iter, status, thr, ntol2) with one more status and the fourth word in use:
+ *   3 least squares (|Abar' rbar|^2 <= ntol2 * anorm2 * |rbar|^2 at done_iter); thr = max(rtol |b|, atol)^2, ntol2 = ntol^2.
+ * scal_dev: 24 doubles.  Slots: 0 alpha, 1 beta, 2 uu (= uh.uh, all-reduced), 3 vv (= vh.vh, all-reduced), 4 phibar,
+ * 5 rhobar, 6 res2, 7 anorm2, 8 t1, 9 t2, 10 rho, 11 c, 12 s, 13 theta, 14 phi, 15 rn2, 16 arn, 17 damp (the caller's, never
+ * written), 18 .. 23 reserved.  Before the first iteration: alpha, beta, phibar = beta, rhobar = alpha, damp; the rest 0.
+ * Iteration `iter` is 1-based over the whole solve; every entry is a no-op writing no byte once status != 0 (lsqr_xw runs
+ * once more, x only, when status is 1 or 3 and done_iter == iter).  Each sum is all-reduced once (comm != NULL):
+ *   lsqr_u   (scale, axpy, norm)  uh = tu / alpha - (alpha / beta) * uh;  uu = uh.uh.  No gate.
+ *   lsqr_v   (scale, axpy, norm)  beta' = sqrt(uu);  vh = tv / beta' - (beta' / alpha) * vh;  vv = vh.vh.  Gate U: uu == 0:
+ *                                 vh is not written and vv = 0.  Then, pair_out_dev != NULL, the step by one thread, behind
+ *                                 the all-reduce, with alpha' = sqrt(vv):
+ *                                   anorm2 += (alpha^2 + beta'^2) + damp^2
+ *                                   rhobar1 = sqrt(rhobar^2 + damp^2);  psi = (damp / rhobar1) * phibar
+ *                                   phibar = (rhobar / rhobar1) * phibar;  res2 += psi^2
+ *                                   rho = sqrt(rhobar1^2 + beta'^2);  c = rhobar1 / rho;  s = beta' / rho
+ *                                   theta = s * alpha';  rhobar = -c * alpha';  phi = c * phibar;  phibar = s * phibar
+ *                                   t1 = phi / rho;  t2 = theta / rho;  rn2 = phibar^2 + res2;  arn = alpha' * |s * phi|
+ *                                   pair_out_dev = (rn2, arn^2);  alpha = alpha';  beta = beta'
+ *                                 and its gates, in this order:
+ *                                   rn2 or arn not finite:              status = 2, done_iter = iter - 1
+ *                                   rn2 <= thr:                         status = 1, done_iter = iter
+ *                                   arn^2 <= (ntol2 * anorm2) * rn2:    status = 3, done_iter = iter
+ *                                 pair_out_dev == NULL: no step, no gate (the setup's vh = tv / beta from vh = 0, alpha = 1).
+ *   lsqr_xw  (two axpys, scale)   x = x + t1 * w;  w = vh / alpha - t2 * w (alpha is the step's alpha').  In the iteration
+ *                                 that stopped only x = x + t1 * w.  After a breakdown x keeps its value of iter - 1.
+ * Separate divide, multiply and subtract, in the order written.  tu and tv (HPCLA_CG_NT bit 2) and x (bit 0) go
+ * non-temporally.  work: hpcla_lsqr_work_bytes() bytes -- one array of partials, then the 32 bytes the iterations entry
+ * uses as the state.  Vectors 16-byte aligned. */
+int64_t hpcla_lsqr_work_bytes(void);
+int hpcla_lsqr_u_f64(hpcla_comm_t *comm, double *scal_dev, const double *tu, double *uh, int64_t n, int64_t iter,
+                     const int64_t *state_dev, void *work, void *stream);
+int hpcla_lsqr_v_f64(hpcla_comm_t *comm, double *scal_dev, const double *tv, double *vh, int64_t n, int64_t iter,
+                     int64_t *state_dev, double *pair_out_dev, void *work, void *stream);
+int hpcla_lsqr_xw_f64(const double *scal_dev, const double *vh, double *x, double *w, int64_t n, int64_t iter,
+                      const int64_t *state_dev, void *stream);
+/* Iterations first_iter .. first_iter + iters - 1 enqueued by ONE host call: per iteration tu = A*vh on A's plan, lsqr_u,
+ * tv = At*uh on At's plan (both through hpcla_spmv_dist_*, always executed), lsqr_v with its step, lsqr_xw.  The plan and CSR
+ * arguments of hpcla_bicgstab_iterations_* come twice: for A (nrows = m local rows; its x operand has nrows_t entries) and,
+ * suffixed _t, for At (nrows_t = n local rows).  uh, tu: nrows doubles; x, vh, w, tv: nrows_t doubles.  hist_dev: pairs,
+ * [2j] = |rbar_j|^2 and [2j+1] = |Abar' rbar_j|^2 of the recurrences (global on every rank, not all-reduced); pair 0 is the
+ * caller's.  The state lives in the last 32 bytes of work and is set up by the caller.  Only enqueues. */
+int hpcla_lsqr_iterations_f64_i32(hpcla_comm_t *comm, hpcla_halo_plan_t *plan, const int32_t *rowptr,
+                                  const int32_t *colval_split, const int16_t *cols16, const hpcla_block_patterns_t *patterns,
+                                  const double *nzval, int64_t nrows, int64_t nnz, int index_base,
+                                  const int32_t *interior_blocks, int64_t n_interior, const int32_t *boundary_blocks,
+                                  int64_t n_boundary, hpcla_halo_plan_t *plan_t, const int32_t *rowptr_t,
+                                  const int32_t *colval_split_t, const int16_t *cols16_t,
+                                  const hpcla_block_patterns_t *patterns_t, const double *nzval_t, int64_t nrows_t,
+                                  int64_t nnz_t, int index_base_t, const int32_t *interior_blocks_t, int64_t n_interior_t,
+                                  const int32_t *boundary_blocks_t, int64_t n_boundary_t, double *x, double *uh, double *vh,
+                                  double *w, double *tu, double *tv, double *hist_dev, double *scal_dev, void *work,
+                                  int64_t first_iter, int iters, void *stream);
+int hpcla_lsqr_iterations_f64_i64(hpcla_comm_t *comm, hpcla_halo_plan_t *plan, const int64_t *rowptr,
+                                  const int64_t *colval_split, const double *nzval, int64_t nrows, int64_t nnz, int index_base,
+                                  const int32_t *interior_blocks, int64_t n_interior, const int32_t *boundary_blocks,
+                                  int64_t n_boundary, hpcla_halo_plan_t *plan_t, const int64_t *rowptr_t,
+                                  const int64_t *colval_split_t, const double *nzval_t, int64_t nrows_t, int64_t nnz_t,
+                                  int index_base_t, const int32_t *interior_blocks_t, int64_t n_interior_t,
+                                  const int32_t *boundary_blocks_t, int64_t n_boundary_t, double *x, double *uh, double *vh,
+                                  double *w, double *tu, double *tv, double *hist_dev, double *scal_dev, void *work,
+                                  int64_t first_iter, int iters, void *stream);
 /* ---- Restarted GMRES(m) for nonsymmetric A: gated steps of right-preconditioned GMRES with twice-applied classical
  * Gram-Schmidt, K = identity or dinv .* (no reference counterpart; a caller of the reference's operators composes the method
  * from A*p, src/sparse.jl:2096-2128, dot, src/vectors.jl:798-812, and the broadcasts, src/vectors.jl:1203-1226: 2c dots, 2c

@@ -13,6 +13,8 @@ Layout
   cg.py              fixed-iteration CG harness; cg(): the converging solver (Jacobi preconditioner, device-side stop)
   bicgstab.py        bicgstab(): BiCGStab for nonsymmetric A, the same device-side stop (csrc/vecops.hip, bicg_* kernels)
   gmres.py           gmres(): restarted GMRES(m), fused twice-applied Gram-Schmidt, the same device-side stop (gmres_* kernels)
+  lsqr.py            lsqr(): least squares for rectangular A on A and its materialised transpose, damped form, two stop rules
+                     on the device (lsqr_* kernels)
   indexing.py        v[a:b], X[r, c], A[r, c], A[:, k], diag(A) and SubmatrixPlan (csrc/submatrix.hip)
   transpose.py matmat.py addition.py repartition.py   the SURVEY 8f "next" rows and their plans
 
@@ -39,6 +41,7 @@ from .matmat import clear_matrix_plan_cache, get_matrix_plan, spgemm
 from .cg import CGGraphPair, CGInfo, CGWorkspace, PCGWorkspace, cg, cg_fixed_iterations, cg_iterate, cg_setup
 from .bicgstab import BiCGStabWorkspace, bicgstab
 from .gmres import GMRESWorkspace, gmres
+from .lsqr import LSQRInfo, LSQRWorkspace, lsqr
 from .convert import to_backend
 from .transpose import (HostTransposeStructure, TransposedHPCSparseMatrix, TransposedHPCVector, TransposePlan,
                         DenseTransposeLists, HostSpmmTPlan, adjoint, clear_transpose_plan_cache, get_transpose_plan,

@@ -167,6 +167,19 @@ _SIGNATURES = {
                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
     "hpcla_bicgstab_iterations_f64_i64": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
+    # LSQR for rectangular A (hp.lsqr): the gated steps and the chunk of iterations (the plan / CSR block twice: A, then At)
+    "hpcla_lsqr_work_bytes": [],
+    "hpcla_lsqr_u_f64": [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
+    "hpcla_lsqr_v_f64": [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp],
+    "hpcla_lsqr_xw_f64": [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp],
+    "hpcla_lsqr_iterations_f64_i32": [_vp,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
+    "hpcla_lsqr_iterations_f64_i64": [_vp,
+                                      _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
+                                      _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
     # restarted GMRES (hp.gmres): the gated steps, the chunk of inner steps, the start and the finish of a cycle
     "hpcla_gmres_work_bytes": [_i32],
     "hpcla_gmres_small_offset": [_i32, _i32],
@@ -293,6 +306,7 @@ _RESTYPES = {
     "hpcla_cols16_padded_len": _i64,
     "hpcla_pcg_work_bytes": _i64,
     "hpcla_bicgstab_work_bytes": _i64,
+    "hpcla_lsqr_work_bytes": _i64,
     "hpcla_gmres_work_bytes": _i64,
     "hpcla_gmres_small_offset": _i64,
 }

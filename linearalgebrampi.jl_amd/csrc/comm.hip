@@ -1272,6 +1272,94 @@ HPCLA_API int hpcla_bicgstab_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_c
                                              scal_dev, work, first_iter, iters, stream);
 }
 
+// ---- a chunk of gated LSQR iterations in ONE host call (the solver, hp.lsqr) ---------------------------------------
+// min |A x - b|^2 + damp^2 |x|^2 for A of any shape m x n, At its materialised transpose (a matrix and a plan of its own).
+// Iteration j = first_iter .. first_iter + iters - 1 (1-based over the whole solve), in this order (the scalars, the gates and
+// the bytes: csrc/vecops.hip):
+//   1. tu = A vh                    hpcla_spmv_dist_* on A's plan -- always executed, not gated
+//   2. uh, uu                       hpcla_lsqr_u_f64: one all-reduce [uu]
+//   3. tv = At uh                   the SpMV on At's plan -- always executed
+//   4. vh, vv, the step, the gates  hpcla_lsqr_v_f64: gate U, one all-reduce [vv], then the one-thread step
+//   5. x += t1 w, w                 hpcla_lsqr_xw_f64 (x only in the iteration that stopped)
+// One rank: 2 SpMV + 5 launches (the step is folded into vv's second stage).  N ranks: + 2 window all-reduces and one 64-lane
+// step launch.  hist_dev[2 j], hist_dev[2 j + 1] = |rbar_j|^2, |Abar' rbar_j|^2 of the recurrences: formed from global
+// scalars on every rank, never all-reduced.
+template <typename I, typename F, typename G>
+static int lsqr_iterations_impl(F split_fn, G fused_fn, hpcla_comm_t *comm, hpcla_halo_plan_t *plan, const I *rowptr,
+                                const I *colval, const int16_t *cols16, const hpcla_block_patterns *patterns,
+                                const double *nzval, int64_t nrows, int64_t nnz, int index_base, const int32_t *interior,
+                                int64_t n_interior, const int32_t *boundary, int64_t n_boundary, hpcla_halo_plan_t *plan_t,
+                                const I *rowptr_t, const I *colval_t, const int16_t *cols16_t,
+                                const hpcla_block_patterns *patterns_t, const double *nzval_t, int64_t nrows_t, int64_t nnz_t,
+                                int index_base_t, const int32_t *interior_t, int64_t n_interior_t, const int32_t *boundary_t,
+                                int64_t n_boundary_t, double *x, double *uh, double *vh, double *w, double *tu, double *tv,
+                                double *hist_dev, double *scal_dev, void *work, int64_t first_iter, int iters, void *stream)
+{
+    if (iters < 0 || first_iter < 1) return set_error(HPCLA_ERR_INVALID, "lsqr_iterations: negative count or first_iter < 1");
+    if (nrows < 0 || nnz < 0 || nrows_t < 0 || nnz_t < 0) return set_error(HPCLA_ERR_INVALID, "lsqr_iterations: negative size");
+    if (!hist_dev || !scal_dev || !work) return set_error(HPCLA_ERR_INVALID, "lsqr_iterations: null scalar / work buffer");
+    if ((nrows > 0 && (!uh || !tu)) || (nrows_t > 0 && (!x || !vh || !w || !tv)))
+        return set_error(HPCLA_ERR_INVALID, "lsqr_iterations: null vector");
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(uh) | reinterpret_cast<uintptr_t>(vh) |
+         reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(tu) | reinterpret_cast<uintptr_t>(tv)) & 15)
+        return set_error(HPCLA_ERR_INVALID, "lsqr_iterations: vectors must be 16-byte aligned");
+    int64_t *state = reinterpret_cast<int64_t *>(static_cast<char *>(work) + hpcla_lsqr_work_bytes()) - 4;
+    for (int64_t j = first_iter; j < first_iter + iters; ++j) {
+        int rc = spmv_dist_impl<I>(split_fn, fused_fn, plan, rowptr, colval, nzval, vh, nrows_t, tu, nrows, nnz, index_base,
+                                   interior, n_interior, boundary, n_boundary, stream, nullptr, cols16, patterns);
+        if (rc) return rc;
+        rc = hpcla_lsqr_u_f64(comm, scal_dev, tu, uh, nrows, j, state, work, stream);
+        if (rc) return rc;
+        rc = spmv_dist_impl<I>(split_fn, fused_fn, plan_t, rowptr_t, colval_t, nzval_t, uh, nrows, tv, nrows_t, nnz_t,
+                               index_base_t, interior_t, n_interior_t, boundary_t, n_boundary_t, stream, nullptr, cols16_t,
+                               patterns_t);
+        if (rc) return rc;
+        rc = hpcla_lsqr_v_f64(comm, scal_dev, tv, vh, nrows_t, j, state, hist_dev + 2 * j, work, stream);
+        if (rc) return rc;
+        rc = hpcla_lsqr_xw_f64(scal_dev, vh, x, w, nrows_t, j, state, stream);
+        if (rc) return rc;
+    }
+    return HPCLA_OK;
+}
+
+HPCLA_API int hpcla_lsqr_iterations_f64_i32(hpcla_comm_t *comm, hpcla_halo_plan_t *plan, const int32_t *rowptr,
+                                            const int32_t *colval_split, const int16_t *cols16,
+                                            const hpcla_block_patterns_t *patterns, const double *nzval, int64_t nrows,
+                                            int64_t nnz, int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                            const int32_t *boundary_blocks, int64_t n_boundary, hpcla_halo_plan_t *plan_t,
+                                            const int32_t *rowptr_t, const int32_t *colval_split_t, const int16_t *cols16_t,
+                                            const hpcla_block_patterns_t *patterns_t, const double *nzval_t, int64_t nrows_t,
+                                            int64_t nnz_t, int index_base_t, const int32_t *interior_blocks_t,
+                                            int64_t n_interior_t, const int32_t *boundary_blocks_t, int64_t n_boundary_t,
+                                            double *x, double *uh, double *vh, double *w, double *tu, double *tv,
+                                            double *hist_dev, double *scal_dev, void *work, int64_t first_iter, int iters,
+                                            void *stream)
+{
+    return lsqr_iterations_impl<int32_t>(spmv_split_i32, spmv_fused_i32, comm, plan, rowptr, colval_split, cols16, patterns,
+                                         nzval, nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks,
+                                         n_boundary, plan_t, rowptr_t, colval_split_t, cols16_t, patterns_t, nzval_t, nrows_t,
+                                         nnz_t, index_base_t, interior_blocks_t, n_interior_t, boundary_blocks_t, n_boundary_t,
+                                         x, uh, vh, w, tu, tv, hist_dev, scal_dev, work, first_iter, iters, stream);
+}
+
+HPCLA_API int hpcla_lsqr_iterations_f64_i64(hpcla_comm_t *comm, hpcla_halo_plan_t *plan, const int64_t *rowptr,
+                                            const int64_t *colval_split, const double *nzval, int64_t nrows, int64_t nnz,
+                                            int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                            const int32_t *boundary_blocks, int64_t n_boundary, hpcla_halo_plan_t *plan_t,
+                                            const int64_t *rowptr_t, const int64_t *colval_split_t, const double *nzval_t,
+                                            int64_t nrows_t, int64_t nnz_t, int index_base_t,
+                                            const int32_t *interior_blocks_t, int64_t n_interior_t,
+                                            const int32_t *boundary_blocks_t, int64_t n_boundary_t, double *x, double *uh,
+                                            double *vh, double *w, double *tu, double *tv, double *hist_dev, double *scal_dev,
+                                            void *work, int64_t first_iter, int iters, void *stream)
+{
+    return lsqr_iterations_impl<int64_t>(spmv_split_i64, spmv_fused_i64, comm, plan, rowptr, colval_split, nullptr, nullptr,
+                                         nzval, nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks,
+                                         n_boundary, plan_t, rowptr_t, colval_split_t, nullptr, nullptr, nzval_t, nrows_t,
+                                         nnz_t, index_base_t, interior_blocks_t, n_interior_t, boundary_blocks_t, n_boundary_t,
+                                         x, uh, vh, w, tu, tv, hist_dev, scal_dev, work, first_iter, iters, stream);
+}
+
 // ---- a chunk of gated GMRES(m) inner steps in ONE host call (the solver, hp.gmres) -----------------------------------
 // Right-preconditioned restarted GMRES with twice-applied classical Gram-Schmidt, K = identity (dinv == NULL: the SpMV reads
 // the basis column itself) or dinv .*.  Step k = first_iter .. first_iter + iters - 1 (1-based over the whole solve), column

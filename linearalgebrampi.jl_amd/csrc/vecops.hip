@@ -810,6 +810,243 @@ __global__ __launch_bounds__(256) void bicg_p_kernel(const double *__restrict__ 
     }
 }
 
+// ---- gated LSQR steps (the solver hpcla_lsqr_iterations_*: min |A x - b|^2 + damp^2 |x|^2 for a rectangular A) -------------
+// Golub-Kahan bidiagonalisation on A (m x n) and At with NO vector ever normalised in memory: uh and vh are kept unnormalised
+// next to their norms beta and alpha, and the scalings ride in the passes that read the vectors anyway (two normalisation
+// passes, 16 (m + n) bytes per row and column, are not made).  Iteration j (1-based over the whole solve); tu = A vh and
+// tv = At uh are the SpMV's, ungated.  Bytes per row (u) or column (v, xw):
+//   lsqr_u    uh = tu / alpha - (alpha / beta) uh;  uu = uh.uh                    read tu, uh, write uh            24
+//   lsqr_v    beta' = sqrt(uu);  vh = tv / beta' - (beta' / alpha) vh;  vv = vh.vh  read tv, vh, write vh            24
+//             gate U  uu == 0: vh is left alone and vv = 0 (exact termination: the step ends the solve)
+//   step      one thread, behind vv's all-reduce; alpha' = sqrt(vv):
+//             anorm2 += (alpha^2 + beta'^2) + damp^2
+//             rhobar1 = sqrt(rhobar^2 + damp^2);  psi = (damp / rhobar1) phibar;  phibar = (rhobar / rhobar1) phibar;  res2 += psi^2
+//             rho = sqrt(rhobar1^2 + beta'^2);  c = rhobar1 / rho;  s = beta' / rho;  theta = s alpha';  rhobar = -c alpha'
+//             phi = c phibar;  phibar = s phibar;  t1 = phi / rho;  t2 = theta / rho
+//             rn2 = phibar^2 + res2;  arn = alpha' |s phi|;  pair = (rn2, arn^2)
+//             gates, in order:  !(rn2 and arn finite)                -> breakdown, done_iter = j - 1
+//                               rn2 <= thr                           -> converged, done_iter = j
+//                               arn^2 <= (ntol2 anorm2) rn2          -> least squares (status 3), done_iter = j
+//             alpha = alpha';  beta = beta'
+//   lsqr_xw   x = x + t1 w;  w = vh / alpha - t2 w                                read x, w, vh, write x, w        40
+//             (x only, 24 B, in the iteration that stopped: status 1 or 3 and done_iter == j)
+// 24 m + 64 n bytes per iteration next to the two SpMVs, two all-reduces; composed from norm / scale / axpy it is about
+// 48 m + 96 n and four host read-backs.  Divides, multiplies and subtractions are rounded separately, in the order written.
+// The state is PCG's (done_iter, status, thr, ntol2): thr = max(rtol |b|, atol)^2 and ntol2 = ntol^2 as doubles.
+// The scalars live in LSQR_SCALARS doubles at these slots (damp is the caller's; the others are read and written here):
+enum LsqrSlot {
+    LSQR_ALPHA = 0, LSQR_BETA = 1, LSQR_UU = 2, LSQR_VV = 3, LSQR_PHIBAR = 4, LSQR_RHOBAR = 5, LSQR_RES2 = 6, LSQR_ANORM2 = 7,
+    LSQR_T1 = 8, LSQR_T2 = 9, LSQR_RHO = 10, LSQR_C = 11, LSQR_S = 12, LSQR_THETA = 13, LSQR_PHI = 14, LSQR_RN2 = 15,
+    LSQR_ARN = 16, LSQR_DAMP = 17, LSQR_SCALARS = 24
+};
+constexpr int64_t LSQR_LEAST_SQUARES = 3;
+// Cache policy: tu in lsqr_u and tv in lsqr_v (HPCLA_CG_NT bit 2: their last use) and x in lsqr_xw (bit 0) are not touched
+// again within the iteration and go non-temporally; uh, vh and w are re-read by the next SpMV or kernel.
+
+__device__ __forceinline__ bool lsqr_finite(double a) { return fabs(a) < __builtin_huge_val(); }     // false for NaN too
+
+template <bool NTQ>
+__global__ __launch_bounds__(RT) void lsqr_u_kernel(const double *__restrict__ scal, const double *__restrict__ tu,
+                                                    double *__restrict__ uh, int64_t n, const int64_t *__restrict__ state,
+                                                    double *__restrict__ partial)
+{
+    if (state[1] != PCG_RUNNING) return;
+    const double alpha = scal[LSQR_ALPHA];
+    const double g = alpha / scal[LSQR_BETA];
+    const int64_t n2 = n / 2;
+    const double2 *t2 = reinterpret_cast<const double2 *>(tu);
+    double2 *u2 = reinterpret_cast<double2 *>(uh);
+    double acc = 0.0;
+    int64_t i = (int64_t)blockIdx.x * RT + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * RT;
+    for (; i < n2; i += stride) {
+        const double2 tv = NTQ ? nt_load2(t2 + i) : t2[i];
+        double2 uv = u2[i];
+        uv.x = tv.x / alpha - g * uv.x;
+        uv.y = tv.y / alpha - g * uv.y;
+        u2[i] = uv;
+        acc = acc + uv.x * uv.x;
+        acc = acc + uv.y * uv.y;
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t j = n - 1;
+        const double un = tu[j] / alpha - g * uh[j];
+        uh[j] = un;
+        acc = acc + un * un;
+    }
+    const double r = block_reduce<RED_SUM>(acc);
+    if (threadIdx.x == 0) partial[blockIdx.x] = r;
+}
+
+// second stage of uu (reduce_stage2<RED_SUM>'s order), one workgroup
+__global__ __launch_bounds__(RT) void lsqr_u_stage2_kernel(const double *__restrict__ partial, int np,
+                                                           const int64_t *__restrict__ state, double *__restrict__ scal)
+{
+    if (state[1] != PCG_RUNNING) return;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < np; i += RT) acc = acc + partial[i];
+    const double uu = block_reduce<RED_SUM>(acc);
+    if (threadIdx.x == 0) scal[LSQR_UU] = uu;
+}
+
+template <bool NTQ>
+__global__ __launch_bounds__(RT) void lsqr_v_kernel(const double *__restrict__ scal, const double *__restrict__ tv,
+                                                    double *__restrict__ vh, int64_t n, const int64_t *__restrict__ state,
+                                                    double *__restrict__ partial)
+{
+    if (state[1] != PCG_RUNNING) return;
+    const double uu = scal[LSQR_UU];
+    if (uu == 0.0) return;                                       // gate U (vv = 0 is the second stage's)
+    const double beta = sqrt(uu);
+    const double g = beta / scal[LSQR_ALPHA];
+    const int64_t n2 = n / 2;
+    const double2 *t2 = reinterpret_cast<const double2 *>(tv);
+    double2 *v2 = reinterpret_cast<double2 *>(vh);
+    double acc = 0.0;
+    int64_t i = (int64_t)blockIdx.x * RT + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * RT;
+    for (; i < n2; i += stride) {
+        const double2 tw = NTQ ? nt_load2(t2 + i) : t2[i];
+        double2 vv = v2[i];
+        vv.x = tw.x / beta - g * vv.x;
+        vv.y = tw.y / beta - g * vv.y;
+        v2[i] = vv;
+        acc = acc + vv.x * vv.x;
+        acc = acc + vv.y * vv.y;
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t j = n - 1;
+        const double vn = tv[j] / beta - g * vh[j];
+        vh[j] = vn;
+        acc = acc + vn * vn;
+    }
+    const double r = block_reduce<RED_SUM>(acc);
+    if (threadIdx.x == 0) partial[blockIdx.x] = r;
+}
+
+// the scalar step of iteration `iter` and its gates; uu and vv are global sums here.  pair is not all-reduced afterwards
+__device__ __forceinline__ void lsqr_step(double *scal, double *pair, int64_t iter, int64_t *state)
+{
+    const double alpha = scal[LSQR_ALPHA], damp = scal[LSQR_DAMP];
+    const double beta1 = sqrt(scal[LSQR_UU]), alpha1 = sqrt(scal[LSQR_VV]);
+    const double anorm2 = scal[LSQR_ANORM2] + ((alpha * alpha + beta1 * beta1) + damp * damp);
+    double rhobar = scal[LSQR_RHOBAR], phibar = scal[LSQR_PHIBAR];
+    const double rhobar1 = sqrt(rhobar * rhobar + damp * damp);
+    const double psi = (damp / rhobar1) * phibar;
+    phibar = (rhobar / rhobar1) * phibar;
+    const double res2 = scal[LSQR_RES2] + psi * psi;
+    const double rho = sqrt(rhobar1 * rhobar1 + beta1 * beta1);
+    const double c = rhobar1 / rho;
+    const double s = beta1 / rho;
+    const double theta = s * alpha1;
+    rhobar = -c * alpha1;
+    const double phi = c * phibar;
+    phibar = s * phibar;
+    const double t1 = phi / rho;
+    const double t2 = theta / rho;
+    const double rn2 = phibar * phibar + res2;
+    const double arn = alpha1 * fabs(s * phi);
+    const double arn2 = arn * arn;
+    scal[LSQR_ANORM2] = anorm2;
+    scal[LSQR_RES2] = res2;
+    scal[LSQR_RHO] = rho;
+    scal[LSQR_C] = c;
+    scal[LSQR_S] = s;
+    scal[LSQR_THETA] = theta;
+    scal[LSQR_RHOBAR] = rhobar;
+    scal[LSQR_PHI] = phi;
+    scal[LSQR_PHIBAR] = phibar;
+    scal[LSQR_T1] = t1;
+    scal[LSQR_T2] = t2;
+    scal[LSQR_RN2] = rn2;
+    scal[LSQR_ARN] = arn;
+    scal[LSQR_ALPHA] = alpha1;
+    scal[LSQR_BETA] = beta1;
+    pair[0] = rn2;
+    pair[1] = arn2;
+    const double *lim = reinterpret_cast<const double *>(state);
+    if (!(lsqr_finite(rn2) && lsqr_finite(arn))) {
+        state[0] = iter - 1;
+        state[1] = PCG_BREAKDOWN;
+    } else if (rn2 <= lim[2]) {
+        state[0] = iter;
+        state[1] = PCG_CONVERGED;
+    } else if (arn2 <= (lim[3] * anorm2) * rn2) {
+        state[0] = iter;
+        state[1] = LSQR_LEAST_SQUARES;
+    }
+}
+
+// second stage of vv, one workgroup; gate U's vv = 0; the step where no all-reduce follows (pair != NULL)
+__global__ __launch_bounds__(RT) void lsqr_v_stage2_kernel(const double *__restrict__ partial, int np, int64_t iter,
+                                                           int64_t *__restrict__ state, double *__restrict__ scal,
+                                                           double *__restrict__ pair)
+{
+    if (state[1] != PCG_RUNNING) return;
+    double vv = 0.0;
+    if (scal[LSQR_UU] != 0.0) {                                  // uniform; else gate U: the partials are stale
+        double acc = 0.0;
+        for (int i = threadIdx.x; i < np; i += RT) acc = acc + partial[i];
+        vv = block_reduce<RED_SUM>(acc);
+    }
+    if (threadIdx.x == 0) {
+        scal[LSQR_VV] = vv;
+        if (pair) lsqr_step(scal, pair, iter, state);
+    }
+}
+
+__global__ void lsqr_step_kernel(double *__restrict__ scal, double *__restrict__ pair, int64_t iter,
+                                 int64_t *__restrict__ state)
+{
+    if (threadIdx.x == 0 && state[1] == PCG_RUNNING) lsqr_step(scal, pair, iter, state);
+}
+
+template <bool NTX>
+__global__ __launch_bounds__(256) void lsqr_xw_kernel(const double *__restrict__ scal, const double *__restrict__ vh,
+                                                      double *__restrict__ x, double *__restrict__ w, int64_t n, int64_t iter,
+                                                      const int64_t *__restrict__ state)
+{
+    const int64_t status = state[1];
+    const bool last = (status == PCG_CONVERGED || status == LSQR_LEAST_SQUARES) && state[0] == iter;
+    if (!(status == PCG_RUNNING || last)) return;
+    const double t1 = scal[LSQR_T1];
+    const int64_t n2 = n / 2;
+    const double2 *v2 = reinterpret_cast<const double2 *>(vh);
+    double2 *x2 = reinterpret_cast<double2 *>(x);
+    double2 *w2 = reinterpret_cast<double2 *>(w);
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    if (last) {                                                  // the iteration that stopped: x = x + t1 w, nothing else
+        for (; i < n2; i += stride) {
+            const double2 wv = w2[i];
+            double2 xv = NTX ? nt_load2(x2 + i) : x2[i];
+            xv.x = xv.x + t1 * wv.x;
+            xv.y = xv.y + t1 * wv.y;
+            if (NTX) nt_store2(xv, x2 + i); else x2[i] = xv;
+        }
+        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) x[n - 1] = x[n - 1] + t1 * w[n - 1];
+        return;
+    }
+    const double alpha = scal[LSQR_ALPHA], t2 = scal[LSQR_T2];
+    for (; i < n2; i += stride) {
+        const double2 vv = v2[i];
+        double2 wv = w2[i];
+        double2 xv = NTX ? nt_load2(x2 + i) : x2[i];
+        xv.x = xv.x + t1 * wv.x;
+        xv.y = xv.y + t1 * wv.y;
+        wv.x = vv.x / alpha - t2 * wv.x;
+        wv.y = vv.y / alpha - t2 * wv.y;
+        if (NTX) nt_store2(xv, x2 + i); else x2[i] = xv;
+        w2[i] = wv;
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t j = n - 1;
+        const double wj = w[j];
+        x[j] = x[j] + t1 * wj;
+        w[j] = vh[j] / alpha - t2 * wj;
+    }
+}
+
 // ---- gated GMRES(m) steps (the solver hpcla_gmres_iterations_*; right preconditioning, K = identity or dinv .*) ---------
 // Inner step k (1-based over the whole solve), column j = (k - 1) mod m, c = j + 1 basis columns V_0 .. V_j at pitch ldv (even,
 // so every column is 16-byte aligned); w = A z is the SpMV's, ungated (z is V_j without a preconditioner).  Classical
@@ -1605,6 +1842,70 @@ HPCLA_API int hpcla_bicg_p_f64(const double *rho_new_dev, const double *rho_dev,
     else
         bicg_p_kernel<false><<<ew_grid(n / 2), 256, 0, st>>>(rho_new_dev, rho_dev, rv_dev, triple_dev, triple_dev + 1, r, v,
                                                              nullptr, p, nullptr, n, state_dev);
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
+// scratch of the gated LSQR steps: one array of stage-1 partials, then the solve's state (its last 32 bytes)
+HPCLA_API int64_t hpcla_lsqr_work_bytes(void)
+{
+    return (int64_t)(MAX_PARTIALS + PCG_STATE_WORDS) * (int64_t)sizeof(double);
+}
+
+HPCLA_API int hpcla_lsqr_u_f64(hpcla_comm_t *comm, double *scal_dev, const double *tu, double *uh, int64_t n, int64_t iter,
+                               const int64_t *state_dev, void *work, void *stream)
+{
+    if (n < 0 || iter < 1) return set_error(HPCLA_ERR_INVALID, "lsqr_u: negative size or iteration < 1");
+    if (!scal_dev || !state_dev || !work) return set_error(HPCLA_ERR_INVALID, "lsqr_u: null scalars / state / work");
+    if (n > 0 && (!tu || !uh)) return set_error(HPCLA_ERR_INVALID, "lsqr_u: null vector");
+    if (bicg_misaligned({tu, uh})) return set_error(HPCLA_ERR_INVALID, "lsqr_u: vectors must be 16-byte aligned");
+    double *partial = reinterpret_cast<double *>(work);
+    const int g = reduce_grid(n);
+    hipStream_t s = as_stream(stream);
+    if (cg_nt_mask() & 4) lsqr_u_kernel<true><<<g, RT, 0, s>>>(scal_dev, tu, uh, n, state_dev, partial);
+    else lsqr_u_kernel<false><<<g, RT, 0, s>>>(scal_dev, tu, uh, n, state_dev, partial);
+    HPCLA_CHECK_LAUNCH();
+    lsqr_u_stage2_kernel<<<1, RT, 0, s>>>(partial, g, state_dev, scal_dev);
+    HPCLA_CHECK_LAUNCH();
+    if (comm) return allreduce_on(comm, scal_dev + LSQR_UU, 1, 0, stream);
+    return HPCLA_OK;
+}
+
+HPCLA_API int hpcla_lsqr_v_f64(hpcla_comm_t *comm, double *scal_dev, const double *tv, double *vh, int64_t n, int64_t iter,
+                               int64_t *state_dev, double *pair_out_dev, void *work, void *stream)
+{
+    if (n < 0 || iter < 1) return set_error(HPCLA_ERR_INVALID, "lsqr_v: negative size or iteration < 1");
+    if (!scal_dev || !state_dev || !work) return set_error(HPCLA_ERR_INVALID, "lsqr_v: null scalars / state / work");
+    if (n > 0 && (!tv || !vh)) return set_error(HPCLA_ERR_INVALID, "lsqr_v: null vector");
+    if (bicg_misaligned({tv, vh})) return set_error(HPCLA_ERR_INVALID, "lsqr_v: vectors must be 16-byte aligned");
+    double *partial = reinterpret_cast<double *>(work);
+    const int g = reduce_grid(n);
+    hipStream_t s = as_stream(stream);
+    if (cg_nt_mask() & 4) lsqr_v_kernel<true><<<g, RT, 0, s>>>(scal_dev, tv, vh, n, state_dev, partial);
+    else lsqr_v_kernel<false><<<g, RT, 0, s>>>(scal_dev, tv, vh, n, state_dev, partial);
+    HPCLA_CHECK_LAUNCH();
+    lsqr_v_stage2_kernel<<<1, RT, 0, s>>>(partial, g, iter, state_dev, scal_dev, comm ? nullptr : pair_out_dev);
+    HPCLA_CHECK_LAUNCH();
+    if (!comm) return HPCLA_OK;
+    const int rc = allreduce_on(comm, scal_dev + LSQR_VV, 1, 0, stream);
+    if (rc) return rc;
+    if (!pair_out_dev) return HPCLA_OK;
+    lsqr_step_kernel<<<1, 64, 0, s>>>(scal_dev, pair_out_dev, iter, state_dev);
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
+HPCLA_API int hpcla_lsqr_xw_f64(const double *scal_dev, const double *vh, double *x, double *w, int64_t n, int64_t iter,
+                                const int64_t *state_dev, void *stream)
+{
+    if (n < 0 || iter < 1) return set_error(HPCLA_ERR_INVALID, "lsqr_xw: negative size or iteration < 1");
+    if (!scal_dev || !state_dev) return set_error(HPCLA_ERR_INVALID, "lsqr_xw: null scalars / state");
+    if (n == 0) return HPCLA_OK;
+    if (!vh || !x || !w) return set_error(HPCLA_ERR_INVALID, "lsqr_xw: null vector");
+    if (bicg_misaligned({vh, x, w})) return set_error(HPCLA_ERR_INVALID, "lsqr_xw: vectors must be 16-byte aligned");
+    hipStream_t s = as_stream(stream);
+    if (cg_nt_mask() & 1) lsqr_xw_kernel<true><<<ew_grid(n / 2), 256, 0, s>>>(scal_dev, vh, x, w, n, iter, state_dev);
+    else lsqr_xw_kernel<false><<<ew_grid(n / 2), 256, 0, s>>>(scal_dev, vh, x, w, n, iter, state_dev);
     HPCLA_CHECK_LAUNCH();
     return HPCLA_OK;
 }
