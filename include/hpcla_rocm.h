@@ -1099,6 +1099,68 @@ int hpcla_lsqr_iterations_f64_i64(hpcla_comm_t *comm, hpcla_halo_plan_t *plan, c
                                   const int32_t *boundary_blocks_t, int64_t n_boundary_t, double *x, double *uh, double *vh,
                                   double *w, double *tu, double *tv, double *hist_dev, double *scal_dev, void *work,
                                   int64_t first_iter, int iters, void *stream);
+/* ---- MINRES for a symmetric, possibly indefinite A: A x = b by Paige and Saunders' Lanczos recurrence with a positive
+ * definite diagonal preconditioner M = dinv .* or the identity (the reference serves this class with ldlt(A) \ b through MUMPS
+ * on the host, src/mumps_factorization.jl:247-259; a caller of its operators composes the method from A*v,
+ * src/sparse.jl:2096-2128, dot, src/vectors.jl:798-812, and the broadcasts, src/vectors.jl:1203-1226: about ten launches and
+ * three host read-backs per iteration).  No vector is normalised in memory: the Lanczos vectors r1, r2 are kept unnormalised
+ * next to their M-norms oldb and beta, y = M r2 is the SpMV's operand (r2 itself when dinv == NULL), v = y / beta is never
+ * stored.
+ * The state is the CG solver's (done_iter, status, thr, reserved); thr = max(rtol sqrt(b.M b), atol)^2: with dinv the stop rule
+ * is in the M norm, sqrt(r.M r).
+ * scal_dev: 16 doubles.  Slots: 0 beta, 1 oldb, 2 yt (= y.t, the SpMV's, all-reduced), 3 bb (= rn.yn, all-reduced), 4 alfa,
+ * 5 cs, 6 sn, 7 dbar, 8 epsln, 9 oldeps, 10 delta, 11 gbar, 12 gamma, 13 phi, 14 phibar, 15 reserved.  Before the first
+ * iteration: beta = phibar = sqrt(r0.M r0), cs = -1; the rest 0.
+ * Iteration `iter` is 1-based over the whole solve; every entry is a no-op writing no byte once status != 0 (minres_xw runs
+ * once more when status == 1 and done_iter == iter).  The sum is all-reduced once (comm != NULL):
+ *   minres_r  (two scales, two axpys, [a product,] dot)
+ *                                 alfa = yt / (beta * beta);  rn = (t / beta - (alfa / beta) * r2) - (beta / oldb) * r1, written
+ *                                 over r1 (iter == 1: no r1 term, r1 is only written);  dinv != NULL: yn = dinv .* rn;
+ *                                 bb = rn.yn (rn.rn without dinv; yn may be NULL then).  32 bytes per row, 48 with dinv.  Then,
+ *                                 pair_out_dev != NULL, the step by one thread, behind the all-reduce:
+ *                                   gate N  !(bb >= 0), or bb or alfa not finite:  status = 2, done_iter = iter - 1
+ *                                   beta' = sqrt(bb);  oldeps = epsln;  delta = cs * dbar + sn * alfa
+ *                                   gbar = sn * dbar - cs * alfa;  epsln = sn * beta';  dbar = (-cs) * beta'
+ *                                   gamma = sqrt(gbar * gbar + beta' * beta')
+ *                                   gate G  !(gamma > 0):                          status = 2, done_iter = iter - 1
+ *                                   cs = gbar / gamma;  sn = beta' / gamma;  phi = cs * phibar;  phibar = sn * phibar
+ *                                   pair_out_dev = (phibar * phibar, bb);  oldb = beta;  beta = beta'
+ *                                   gate C  phibar * phibar <= thr:                status = 1, done_iter = iter
+ *                                 A gate that reports a breakdown writes no scalar.  pair_out_dev == NULL: no step, no gate
+ *                                 (the setup's r2 = t, y = dinv .* r2, bb = r2.y from beta = 1, yt = 0 and r2 = 0).
+ *   minres_xw (a scale, three axpys)  w = ((y / oldb - oldeps * w1) - delta * w2) / gamma, written over w1;  x = x + phi * w.
+ *                                 y is the operand of this iteration's SpMV and oldb, after the step, its norm.  48 bytes per
+ *                                 row.  After a breakdown x keeps its value of iter - 1.
+ * Separate divide, multiply, add, subtract and square root, in the order written.  t (HPCLA_CG_NT bit 2) and x (bit 0) go
+ * non-temporally.  work: hpcla_minres_work_bytes() bytes -- one array of partials, then the 32 bytes the iterations entry
+ * uses as the state.  Vectors 16-byte aligned; a written vector aliases no other. */
+int64_t hpcla_minres_work_bytes(void);
+int hpcla_minres_r_f64(hpcla_comm_t *comm, double *scal_dev, const double *t, const double *r2, const double *dinv, double *r1,
+                       double *yn, int64_t n, int64_t iter, int64_t *state_dev, double *pair_out_dev, void *work,
+                       void *stream);
+int hpcla_minres_xw_f64(const double *scal_dev, const double *y, const double *w2, double *w1, double *x, int64_t n,
+                        int64_t iter, const int64_t *state_dev, void *stream);
+/* Iterations first_iter .. first_iter + iters - 1 enqueued by ONE host call: per iteration t = A*y with yt = y.t into slot 2
+ * (hpcla_spmv_dist_dot_*, always executed), minres_r with its step, minres_xw.  Two buffers each of r, w and (dinv != NULL) y
+ * rotate by the parity of the iteration: iteration j reads r2, y and w2 from the buffers (j - 1) & 1 (0: _a, 1: _b) and
+ * overwrites the buffers j & 1; before iteration 1 r_a = r0, y_a = dinv .* r0, w_a = w_b = 0.  dinv == NULL: y_a and y_b are
+ * not used and may be NULL.  hist_dev: pairs, [2j] = phibar_j^2 (the squared residual norm of the recurrence, in the M norm)
+ * and [2j+1] = beta_{j+1}^2 (global on every rank, not all-reduced); pair 0 is the caller's.  dot_work: the byte count of
+ * hpcla_spmv_dot_work_bytes.  The state lives in the last 32 bytes of work and is set up by the caller.  Everything else as
+ * for hpcla_pcg_iterations_*.  Only enqueues. */
+int hpcla_minres_iterations_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int32_t *rowptr,
+                                    const int32_t *colval_split, const int16_t *cols16, const hpcla_block_patterns_t *patterns,
+                                    const double *nzval, int64_t nrows, int64_t nnz, int index_base,
+                                    const int32_t *interior_blocks, int64_t n_interior, const int32_t *boundary_blocks,
+                                    int64_t n_boundary, const double *dinv, double *x, double *r_a, double *r_b, double *y_a,
+                                    double *y_b, double *w_a, double *w_b, double *t, double *hist_dev, double *scal_dev,
+                                    void *dot_work, void *work, int64_t first_iter, int iters, void *stream);
+int hpcla_minres_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int64_t *rowptr,
+                                    const int64_t *colval_split, const double *nzval, int64_t nrows, int64_t nnz, int index_base,
+                                    const int32_t *interior_blocks, int64_t n_interior, const int32_t *boundary_blocks,
+                                    int64_t n_boundary, const double *dinv, double *x, double *r_a, double *r_b, double *y_a,
+                                    double *y_b, double *w_a, double *w_b, double *t, double *hist_dev, double *scal_dev,
+                                    void *dot_work, void *work, int64_t first_iter, int iters, void *stream);
 /* ---- Restarted GMRES(m) for nonsymmetric A: gated steps of right-preconditioned GMRES with twice-applied classical
  * Gram-Schmidt, K = identity or dinv .* (no reference counterpart; a caller of the reference's operators composes the method
  * from A*p, src/sparse.jl:2096-2128, dot, src/vectors.jl:798-812, and the broadcasts, src/vectors.jl:1203-1226: 2c dots, 2c

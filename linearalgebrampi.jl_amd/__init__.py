@@ -15,6 +15,8 @@ Layout
   gmres.py           gmres(): restarted GMRES(m), fused twice-applied Gram-Schmidt, the same device-side stop (gmres_* kernels)
   lsqr.py            lsqr(): least squares for rectangular A on A and its materialised transpose, damped form, two stop rules
                      on the device (lsqr_* kernels)
+  minres.py          minres(): MINRES for symmetric indefinite A, diagonal preconditioner, the same device-side stop in the M norm
+                     (minres_* kernels)
   indexing.py        v[a:b], X[r, c], A[r, c], A[:, k], diag(A) and SubmatrixPlan (csrc/submatrix.hip)
   transpose.py matmat.py addition.py repartition.py   the SURVEY 8f "next" rows and their plans
 
@@ -42,6 +44,7 @@ from .cg import CGGraphPair, CGInfo, CGWorkspace, PCGWorkspace, cg, cg_fixed_ite
 from .bicgstab import BiCGStabWorkspace, bicgstab
 from .gmres import GMRESWorkspace, gmres
 from .lsqr import LSQRInfo, LSQRWorkspace, lsqr
+from .minres import MinresWorkspace, minres
 from .convert import to_backend
 from .transpose import (HostTransposeStructure, TransposedHPCSparseMatrix, TransposedHPCVector, TransposePlan,
                         DenseTransposeLists, HostSpmmTPlan, adjoint, clear_transpose_plan_cache, get_transpose_plan,

@@ -180,6 +180,14 @@ _SIGNATURES = {
                                       _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
                                       _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
+    # MINRES for symmetric indefinite A (hp.minres): the gated steps and the chunk of iterations
+    "hpcla_minres_work_bytes": [],
+    "hpcla_minres_r_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp],
+    "hpcla_minres_xw_f64": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp],
+    "hpcla_minres_iterations_f64_i32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp,
+                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
+    "hpcla_minres_iterations_f64_i64": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp,
+                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
     # restarted GMRES (hp.gmres): the gated steps, the chunk of inner steps, the start and the finish of a cycle
     "hpcla_gmres_work_bytes": [_i32],
     "hpcla_gmres_small_offset": [_i32, _i32],
@@ -307,6 +315,7 @@ _RESTYPES = {
     "hpcla_pcg_work_bytes": _i64,
     "hpcla_bicgstab_work_bytes": _i64,
     "hpcla_lsqr_work_bytes": _i64,
+    "hpcla_minres_work_bytes": _i64,
     "hpcla_gmres_work_bytes": _i64,
     "hpcla_gmres_small_offset": _i64,
 }

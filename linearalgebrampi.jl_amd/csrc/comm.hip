@@ -1360,6 +1360,84 @@ HPCLA_API int hpcla_lsqr_iterations_f64_i64(hpcla_comm_t *comm, hpcla_halo_plan_
                                          x, uh, vh, w, tu, tv, hist_dev, scal_dev, work, first_iter, iters, stream);
 }
 
+// ---- a chunk of gated MINRES iterations in ONE host call (the solver, hp.minres) ------------------------------------
+// A x = b for a symmetric, possibly indefinite A, M = identity (dinv == NULL: y is r) or dinv .*.  Iteration j = first_iter ..
+// first_iter + iters - 1 (1-based over the whole solve), in this order (the scalars, the gates and the bytes: csrc/vecops.hip):
+//   1. t = A y, yt = y.t            hpcla_spmv_dist_dot_* -- always executed, not gated; one all-reduce [yt]
+//   2. rn, [yn,] bb, the step       hpcla_minres_r_f64: one all-reduce [bb], then the one-thread step with gates N, G, C
+//   3. w, x += phi w                hpcla_minres_xw_f64 (still runs in the iteration that converged)
+// The buffers rotate by the parity of j, so a chunk may start at any iteration: the operand y and r2 are buffer (j - 1) & 1,
+// rn and yn overwrite buffer j & 1 (r1 and the y before); w2 is buffer (j - 1) & 1 and the new w overwrites w1, buffer j & 1.
+// One rank: SpMV + dot stage + 3 launches (the step is folded into bb's second stage).  N ranks: + 2 window all-reduces and
+// one 64-lane step launch.  hist_dev[2 j], hist_dev[2 j + 1] = phibar_j^2, beta_{j+1}^2: formed from global scalars on every
+// rank, never all-reduced.
+template <typename I, typename F, typename G>
+static int minres_iterations_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const I *rowptr,
+                                  const I *colval, const int16_t *cols16, const hpcla_block_patterns *patterns,
+                                  const double *nzval, int64_t nrows, int64_t nnz, int index_base, const int32_t *interior,
+                                  int64_t n_interior, const int32_t *boundary, int64_t n_boundary, const double *dinv, double *x,
+                                  double *r_a, double *r_b, double *y_a, double *y_b, double *w_a, double *w_b, double *t,
+                                  double *hist_dev, double *scal_dev, void *dot_work, void *work, int64_t first_iter, int iters,
+                                  void *stream)
+{
+    if (iters < 0 || first_iter < 1) return set_error(HPCLA_ERR_INVALID, "minres_iterations: negative count or first_iter < 1");
+    if (nrows < 0 || nnz < 0) return set_error(HPCLA_ERR_INVALID, "minres_iterations: negative size");
+    if (!hist_dev || !scal_dev || !dot_work || !work)
+        return set_error(HPCLA_ERR_INVALID, "minres_iterations: null scalar / work buffer");
+    if (nrows > 0 && (!x || !r_a || !r_b || !w_a || !w_b || !t || (dinv && (!y_a || !y_b))))
+        return set_error(HPCLA_ERR_INVALID, "minres_iterations: null vector");
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(r_a) | reinterpret_cast<uintptr_t>(r_b) |
+         reinterpret_cast<uintptr_t>(w_a) | reinterpret_cast<uintptr_t>(w_b) | reinterpret_cast<uintptr_t>(t) |
+         reinterpret_cast<uintptr_t>(dinv) |
+         (dinv ? reinterpret_cast<uintptr_t>(y_a) | reinterpret_cast<uintptr_t>(y_b) : 0)) & 15)
+        return set_error(HPCLA_ERR_INVALID, "minres_iterations: vectors must be 16-byte aligned");
+    int64_t *state = reinterpret_cast<int64_t *>(static_cast<char *>(work) + hpcla_minres_work_bytes()) - 4;
+    double *rbuf[2] = {r_a, r_b}, *wbuf[2] = {w_a, w_b};
+    double *ybuf[2] = {dinv ? y_a : r_a, dinv ? y_b : r_b};
+    for (int64_t j = first_iter; j < first_iter + iters; ++j) {
+        const int cur = (int)((j - 1) & 1), nxt = (int)(j & 1);
+        int rc = spmv_dist_dot_impl<I>(split_fn, fused_fn, plan, comm, rowptr, colval, nzval, ybuf[cur], nrows, t, nrows, nnz,
+                                       index_base, interior, n_interior, boundary, n_boundary, scal_dev + MINRES_YT, dot_work,
+                                       stream, cols16, patterns);
+        if (rc) return rc;
+        rc = hpcla_minres_r_f64(comm, scal_dev, t, rbuf[cur], dinv, rbuf[nxt], dinv ? ybuf[nxt] : nullptr, nrows, j, state,
+                                hist_dev + 2 * j, work, stream);
+        if (rc) return rc;
+        rc = hpcla_minres_xw_f64(scal_dev, ybuf[cur], wbuf[cur], wbuf[nxt], x, nrows, j, state, stream);
+        if (rc) return rc;
+    }
+    return HPCLA_OK;
+}
+
+HPCLA_API int hpcla_minres_iterations_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int32_t *rowptr,
+                                              const int32_t *colval_split, const int16_t *cols16,
+                                              const hpcla_block_patterns_t *patterns, const double *nzval, int64_t nrows,
+                                              int64_t nnz, int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                              const int32_t *boundary_blocks, int64_t n_boundary, const double *dinv, double *x,
+                                              double *r_a, double *r_b, double *y_a, double *y_b, double *w_a, double *w_b,
+                                              double *t, double *hist_dev, double *scal_dev, void *dot_work, void *work,
+                                              int64_t first_iter, int iters, void *stream)
+{
+    return minres_iterations_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, comm, rowptr, colval_split, cols16, patterns,
+                                           nzval, nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks,
+                                           n_boundary, dinv, x, r_a, r_b, y_a, y_b, w_a, w_b, t, hist_dev, scal_dev, dot_work,
+                                           work, first_iter, iters, stream);
+}
+
+HPCLA_API int hpcla_minres_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int64_t *rowptr,
+                                              const int64_t *colval_split, const double *nzval, int64_t nrows, int64_t nnz,
+                                              int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                              const int32_t *boundary_blocks, int64_t n_boundary, const double *dinv, double *x,
+                                              double *r_a, double *r_b, double *y_a, double *y_b, double *w_a, double *w_b,
+                                              double *t, double *hist_dev, double *scal_dev, void *dot_work, void *work,
+                                              int64_t first_iter, int iters, void *stream)
+{
+    return minres_iterations_impl<int64_t>(spmv_split_i64, spmv_fused_i64, plan, comm, rowptr, colval_split, nullptr, nullptr,
+                                           nzval, nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks,
+                                           n_boundary, dinv, x, r_a, r_b, y_a, y_b, w_a, w_b, t, hist_dev, scal_dev, dot_work,
+                                           work, first_iter, iters, stream);
+}
+
 // ---- a chunk of gated GMRES(m) inner steps in ONE host call (the solver, hp.gmres) -----------------------------------
 // Right-preconditioned restarted GMRES with twice-applied classical Gram-Schmidt, K = identity (dinv == NULL: the SpMV reads
 // the basis column itself) or dinv .*.  Step k = first_iter .. first_iter + iters - 1 (1-based over the whole solve), column

@@ -1047,6 +1047,203 @@ __global__ __launch_bounds__(256) void lsqr_xw_kernel(const double *__restrict__
     }
 }
 
+// ---- gated MINRES steps (the solver hpcla_minres_iterations_*: A x = b for a symmetric, possibly indefinite A) -------------
+// Paige and Saunders' Lanczos recurrence with a positive definite diagonal preconditioner M = dinv .* (or the identity) and
+// NO vector normalised in memory: the Lanczos vectors r1, r2 stay unnormalised next to their M-norms oldb, beta, y = M r2 is
+// the SpMV's operand (r2 itself without M) and v = y / beta is never stored.  Two buffers each of r, w (and y with M) rotate by
+// pointer: rn overwrites r1 (its last use), yn the y of the iteration before, the new w overwrites w1.  Iteration j (1-based
+// over the whole solve); t = A y and yt = y.t are the SpMV's, ungated.  Bytes per row:
+//   minres_r   alfa = yt / (beta beta)                                                          read t, r1, r2, write rn   32
+//              rn = (t / beta - (alfa / beta) r2) - (beta / oldb) r1   (j = 1: no r1 term, r1 is only written: 24)
+//              [ yn = dinv .* rn ];  bb = rn.yn                                      with M: + read dinv, write yn         48
+//   step       one thread, behind bb's all-reduce:
+//              gate N  !(bb >= 0), or bb or alfa not finite       -> breakdown, done_iter = j - 1, no scalar is written
+//              beta' = sqrt(bb);  oldeps = epsln;  delta = cs dbar + sn alfa;  gbar = sn dbar - cs alfa
+//              epsln = sn beta';  dbar = (-cs) beta';  gamma = sqrt(gbar gbar + beta' beta')
+//              gate G  !(gamma > 0)                               -> breakdown, done_iter = j - 1, no scalar is written
+//              cs = gbar / gamma;  sn = beta' / gamma;  phi = cs phibar;  phibar = sn phibar
+//              pair = (phibar phibar, bb);  oldb = beta;  beta = beta'
+//              gate C  phibar phibar <= thr                       -> converged, done_iter = j
+//   minres_xw  w = ((y / oldb - oldeps w1) - delta w2) / gamma;  x = x + phi w        read y, w1, w2, x, write w, x        48
+//              (y and oldb are this iteration's operand and its norm: minres_r left both alone; still runs for done_iter == j)
+// 80 bytes per iteration next to the SpMV (96 with M: y is stored once so that xw does not read r2 and dinv, 8 bytes fewer than
+// forming v from them), two all-reduces [yt], [bb]; composed from dot / norm / scale / axpy it is 176 and two host read-backs.
+// beta' = 0 is the lucky termination: sn = 0, phibar = 0 and gate C ends the solve before anything is divided by beta'.
+// Divides, multiplies, adds, subtractions and square roots are rounded separately, in the order written.
+// The state is PCG's (done_iter, status, thr): thr = max(rtol sqrt(b.M b), atol)^2 as a double.
+// The scalars live in MINRES_SCALARS doubles at the slots of MinresSlot (comm_internal.h: the iterations loop in comm.hip names
+// yt's slot too; yt is the SpMV's, the others are read and written here).
+// Cache policy: t in minres_r (HPCLA_CG_NT bit 2: its last use) and x in minres_xw (bit 0) are not touched again within the
+// iteration and go non-temporally; r, y and w are re-read by the next SpMV or kernel.
+
+template <bool NTQ, bool PRECOND>
+__global__ __launch_bounds__(RT) void minres_r_kernel(const double *__restrict__ scal, const double *__restrict__ t,
+                                                      const double *__restrict__ r2, const double *__restrict__ dinv,
+                                                      double *__restrict__ r1, double *__restrict__ yn, int64_t n, int64_t iter,
+                                                      const int64_t *__restrict__ state, double *__restrict__ partial)
+{
+    if (state[1] != PCG_RUNNING) return;
+    const double beta = scal[MINRES_BETA];
+    const double alfa = scal[MINRES_YT] / (beta * beta);
+    const double a = alfa / beta;
+    const bool first = iter == 1;                                // no r1 term: r1 is only written
+    const double c = first ? 0.0 : beta / scal[MINRES_OLDB];
+    const int64_t n2 = n / 2;
+    const double2 *t2 = reinterpret_cast<const double2 *>(t);
+    const double2 *q2 = reinterpret_cast<const double2 *>(r2);
+    const double2 *d2 = reinterpret_cast<const double2 *>(dinv);
+    double2 *p2 = reinterpret_cast<double2 *>(r1);
+    double2 *y2 = reinterpret_cast<double2 *>(yn);
+    double acc = 0.0;
+    int64_t i = (int64_t)blockIdx.x * RT + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * RT;
+    for (; i < n2; i += stride) {
+        const double2 tv = NTQ ? nt_load2(t2 + i) : t2[i];
+        const double2 qv = q2[i];
+        double2 rn;
+        rn.x = tv.x / beta - a * qv.x;
+        rn.y = tv.y / beta - a * qv.y;
+        if (!first) {
+            const double2 pv = p2[i];
+            rn.x = rn.x - c * pv.x;
+            rn.y = rn.y - c * pv.y;
+        }
+        p2[i] = rn;
+        if (PRECOND) {
+            const double2 dv = d2[i];
+            double2 yv;
+            yv.x = dv.x * rn.x;
+            yv.y = dv.y * rn.y;
+            y2[i] = yv;
+            acc = acc + rn.x * yv.x;
+            acc = acc + rn.y * yv.y;
+        } else {
+            acc = acc + rn.x * rn.x;
+            acc = acc + rn.y * rn.y;
+        }
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t j = n - 1;
+        double rn = t[j] / beta - a * r2[j];
+        if (!first) rn = rn - c * r1[j];
+        r1[j] = rn;
+        double yv = rn;
+        if (PRECOND) {
+            yv = dinv[j] * rn;
+            yn[j] = yv;
+        }
+        acc = acc + rn * yv;
+    }
+    const double s = block_reduce<RED_SUM>(acc);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// the scalar step of iteration `iter` and its gates; yt and bb are global sums here.  pair is not all-reduced afterwards
+__device__ __forceinline__ void minres_step(double *scal, double *pair, int64_t iter, int64_t *state)
+{
+    const double beta = scal[MINRES_BETA], bb = scal[MINRES_BB];
+    const double alfa = scal[MINRES_YT] / (beta * beta);
+    if (!(bb >= 0.0 && lsqr_finite(bb) && lsqr_finite(alfa))) {  // gate N (a NaN fails bb >= 0)
+        state[0] = iter - 1;
+        state[1] = PCG_BREAKDOWN;
+        return;
+    }
+    const double cs = scal[MINRES_CS], sn = scal[MINRES_SN], dbar = scal[MINRES_DBAR], phibar = scal[MINRES_PHIBAR];
+    const double betan = sqrt(bb);
+    const double oldeps = scal[MINRES_EPSLN];
+    const double delta = cs * dbar + sn * alfa;
+    const double gbar = sn * dbar - cs * alfa;
+    const double epsln = sn * betan;
+    const double dbarn = (-cs) * betan;
+    const double gamma = sqrt(gbar * gbar + betan * betan);
+    if (!(gamma > 0.0)) {                                        // gate G: also catches a NaN gamma
+        state[0] = iter - 1;
+        state[1] = PCG_BREAKDOWN;
+        return;
+    }
+    const double csn = gbar / gamma;
+    const double snn = betan / gamma;
+    const double phi = csn * phibar;
+    const double phibarn = snn * phibar;
+    const double res2 = phibarn * phibarn;
+    scal[MINRES_ALFA] = alfa;
+    scal[MINRES_OLDEPS] = oldeps;
+    scal[MINRES_DELTA] = delta;
+    scal[MINRES_GBAR] = gbar;
+    scal[MINRES_EPSLN] = epsln;
+    scal[MINRES_DBAR] = dbarn;
+    scal[MINRES_GAMMA] = gamma;
+    scal[MINRES_CS] = csn;
+    scal[MINRES_SN] = snn;
+    scal[MINRES_PHI] = phi;
+    scal[MINRES_PHIBAR] = phibarn;
+    scal[MINRES_OLDB] = beta;
+    scal[MINRES_BETA] = betan;
+    pair[0] = res2;
+    pair[1] = bb;
+    if (res2 <= reinterpret_cast<const double *>(state)[2]) {    // gate C
+        state[0] = iter;
+        state[1] = PCG_CONVERGED;
+    }
+}
+
+// second stage of bb (reduce_stage2<RED_SUM>'s order), one workgroup; the step where no all-reduce follows (pair != NULL)
+__global__ __launch_bounds__(RT) void minres_r_stage2_kernel(const double *__restrict__ partial, int np, int64_t iter,
+                                                             int64_t *__restrict__ state, double *__restrict__ scal,
+                                                             double *__restrict__ pair)
+{
+    if (state[1] != PCG_RUNNING) return;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < np; i += RT) acc = acc + partial[i];
+    const double bb = block_reduce<RED_SUM>(acc);
+    if (threadIdx.x == 0) {
+        scal[MINRES_BB] = bb;
+        if (pair) minres_step(scal, pair, iter, state);
+    }
+}
+
+__global__ void minres_step_kernel(double *__restrict__ scal, double *__restrict__ pair, int64_t iter,
+                                   int64_t *__restrict__ state)
+{
+    if (threadIdx.x == 0 && state[1] == PCG_RUNNING) minres_step(scal, pair, iter, state);
+}
+
+template <bool NTX>
+__global__ __launch_bounds__(256) void minres_xw_kernel(const double *__restrict__ scal, const double *__restrict__ y,
+                                                        const double *__restrict__ w2, double *__restrict__ w1,
+                                                        double *__restrict__ x, int64_t n, int64_t iter,
+                                                        const int64_t *__restrict__ state)
+{
+    const int64_t status = state[1];
+    if (!(status == PCG_RUNNING || (status == PCG_CONVERGED && state[0] == iter))) return;
+    const double oldb = scal[MINRES_OLDB], oldeps = scal[MINRES_OLDEPS], delta = scal[MINRES_DELTA];
+    const double gamma = scal[MINRES_GAMMA], phi = scal[MINRES_PHI];
+    const int64_t n2 = n / 2;
+    const double2 *y2 = reinterpret_cast<const double2 *>(y);
+    const double2 *b2 = reinterpret_cast<const double2 *>(w2);
+    double2 *a2 = reinterpret_cast<double2 *>(w1);
+    double2 *x2 = reinterpret_cast<double2 *>(x);
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (; i < n2; i += stride) {
+        const double2 yv = y2[i], bv = b2[i];
+        double2 wv = a2[i];
+        double2 xv = NTX ? nt_load2(x2 + i) : x2[i];
+        wv.x = ((yv.x / oldb - oldeps * wv.x) - delta * bv.x) / gamma;
+        wv.y = ((yv.y / oldb - oldeps * wv.y) - delta * bv.y) / gamma;
+        xv.x = xv.x + phi * wv.x;
+        xv.y = xv.y + phi * wv.y;
+        a2[i] = wv;
+        if (NTX) nt_store2(xv, x2 + i); else x2[i] = xv;
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t j = n - 1;
+        const double wj = ((y[j] / oldb - oldeps * w1[j]) - delta * w2[j]) / gamma;
+        w1[j] = wj;
+        x[j] = x[j] + phi * wj;
+    }
+}
+
 // ---- gated GMRES(m) steps (the solver hpcla_gmres_iterations_*; right preconditioning, K = identity or dinv .*) ---------
 // Inner step k (1-based over the whole solve), column j = (k - 1) mod m, c = j + 1 basis columns V_0 .. V_j at pitch ldv (even,
 // so every column is 16-byte aligned); w = A z is the SpMV's, ungated (z is V_j without a preconditioner).  Classical
@@ -1906,6 +2103,63 @@ HPCLA_API int hpcla_lsqr_xw_f64(const double *scal_dev, const double *vh, double
     hipStream_t s = as_stream(stream);
     if (cg_nt_mask() & 1) lsqr_xw_kernel<true><<<ew_grid(n / 2), 256, 0, s>>>(scal_dev, vh, x, w, n, iter, state_dev);
     else lsqr_xw_kernel<false><<<ew_grid(n / 2), 256, 0, s>>>(scal_dev, vh, x, w, n, iter, state_dev);
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
+// scratch of the gated MINRES steps: one array of stage-1 partials, then the solve's state (its last 32 bytes)
+HPCLA_API int64_t hpcla_minres_work_bytes(void)
+{
+    return (int64_t)(MAX_PARTIALS + PCG_STATE_WORDS) * (int64_t)sizeof(double);
+}
+
+HPCLA_API int hpcla_minres_r_f64(hpcla_comm_t *comm, double *scal_dev, const double *t, const double *r2, const double *dinv,
+                                 double *r1, double *yn, int64_t n, int64_t iter, int64_t *state_dev, double *pair_out_dev,
+                                 void *work, void *stream)
+{
+    if (n < 0 || iter < 1) return set_error(HPCLA_ERR_INVALID, "minres_r: negative size or iteration < 1");
+    if (!scal_dev || !state_dev || !work) return set_error(HPCLA_ERR_INVALID, "minres_r: null scalars / state / work");
+    if (n > 0 && (!t || !r2 || !r1 || (dinv && !yn))) return set_error(HPCLA_ERR_INVALID, "minres_r: null vector");
+    if (n > 0 && (r1 == r2 || r1 == t || (dinv && (yn == r1 || yn == r2 || yn == t))))
+        return set_error(HPCLA_ERR_INVALID, "minres_r: the written vectors must not alias the others");
+    if (bicg_misaligned({t, r2, dinv, r1, dinv ? yn : nullptr}))
+        return set_error(HPCLA_ERR_INVALID, "minres_r: vectors must be 16-byte aligned");
+    double *partial = reinterpret_cast<double *>(work);
+    const int g = reduce_grid(n);
+    hipStream_t s = as_stream(stream);
+    const bool nt = cg_nt_mask() & 4;
+#define HPCLA_MINRES_R(NT, PC) minres_r_kernel<NT, PC><<<g, RT, 0, s>>>(scal_dev, t, r2, dinv, r1, yn, n, iter, state_dev, partial)
+    if (dinv) {
+        if (nt) HPCLA_MINRES_R(true, true); else HPCLA_MINRES_R(false, true);
+    } else {
+        if (nt) HPCLA_MINRES_R(true, false); else HPCLA_MINRES_R(false, false);
+    }
+#undef HPCLA_MINRES_R
+    HPCLA_CHECK_LAUNCH();
+    minres_r_stage2_kernel<<<1, RT, 0, s>>>(partial, g, iter, state_dev, scal_dev, comm ? nullptr : pair_out_dev);
+    HPCLA_CHECK_LAUNCH();
+    if (!comm) return HPCLA_OK;
+    const int rc = allreduce_on(comm, scal_dev + MINRES_BB, 1, 0, stream);
+    if (rc) return rc;
+    if (!pair_out_dev) return HPCLA_OK;
+    minres_step_kernel<<<1, 64, 0, s>>>(scal_dev, pair_out_dev, iter, state_dev);
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
+HPCLA_API int hpcla_minres_xw_f64(const double *scal_dev, const double *y, const double *w2, double *w1, double *x, int64_t n,
+                                  int64_t iter, const int64_t *state_dev, void *stream)
+{
+    if (n < 0 || iter < 1) return set_error(HPCLA_ERR_INVALID, "minres_xw: negative size or iteration < 1");
+    if (!scal_dev || !state_dev) return set_error(HPCLA_ERR_INVALID, "minres_xw: null scalars / state");
+    if (n == 0) return HPCLA_OK;
+    if (!y || !w2 || !w1 || !x) return set_error(HPCLA_ERR_INVALID, "minres_xw: null vector");
+    if (w1 == w2 || w1 == y || w1 == x || x == y || x == w2)
+        return set_error(HPCLA_ERR_INVALID, "minres_xw: the written vectors must not alias the others");
+    if (bicg_misaligned({y, w2, w1, x})) return set_error(HPCLA_ERR_INVALID, "minres_xw: vectors must be 16-byte aligned");
+    hipStream_t s = as_stream(stream);
+    if (cg_nt_mask() & 1) minres_xw_kernel<true><<<ew_grid(n / 2), 256, 0, s>>>(scal_dev, y, w2, w1, x, n, iter, state_dev);
+    else minres_xw_kernel<false><<<ew_grid(n / 2), 256, 0, s>>>(scal_dev, y, w2, w1, x, n, iter, state_dev);
     HPCLA_CHECK_LAUNCH();
     return HPCLA_OK;
 }
