@@ -1245,6 +1245,52 @@ int hpcla_gmres_restart_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, con
                                 int64_t n_boundary, const double *dinv, const double *b, const double *x, double *V,
                                 int64_t ldv, double *w, double *z, double *small_dev, double *hist_dev, void *work,
                                 int restart, int64_t iter, void *stream);
+/* ---- Extreme eigenpairs of a symmetric A: thick-restart Lanczos (Wu and Simon; Krylov-Schur for symmetric A) with full
+ * reorthogonalisation by twice-applied classical Gram-Schmidt (no reference counterpart: the reference has no eigensolver; a
+ * caller of its operators composes Lanczos from A*p, src/sparse.jl:2096-2128, dot, src/vectors.jl:798-812, and the broadcasts,
+ * src/vectors.jl:1203-1226: 2c dots, 2c axpys and 2c + 1 host read-backs in the step that orthogonalises against c columns,
+ * and the restart V[:, 0:p] = V[:, 0:m] * S as a dense product plus a copy back).
+ * The basis is the GMRES one: ncv + 1 columns of n doubles at an even pitch ldv >= n.  The step reuses gmres_dots, the first
+ * pass of gmres_update and gmres_next as they are; the state is the CG solver's (done_iter, status, thr [not used], reserved)
+ * with status 2 = breakdown and one more:
+ *   4 invariant: the new vector is exactly zero at done_iter, the Krylov space is invariant and its Ritz pairs are exact.
+ * The small arrays of a solve live in ONE buffer of hpcla_eigsh_small_offset(ncv, 6) doubles; the offset of each is
+ * hpcla_eigsh_small_offset(ncv, which), which = 0 .. 5:  T (ncv x ncv, column j at T + j*ncv: the projected matrix's upper
+ * triangle as the device computed it), beta (ncv), h1, h2 (the two passes' coefficients), nn (w.w), hn (the divisor of
+ * hpcla_gmres_next_f64).  -1 for ncv outside 1..64.  Scratch and state: hpcla_gmres_work_bytes(ncv) bytes.
+ *   eigsh_update    the second pass of column j = ncols - 1 at step iter (1-based over the solve): w = ((w - h_dev[0]*V_0) -
+ *                   h_dev[1]*V_1) - ..., nn = w.w, one all-reduce (comm != NULL), then by one thread:
+ *                     gate N  nn != nn:  status = 2, done_iter = iter - 1, nothing of column j is stored
+ *                     T[i, j] = h1[i] + h2[i] for i <= j;  beta[j] = hn = sqrt(nn)
+ *                     gate I  nn == 0:   status = 4, done_iter = iter (column j is stored)
+ *                   Once status != 0 it writes no byte with comm == NULL; with a communicator the all-reduce between the two
+ *                   gated launches still runs and rewrites nn (scratch: nothing reads it behind a stop), and nothing else.
+ *   eigsh_rotate    the restart, one pass over the basis (csrc/eigsh.hip).  S_dev: m x p, column j at S_dev + j*m.  Row r:
+ *                   acc = V[r,0]*S[0,j];  acc = acc + V[r,i]*S[i,j], i ascending, separately rounded.  out == NULL: in place,
+ *                   V[:, 0:p] = V[:, 0:m] * S (every lane loads its whole row before it stores), and column p receives old
+ *                   column m when move_last != 0; columns beyond, and the pad of an odd n, are untouched.  out != NULL
+ *                   (move_last must be 0): V is only read and the n x p product goes to out[r*out_row_stride +
+ *                   j*out_col_stride].  1 <= p <= m <= 64; V 16-byte aligned.  8 (m + p) + 16 bytes per row in place. */
+int64_t hpcla_eigsh_small_offset(int ncv, int which);
+int hpcla_eigsh_update_f64(hpcla_comm_t *comm, const double *V, int64_t ldv, int ncols, const double *h_dev, double *w,
+                           int64_t n, int64_t iter, int ncv, double *small_dev, int64_t *state_dev, void *work, void *stream);
+int hpcla_eigsh_rotate_f64(double *V, int64_t ldv, int m, int p, const double *S_dev, int move_last, double *out,
+                           int64_t out_row_stride, int64_t out_col_stride, int64_t n, void *stream);
+/* Columns first_col .. first_col + count - 1 of a cycle (steps first_iter .. of the solve) enqueued by ONE host call: per
+ * column j, w = A*V_j through hpcla_spmv_dist_* (always executed), gmres_dots into h1, gmres_update (first pass), gmres_dots
+ * into h2, eigsh_update, and gmres_next into column j + 1 (also at j + 1 == ncv).  The state lives in the last 32 bytes of
+ * work and is set up by the caller.  Everything else as for hpcla_gmres_iterations_*.  Only enqueues. */
+int hpcla_eigsh_steps_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int32_t *rowptr, const int32_t *colval_split,
+                              const int16_t *cols16, const hpcla_block_patterns_t *patterns, const double *nzval, int64_t nrows,
+                              int64_t nnz, int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                              const int32_t *boundary_blocks, int64_t n_boundary, double *V, int64_t ldv, double *w,
+                              double *small_dev, void *work, int ncv, int first_col, int count, int64_t first_iter,
+                              void *stream);
+int hpcla_eigsh_steps_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int64_t *rowptr, const int64_t *colval_split,
+                              const double *nzval, int64_t nrows, int64_t nnz, int index_base, const int32_t *interior_blocks,
+                              int64_t n_interior, const int32_t *boundary_blocks, int64_t n_boundary, double *V, int64_t ldv,
+                              double *w, double *small_dev, void *work, int ncv, int first_col, int count, int64_t first_iter,
+                              void *stream);
 int hpcla_divide_f64(const double *x, double a_host, double *y, int64_t n, void *stream);
 int hpcla_axpby_f64(double a, const double *x, double b, const double *y, double *z, int64_t n,
                     void *stream);

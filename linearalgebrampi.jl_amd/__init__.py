@@ -17,6 +17,8 @@ Layout
                      on the device (lsqr_* kernels)
   minres.py          minres(): MINRES for symmetric indefinite A, diagonal preconditioner, the same device-side stop in the M norm
                      (minres_* kernels)
+  eigsh.py           eigsh(): extreme eigenpairs of a symmetric A by thick-restart Lanczos on the GMRES kernels; the restart
+                     rotates the basis in place in one pass (csrc/eigsh.hip)
   indexing.py        v[a:b], X[r, c], A[r, c], A[:, k], diag(A) and SubmatrixPlan (csrc/submatrix.hip)
   transpose.py matmat.py addition.py repartition.py   the SURVEY 8f "next" rows and their plans
 
@@ -45,6 +47,7 @@ from .bicgstab import BiCGStabWorkspace, bicgstab
 from .gmres import GMRESWorkspace, gmres
 from .lsqr import LSQRInfo, LSQRWorkspace, lsqr
 from .minres import MinresWorkspace, minres
+from .eigsh import EigshInfo, EigshWorkspace, eigsh
 from .convert import to_backend
 from .transpose import (HostTransposeStructure, TransposedHPCSparseMatrix, TransposedHPCVector, TransposePlan,
                         DenseTransposeLists, HostSpmmTPlan, adjoint, clear_transpose_plan_cache, get_transpose_plan,

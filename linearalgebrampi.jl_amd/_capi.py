@@ -206,6 +206,14 @@ _SIGNATURES = {
                                     _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp],
     "hpcla_gmres_restart_f64_i64": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
                                     _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp],
+    # thick-restart Lanczos (hp.eigsh): the Lanczos second pass, the columns of a cycle, the restart's rotate (csrc/eigsh.hip)
+    "hpcla_eigsh_small_offset": [_i32, _i32],
+    "hpcla_eigsh_update_f64": [_vp, _vp, _i64, _i32, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp],
+    "hpcla_eigsh_rotate_f64": [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _i64, _i64, _i64, _vp],
+    "hpcla_eigsh_steps_f64_i32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp,
+                                  _vp, _vp, _i32, _i32, _i32, _i64, _vp],
+    "hpcla_eigsh_steps_f64_i64": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp,
+                                  _vp, _vp, _i32, _i32, _i32, _i64, _vp],
     "hpcla_colspace_work_bytes": [_i64],
     "hpcla_compress_columns_i32": [_vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
     "hpcla_compress_columns_i64": [_vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
@@ -318,6 +326,7 @@ _RESTYPES = {
     "hpcla_minres_work_bytes": _i64,
     "hpcla_gmres_work_bytes": _i64,
     "hpcla_gmres_small_offset": _i64,
+    "hpcla_eigsh_small_offset": _i64,
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -1592,3 +1592,76 @@ HPCLA_API int hpcla_gmres_restart_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t 
                                        nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks, n_boundary, dinv, b,
                                        x, V, w, z, small_dev, hist_dev, state, work, restart, iter, stream);
 }
+
+// ---- columns of a thick-restart Lanczos cycle in ONE host call (the eigensolver, hp.eigsh) ---------------------------------
+// Full reorthogonalisation by twice-applied classical Gram-Schmidt on the GMRES kernels.  Column j = first_col ..
+// first_col + count - 1 of a cycle of ncv columns, c = j + 1, step first_iter + (j - first_col) of the solve:
+//   1. w = A V_j                    hpcla_spmv_dist_* -- always executed, not gated
+//   2. h1 = V^T w                   hpcla_gmres_dots_f64
+//   3. w = w - V h1                 hpcla_gmres_update_f64, first pass
+//   4. h2 = V^T w                   the dots again
+//   5. w = w - V h2, nn = w.w       hpcla_eigsh_update_f64: one all-reduce [nn], the Lanczos small step, gates N and I
+//   6. V_{j+1} = w / hn             hpcla_gmres_next_f64, also at c == ncv: the basis has ncv + 1 columns
+// One rank: SpMV + 6 + 2 ceil(c / 8) launches per step, no read-back.  The host reads the small buffer once per cycle.
+template <typename I, typename F, typename G>
+static int eigsh_steps_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const I *rowptr, const I *colval,
+                            const int16_t *cols16, const hpcla_block_patterns *patterns, const double *nzval, int64_t nrows,
+                            int64_t nnz, int index_base, const int32_t *interior, int64_t n_interior, const int32_t *boundary,
+                            int64_t n_boundary, double *V, int64_t ldv, double *w, double *small_dev, void *work, int ncv,
+                            int first_col, int count, int64_t first_iter, void *stream)
+{
+    if (nrows < 0 || nnz < 0) return set_error(HPCLA_ERR_INVALID, "eigsh_steps: negative size");
+    if (ncv < 1 || ncv > 64) return set_error(HPCLA_ERR_INVALID, "eigsh_steps: ncv must be in 1..64");
+    if (first_col < 0 || count < 0 || first_col + count > ncv || first_iter < 1)
+        return set_error(HPCLA_ERR_INVALID, "eigsh_steps: columns outside 0..ncv-1 or first_iter < 1");
+    if (ldv < nrows || (ldv & 1)) return set_error(HPCLA_ERR_INVALID, "eigsh_steps: the pitch must be even and at least nrows");
+    if (!small_dev || !work) return set_error(HPCLA_ERR_INVALID, "eigsh_steps: null small arrays / work");
+    if (nrows > 0 && (!V || !w)) return set_error(HPCLA_ERR_INVALID, "eigsh_steps: null vector");
+    if ((reinterpret_cast<uintptr_t>(V) | reinterpret_cast<uintptr_t>(w)) & 15)
+        return set_error(HPCLA_ERR_INVALID, "eigsh_steps: vectors must be 16-byte aligned");
+    int64_t *state = reinterpret_cast<int64_t *>(static_cast<char *>(work) + hpcla_gmres_work_bytes(ncv)) - 4;
+    double *h1 = small_dev + hpcla_eigsh_small_offset(ncv, 2), *h2 = small_dev + hpcla_eigsh_small_offset(ncv, 3);
+    double *hn = small_dev + hpcla_eigsh_small_offset(ncv, 5);
+    for (int j = first_col; j < first_col + count; ++j) {
+        const int c = j + 1;
+        const int64_t k = first_iter + (j - first_col);
+        int rc = spmv_dist_impl<I>(split_fn, fused_fn, plan, rowptr, colval, nzval, V + (int64_t)j * ldv, nrows, w, nrows, nnz,
+                                   index_base, interior, n_interior, boundary, n_boundary, stream, nullptr, cols16, patterns);
+        if (rc) return rc;
+        rc = hpcla_gmres_dots_f64(comm, V, ldv, c, w, nrows, state, h1, work, stream);
+        if (rc) return rc;
+        rc = hpcla_gmres_update_f64(comm, V, ldv, c, h1, w, nrows, k, ncv, nullptr, nullptr, state, work, stream);
+        if (rc) return rc;
+        rc = hpcla_gmres_dots_f64(comm, V, ldv, c, w, nrows, state, h2, work, stream);
+        if (rc) return rc;
+        rc = hpcla_eigsh_update_f64(comm, V, ldv, c, h2, w, nrows, k, ncv, small_dev, state, work, stream);
+        if (rc) return rc;
+        rc = hpcla_gmres_next_f64(w, hn, nullptr, V + (int64_t)c * ldv, nullptr, nrows, state, stream);
+        if (rc) return rc;
+    }
+    return HPCLA_OK;
+}
+
+HPCLA_API int hpcla_eigsh_steps_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int32_t *rowptr,
+                                        const int32_t *colval_split, const int16_t *cols16, const hpcla_block_patterns_t *patterns,
+                                        const double *nzval, int64_t nrows, int64_t nnz, int index_base,
+                                        const int32_t *interior_blocks, int64_t n_interior, const int32_t *boundary_blocks,
+                                        int64_t n_boundary, double *V, int64_t ldv, double *w, double *small_dev, void *work,
+                                        int ncv, int first_col, int count, int64_t first_iter, void *stream)
+{
+    return eigsh_steps_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, comm, rowptr, colval_split, cols16, patterns, nzval,
+                                     nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks, n_boundary, V, ldv, w,
+                                     small_dev, work, ncv, first_col, count, first_iter, stream);
+}
+
+HPCLA_API int hpcla_eigsh_steps_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int64_t *rowptr,
+                                        const int64_t *colval_split, const double *nzval, int64_t nrows, int64_t nnz,
+                                        int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                        const int32_t *boundary_blocks, int64_t n_boundary, double *V, int64_t ldv, double *w,
+                                        double *small_dev, void *work, int ncv, int first_col, int count, int64_t first_iter,
+                                        void *stream)
+{
+    return eigsh_steps_impl<int64_t>(spmv_split_i64, spmv_fused_i64, plan, comm, rowptr, colval_split, nullptr, nullptr, nzval,
+                                     nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks, n_boundary, V, ldv, w,
+                                     small_dev, work, ncv, first_col, count, first_iter, stream);
+}

@@ -2352,6 +2352,109 @@ HPCLA_API int hpcla_gmres_finish_f64(const double *V, int64_t ldv, int ncols, in
     return hpcla_gmres_xupdate_f64(V, ldv, ncols, q.y, dinv, x, n, nullptr, stream);
 }
 
+// ---- the Lanczos step of hp.eigsh (thick-restart Lanczos, full CGS2 reorthogonalisation; hpcla_eigsh_steps_*) ---------------
+// Column j of a cycle of m = ncv columns, c = j + 1 basis columns, iter 1-based over the whole solve: w = A V_j (ungated),
+// gmres_dots, gmres_update (first pass), gmres_dots, then THIS second pass -- gmres_update_kernel<true> as it is, and the
+// Lanczos small step in place of the Givens one.  It keeps the projected matrix: T (m x m, column j at T + j*m), beta (m):
+//   N  nn != nn                         -> status 2 (breakdown), done_iter = iter - 1; nothing of column j is stored
+//   T[i, j] = h1[i] + h2[i], i <= j;  beta[j] = hn = sqrt(nn)
+//   I  nn == 0                          -> status 4 (invariant), done_iter = iter; column j is stored
+// gmres_next then writes V_{j+1} = w / hn (gated: not behind a stop).  Bytes per row and launches are the GMRES step's.
+constexpr int64_t EIGSH_INVARIANT = 4;
+
+struct EigshSmall {
+    double *T, *beta, *h1, *h2, *nn, *hn;                    // T: m x m;  beta, h1, h2: m;  nn, hn: 1
+};
+
+static void eigsh_small_offsets(int m, int64_t off[7])          // off[6]: the buffer's length
+{
+    const int64_t len[6] = {(int64_t)m * m, m, m, m, 1, 1};
+    off[0] = 0;
+    for (int i = 0; i < 6; ++i) off[i + 1] = off[i] + len[i];
+}
+
+static void eigsh_small_layout(int m, double *base, EigshSmall *q)
+{
+    int64_t off[7];
+    eigsh_small_offsets(m, off);
+    *q = EigshSmall{base + off[0], base + off[1], base + off[2], base + off[3], base + off[4], base + off[5]};
+}
+
+__device__ void eigsh_small_step(const EigshSmall &q, int j, int m, double nn, int64_t iter, int64_t *state)
+{
+    if (nn != nn) {                                              // gate N
+        state[0] = iter - 1;
+        state[1] = PCG_BREAKDOWN;
+        return;
+    }
+    double *Tj = q.T + (int64_t)j * m;
+    for (int i = 0; i <= j; ++i) Tj[i] = q.h1[i] + q.h2[i];
+    const double hn = sqrt(nn);
+    q.beta[j] = hn;
+    q.hn[0] = hn;
+    if (nn == 0.0) {                                             // gate I
+        state[0] = iter;
+        state[1] = EIGSH_INVARIANT;
+    }
+}
+
+// second stage of w.w, one workgroup; runs the small step where no all-reduce follows (gate != 0)
+__global__ __launch_bounds__(RT) void eigsh_update_stage2_kernel(const double *__restrict__ partial, int np, EigshSmall q, int j,
+                                                                 int m, int64_t iter, int gate, int64_t *__restrict__ state)
+{
+    if (state[1] != PCG_RUNNING) return;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < np; i += RT) acc = acc + partial[i];
+    const double nn = block_reduce<RED_SUM>(acc);
+    if (threadIdx.x == 0) {
+        q.nn[0] = nn;
+        if (gate) eigsh_small_step(q, j, m, nn, iter, state);
+    }
+}
+
+__global__ void eigsh_small_step_kernel(EigshSmall q, int j, int m, int64_t iter, int64_t *__restrict__ state)
+{
+    if (threadIdx.x == 0 && state[1] == PCG_RUNNING) eigsh_small_step(q, j, m, q.nn[0], iter, state);
+}
+
+// where the small arrays of hp.eigsh live in the solve's one buffer of doubles: which = 0 .. 5 for T, beta, h1, h2, nn, hn;
+// which = 6: the buffer's length
+HPCLA_API int64_t hpcla_eigsh_small_offset(int ncv, int which)
+{
+    if (ncv < 1 || ncv > GMRES_MAX_RESTART || which < 0 || which > 6) return -1;
+    int64_t off[7];
+    eigsh_small_offsets(ncv, off);
+    return off[which];
+}
+
+// the second pass of column j = ncols - 1: w = w - V h2, nn = w.w (one all-reduce), then the Lanczos small step with gates N, I
+HPCLA_API int hpcla_eigsh_update_f64(hpcla_comm_t *comm, const double *V, int64_t ldv, int ncols, const double *h_dev, double *w,
+                                     int64_t n, int64_t iter, int ncv, double *small_dev, int64_t *state_dev, void *work,
+                                     void *stream)
+{
+    if (gmres_bad_basis(n, ldv, ncols, ncv) || iter < 1)
+        return set_error(HPCLA_ERR_INVALID, "eigsh_update: negative size, odd or short pitch, bad column count or iteration < 1");
+    if (!h_dev || !state_dev || !small_dev || !work)
+        return set_error(HPCLA_ERR_INVALID, "eigsh_update: null coefficients / state / small arrays / work");
+    if (n > 0 && (!V || !w)) return set_error(HPCLA_ERR_INVALID, "eigsh_update: null vector");
+    if (bicg_misaligned({V, w})) return set_error(HPCLA_ERR_INVALID, "eigsh_update: vectors must be 16-byte aligned");
+    double *partial = reinterpret_cast<double *>(work);
+    const int g = reduce_grid(n);
+    hipStream_t s = as_stream(stream);
+    EigshSmall q;
+    eigsh_small_layout(ncv, small_dev, &q);
+    gmres_update_kernel<true><<<g, RT, 0, s>>>(V, ldv, ncols, h_dev, w, n, state_dev, partial);
+    HPCLA_CHECK_LAUNCH();
+    eigsh_update_stage2_kernel<<<1, RT, 0, s>>>(partial, g, q, ncols - 1, ncv, iter, comm ? 0 : 1, state_dev);
+    HPCLA_CHECK_LAUNCH();
+    if (!comm) return HPCLA_OK;
+    const int rc = allreduce_on(comm, q.nn, 1, 0, stream);
+    if (rc) return rc;
+    eigsh_small_step_kernel<<<1, 64, 0, s>>>(q, ncols - 1, ncv, iter, state_dev);
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
 // merge-combine: the five addition kernels of the reference (_copy_a_only_/_copy_b_only_/
 // _negate_b_only_/_add_both_/_sub_both_kernel!, src/sparse.jl:1258-1303) as ONE pass over the result:
 // entry i of the merged pattern takes a[ia[i]] (ia[i] >= 0) and/or b[ib[i]] (ib[i] >= 0); an entry that
