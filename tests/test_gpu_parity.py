@@ -691,7 +691,7 @@ def test_to_backend_round_trip(hp, orc, gpu_backend_i32):
     hp.clear_plan_cache()
 
 
-@pytest.mark.parametrize("k", [1, 2, 3, 4, 6, 8, 10, 12, 14, 16, 17, 18, 24, 40])
+@pytest.mark.parametrize("k", [1, 2, 3, 4, 6, 8, 10, 12, 14, 16, 17, 18, 24, 32, 40])
 @pytest.mark.parametrize("layout", ["row", "col"])
 def test_spmm_bit_exact_raw_abi(hp, orc, gpu_backend_i32, k, layout):
     import torch

@@ -473,3 +473,47 @@ def test_halo_plans_have_one_constructor(hp):
     assert dataclasses.is_dataclass(SpmmExchange) and not issubclass(SpmmExchange, tuple)
     assert not hasattr(SpmmExchange, "__getitem__") and not hasattr(SpmmExchange, "__iter__")
 
+
+
+# library switches (getenv in csrc/) that tests/test_gpu_kernel_variants.py's settings table does not carry: the test file that
+# sets the variable for a child process, or the reason why none does
+SWITCHES_COVERED_ELSEWHERE = {
+    "HPCLA_HALO_MODE": "tests/test_gpu_multirank.py",
+    "HPCLA_FORCE_RCCL": "tests/test_gpu_block_patterns.py",
+    "HPCLA_PUSH_TIMEOUT_S": "tests/test_gpu_multirank.py",
+    "HPCLA_WINDOW_ALLOC": "transport diagnostics: how a peer window is allocated, no kernel variant",
+    "HPCLA_WINDOW_DEFER_FREE": "transport diagnostics: when a peer window is freed, no kernel variant",
+}
+
+
+def test_every_library_switch_has_a_test_that_sets_it():
+    """Every name in a getenv("HPCLA_...") of csrc/*.hip and csrc/*.h is a variable of the kernel-variant children's settings
+    table or is listed above; every variable of the table -- and of the worker's family table -- is read by the sources, so
+    a typo or a renamed switch cannot make a child test nothing, and a new switch cannot land without a test."""
+    from tests import _kernel_variants_worker as worker
+    from tests import test_gpu_kernel_variants as variants
+    csrc = os.path.join(ROOT, "linearalgebrampi.jl_amd", "csrc")
+    read = {}
+    for fn in sorted(os.listdir(csrc)):
+        if fn.endswith((".hip", ".h")):
+            for name in re.findall(r'getenv\(\s*"(HPCLA_[A-Z0-9_]+)"', open(os.path.join(csrc, fn)).read()):
+                read.setdefault(name, fn)
+    assert len(read) >= 15, read
+    table = set(variants.TABLE_VARIABLES)
+    assert table == {v for fam in variants.FAMILY_SETTINGS.values() for setting in fam for v in setting}
+    assert not table & set(SWITCHES_COVERED_ELSEWHERE)
+    untested = {name: fn for name, fn in read.items() if name not in table and name not in SWITCHES_COVERED_ELSEWHERE}
+    assert not untested, f"switches that no test sets: {untested}"
+    assert table <= set(read), f"table variables that csrc/ never reads: {sorted(table - set(read))}"
+    assert set(SWITCHES_COVERED_ELSEWHERE) <= set(read), sorted(set(SWITCHES_COVERED_ELSEWHERE) - set(read))
+    # the worker names a failing check's family by these; the parent removes them all for the baseline
+    assert set(worker.FAMILY_VARIABLES) == set(variants.FAMILY_SETTINGS)
+    for family, names in worker.FAMILY_VARIABLES.items():
+        assert set(names) == {v for setting in variants.FAMILY_SETTINGS[family] for v in setting}, family
+    for name, where in SWITCHES_COVERED_ELSEWHERE.items():
+        if where.startswith("tests/"):
+            assert name in open(os.path.join(ROOT, where)).read(), (name, where)
+    # every child carries at most one setting of a family, and every setting of the table is carried by a child
+    carried = [s[f] for s in variants.SETTINGS for f in s]
+    assert sorted(map(str, carried)) == sorted(str(x) for fam in variants.FAMILY_SETTINGS.values() for x in fam)
+    assert len(variants.SETTINGS) == 7
