@@ -27,6 +27,7 @@ from tests import _pcg_cases as pc
 
 SIZES = pc.SIZES
 HEAD = 5                   # history entries compared with the restatement
+LARGE_SIZE = pc.LARGE_SIZE  # 65 x 63: the same head, HIST_RTOL is 30 times the CPU spread there (3.3e-14, with Jacobi)
 HIST_RTOL = 1e-12          # ... to this margin (basis: tests/test_gpu_bicgstab.py)
 HALF_SIZE, HALF_RTOL, HALF_ITERATIONS = (16, 16), 0.7, 8      # the half-step case
 HALF_HIST_RTOL = 1e-11     # its whole history: 45 times the CPU spread of four summation orders (2.2e-13, entry 7)

@@ -41,6 +41,7 @@ T_RTOL = 1e-12             # first-cycle T and beta against the restatement, rel
 VAL_RTOL = 1e-12           # eigenvalues against numpy.linalg.eigvalsh of the dense matrix, relative to anorm
 SPREAD = 1e-13             # bound on the CPU spread of T and of the eigenvalues over the four summation orders
 RANK_CASE = ("plain", (24, 20), 4, 20)
+LARGE_SIZE = pc.LARGE_SIZE  # 65 x 63, first cycle at ncv = 20: T_RTOL is 700 times the CPU spread of T and beta there (1.4e-15)
 
 
 def plain_poisson(orc, nx, ny):

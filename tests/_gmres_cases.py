@@ -41,6 +41,7 @@ SIZES = bc.SIZES
 RESTARTS = (30, 8)
 HEAD = 9                   # history entries compared with the restatement (restart = 5: the head crosses a restart)
 HEAD_RESTART = 5
+LARGE_SIZE = pc.LARGE_SIZE  # 65 x 63: the same head and restart, HIST_RTOL is 430 times the CPU spread there (2.3e-15)
 HIST_RTOL = 1e-12          # ... to this margin, the project's history margin; the CPU spread must stay below 1e-13
 RISE_RTOL = 1e-12          # the history never rises by more than this, relative
 

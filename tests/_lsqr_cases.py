@@ -27,6 +27,7 @@ from tests import _pcg_cases as pc
 SIZES = pc.SIZES
 DOTS = bc.DOTS
 HEAD = 13                  # history entries compared with the restatement
+LARGE_SIZE = pc.LARGE_SIZE  # 65 x 63, tall: 8190 x 4095; the same head, HIST_RTOL is 80 times the CPU spread there (1.2e-14)
 HIST_RTOL = 1e-12          # ... to this margin: 20 x the CPU spread of four summation orders (measured <= 7.1e-15)
 DAMPS = (0.0, 0.3)
 RANK_SIZE = (24, 20)       # the case of the history-head and rank tests

@@ -30,6 +30,7 @@ from tests import _pcg_cases as pc
 SIZES = pc.SIZES
 DOTS = bc.DOTS
 HEAD = 13                  # history entries compared with the restatement
+LARGE_SIZE = pc.LARGE_SIZE  # 65 x 63: 8190 rows stacked, 4095 shifted; the same head, HIST_RTOL is 90 times the spread (1.1e-14)
 HIST_RTOL = pc.CG_RTOL     # ... to the project's history margin, 1e-12 (the CPU spread of four summation orders: <= 1e-14)
 RANK_SIZE = (24, 20)       # the case of the history-head and rank tests: 960 rows
 SHIFT_SIZE = (33, 31)
@@ -95,6 +96,15 @@ def all_cases(orc):
     case = shifted(orc, *SHIFT_SIZE)
     out["shifted", SHIFT_SIZE, False] = (*case, None)
     out["shifted", SHIFT_SIZE, True] = (*case, jacobi(*case[:3]))
+    return out
+
+
+def large_cases(orc):
+    """[(name, (rowptr, colidx, vals, b), dinv)] at LARGE_SIZE: the three cases of the history-head test, no dense matrices."""
+    out = [("saddle", saddle(orc, *LARGE_SIZE), None)]
+    case = scaled_saddle(orc, *LARGE_SIZE)
+    out.append(("scaled_saddle", case, jacobi(*case[:3])))
+    out.append(("shifted", shifted(orc, *LARGE_SIZE), None))
     return out
 
 

@@ -23,6 +23,10 @@ SEED_SCALE = 0xD1A6
 SEED_RHS = 0xBEEF
 SIZES = [(16, 16), (24, 20), (33, 31)]
 HEAD = 13                  # history entries compared with the restatement
+# One case per solver above one reduction workgroup: 65 x 63 = 4095 rows is odd and gives two stage-1 partials (8190 rows of the
+# stacked cases: four).  Only the head of the history is compared there, and no dense matrix is built at this size.
+LARGE_SIZE = (65, 63)
+LARGE_MARGIN_FACTOR = 10   # a margin used at LARGE_SIZE is at least this many times the CPU spread of four summation orders
 
 
 def scaled_poisson(orc, nx, ny):
@@ -71,8 +75,9 @@ def bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
-def pcg(rowptr, colidx, vals, b, dinv=None, rtol=1e-8, atol=0.0, maxiter=None, x0=None):
-    """The solver's loop on the host.  Returns (x, iterations, status, residual_norms)."""
+def pcg(rowptr, colidx, vals, b, dinv=None, rtol=1e-8, atol=0.0, maxiter=None, x0=None, dot=np.dot):
+    """The solver's loop on the host.  Returns (x, iterations, status, residual_norms).  ``dot`` can be swapped for another
+    summation order (``_bicgstab_cases.DOTS``) to measure what the order alone does to the history."""
     n = len(b)
     maxiter = 10 * n if maxiter is None else maxiter
     A = lambda v: matvec(rowptr, colidx, vals, v)
@@ -81,8 +86,8 @@ def pcg(rowptr, colidx, vals, b, dinv=None, rtol=1e-8, atol=0.0, maxiter=None, x
     r = b.copy() if x0 is None else b - A(x)
     z = prec(r)
     p = z.copy()
-    rr, rz = float(np.dot(r, r)), float(np.dot(r, z))
-    bb = float(np.dot(b, b))
+    rr, rz = float(dot(r, r)), float(dot(r, z))
+    bb = float(dot(b, b))
     if bb == 0.0:
         return np.zeros(n), 0, "converged", [0.0]
     thr = max(rtol * math.sqrt(bb), atol) ** 2
@@ -91,13 +96,13 @@ def pcg(rowptr, colidx, vals, b, dinv=None, rtol=1e-8, atol=0.0, maxiter=None, x
         return x, 0, "converged", hist
     for j in range(1, maxiter + 1):
         Ap = A(p)
-        pAp = float(np.dot(p, Ap))
+        pAp = float(dot(p, Ap))
         if not (pAp > 0):                                   # gate A
             return x, j - 1, "breakdown", hist
         a = rz / pAp
         r = r - a * Ap
         z = prec(r)
-        rr, rz_new = float(np.dot(r, r)), float(np.dot(r, z))
+        rr, rz_new = float(dot(r, r)), float(dot(r, z))
         hist.append(math.sqrt(rr))
         converged = rr <= thr                               # gate B
         beta = rz_new / rz

@@ -13,6 +13,13 @@ Matrices (global CSR, columns ascending within a row, built once per process):
   p5     the 5-point matrix of a 96 x 96 grid (9 216 rows).
   band   70 001 rows, 3 entries per row: SCAN_CHUNK = 1 024 elements per workgroup of the scan (csrc/scan.h), so the row
          scan of the full range runs over 69 chunks and the column scan over as many.
+  band263537  the same band with BAND_LONG_ROWS = 263 537 rows (``band<n>`` is the band of n rows).  One workgroup scans the
+         chunks' sums 256 at a time and carries the running total from trip to trip, so the carry first matters beyond
+         256 * 1 024 = 262 144 scanned elements.  band_long_rows selects 262 157 rows (the row scan has one element more: 257
+         chunks, a second trip with one live lane) and cuts them to columns 150 000 .. 262 999, so the chunks of the first
+         trip hold none, some or 3 072 entries and those of the second some: a carry from the wrong trip shows in rowptr.
+         band_long_cols selects columns 7 .. 263 499 (263 493 wide: 258 chunks) of rows 259 000 .. 263 536, so the columns
+         that occur lie on both sides of the first carry and most chunks are empty.
 """
 import functools
 
@@ -21,6 +28,10 @@ import numpy as np
 SCAN_CHUNK = 1024
 BAND_ROWS = 68 * SCAN_CHUNK + 369            # 70 001: several chunks, and not a multiple of one
 assert BAND_ROWS == 70001
+SCAN_TRIP = 256 * SCAN_CHUNK                 # elements whose chunk sums one trip of the scan's second phase covers
+BAND_LONG_ROWS = SCAN_TRIP + SCAN_CHUNK + 369
+BAND_LONG = f"band{BAND_LONG_ROWS}"
+assert BAND_LONG_ROWS == 263537
 
 NR, NC = 3000, 5000
 GAP_LO, GAP_HI = 2000, 2010
@@ -57,8 +68,8 @@ def matrix(key: str) -> CSR:
         return A.with_values(rng.uniform(-1.0, 1.0, len(A.data)))
     if key == "p5":
         return _five_point(96, 96)
-    if key == "band":
-        return _band(BAND_ROWS)
+    if key.startswith("band"):
+        return _band(BAND_ROWS if key == "band" else int(key[4:]))
     raise KeyError(key)
 
 
@@ -129,6 +140,8 @@ CASES = (
         ("p5_odd", "p5", 97, 4100, 191, 4007),
         ("band_all", "band", 0, BAND_ROWS, 0, BAND_ROWS),                     # 70 001 selected rows: 69 scan chunks
         ("band_mid", "band", 1023, 66000, 1024, 65999),
+        ("band_long_rows", BAND_LONG, 5, 5 + SCAN_TRIP + 13, 150_000, 263_000),     # 262 157 selected rows: 257 scan chunks
+        ("band_long_cols", BAND_LONG, 259_000, BAND_LONG_ROWS, 7, 263_500),         # 263 493 columns: 258 scan chunks
     ]
 )
 COLUMN_CASES = (            # (name, matrix, k)

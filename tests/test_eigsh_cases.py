@@ -236,3 +236,23 @@ def test_restatement_on_the_exact_cases():
     got, X, info = ec.eigsh(*pc.diag_matrix(np.arange(1.0, 61.0)), k=4, ncv=20, maxiter=5)       # maxiter inside the first cycle
     assert (info["status"], info["converged"], info["iterations"], info["restarts"]) == ("maxiter", False, 20, 0)
     assert len(info["history"]) == 1 and got.shape == (4,) and X.shape == (60, 4)
+
+
+def test_first_cycle_spread_at_the_large_size(orc):
+    """Plain Poisson at 65 x 63 (4095 rows, two reduction workgroups on the device), ncv = 20, one cycle: T and beta under the
+    four summation orders.  T_RTOL, which tests/test_gpu_eigsh.py asks there, must be at least 10 times the spread relative to
+    max|T| (measured: T 1.3e-15, beta 1.4e-15: 700 times)."""
+    rowptr, colidx, vals = ec.plain_poisson(orc, *ec.LARGE_SIZE)
+    assert len(rowptr) - 1 == 4095
+    Ts, betas = [], []
+    for dot in bc.DOTS.values():
+        first = {}
+        _, _, info = ec.eigsh(rowptr, colidx, vals, k=4, ncv=20, maxiter=1, dot=dot, first_T=first)
+        assert (info["status"], info["iterations"], info["restarts"]) == ("maxiter", 20, 0)
+        Ts.append(np.triu(first["T"]))
+        betas.append(first["beta"])
+    scale = np.abs(Ts[0]).max()
+    sT = (np.max(Ts, axis=0) - np.min(Ts, axis=0)).max() / scale
+    sb = (np.max(betas, axis=0) - np.min(betas, axis=0)).max() / scale
+    print(f"plain {ec.LARGE_SIZE}: first-cycle T spread {sT:.1e}, beta {sb:.1e} (relative to max|T| = {scale:.3g})")
+    assert pc.LARGE_MARGIN_FACTOR * max(sT, sb) <= ec.T_RTOL

@@ -15,6 +15,8 @@ import os
 import numpy as np
 import pytest
 
+from tests import _grid_regimes as gr
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
 
@@ -281,8 +283,14 @@ def test_spmm_split_f32_with_widened_ghost_rows(hp, orc, k, ldb, ldg, ldc):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", [0, 1, 3, 4, 1023, 1024, 1025, 1_000_003])
+@pytest.mark.parametrize("n", gr.F32_ALONE)
 def test_reductions_and_updates_f32(hp, n):
+    """The float32 reductions take four floats per lane and load on a grid of ceil(floor(n / 4) / 1024) workgroups, at most 1024
+    (csrc/f32.hip; tests/_grid_regimes.py restates it and tests/test_grid_regimes.py checks that these sizes reach every
+    regime): up to 1025 one workgroup, with tails of 0 to 3 floats; 1 000 003 gives 245 partials (one trip of the second stage
+    with idle lanes); 1 228 807 gives 301 (a second, ragged trip of 45 lanes) and a tail of three; 4 194 307 caps the grid at
+    1024 workgroups, each lane in four grid-stride trips, with a tail of three.  The updates' grid is ceil(floor(n / 4) / 256)
+    capped at 8192, which 4 194 307 fills in one trip."""
     import torch
     rng = np.random.default_rng(n)
     x = (rng.random(n) - 0.5).astype(F32)

@@ -7,7 +7,8 @@ Margins (none of them taken from the device's results; tests/test_eigsh_cases.py
     rounded expressions (the library is built with -ffp-contract=off; IEEE sqrt);
   * nn = w.w: 1e-12 of math.fsum relative to the sum of |terms|, the project's margin for its reductions;
   * the first cycle's T and beta: T_RTOL = 1e-12 of max|T|, the project's margin (four summation orders on the CPU spread by
-    <= 1.1e-15 of max|T|, 2.9e-15 absolute on this case: about 300 times less; the bound on that spread is 1e-13);
+    <= 1.1e-15 of max|T|, 2.9e-15 absolute on this case: about 300 times less; the bound on that spread is 1e-13; at 65 x 63
+    they spread by <= 1.4e-15 of max|T|: 700 times less);
   * eigenvalues: VAL_RTOL = 1e-12 of anorm against numpy.linalg.eigvalsh of the dense matrix (the restatement: <= 1.7e-14,
     its spread over the four orders <= 1.3e-14);
   * step counts: within one cycle's m - p steps of the restatement's (identical across the four orders on the CPU);
@@ -24,6 +25,7 @@ import pytest
 
 from tests import _eigsh_cases as ec
 from tests import _gmres_cases as gc
+from tests import _grid_regimes as gr
 from tests import _pcg_cases as pc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -167,10 +169,14 @@ class _Alone:
                                                self.m, small.data_ptr(), st.data_ptr(), self.work.data_ptr(), None) == 0
 
 
-@pytest.mark.parametrize("n,c", [(n, c) for n in (1, 2, 515, 2049, 2051) for c in (1, 8, 9, 17, 31)])
+@pytest.mark.parametrize("n,c", gr.EIGSH_UPDATE_ALONE)
 def test_lanczos_second_pass_alone(hp, n, c):
     """The (n, c) edges of tests/test_gpu_gmres.py: 2049 is the last size on one reduction workgroup with a scalar tail, 2051 the
-    first odd size on two; c = 8 | 9 is the edge of the 4-fold unrolled column loop and 17, 31 leave remainders of it."""
+    first odd size on two; c = 8 | 9 is the edge of the 4-fold unrolled column loop and 17, 31 leave remainders of it.
+    614 403 (c = 1 and 9) is odd with 301 partials: eigsh_update_stage2 walks them in two trips of 256 lanes, the last one ragged
+    (45 lanes), and gmres_update<true> runs on 301 workgroups; 4 194 307 (c = 9: the basis is (c + 1) n doubles) caps that grid at
+    2048 workgroups of five grid-stride trips, eight full trips of the second stage, and is odd.  tests/_grid_regimes.py holds the
+    sizes, tests/test_grid_regimes.py checks that they reach every regime."""
     import torch
     K = _Alone(hp, n, c)
     rng = np.random.default_rng(1000 * c + n % 1000)
@@ -250,6 +256,30 @@ def test_first_cycle_matches_the_restatement(hp, cases, gpu_backend_i32, gpu_bac
     print(f"{which}: first-cycle T deviation {dT:.2e}, beta {db:.2e} (relative to max|T| = {scale:.3g})")
     assert dT <= ec.T_RTOL and db <= ec.T_RTOL
     assert not np.tril(T, -1).any()                                                       # only the upper triangle is written
+    hp.clear_plan_cache()
+
+
+def test_first_cycle_at_the_large_size(hp, orc, gpu_backend_i32):
+    """Plain Poisson at 65 x 63: 4095 rows, odd, so both passes of every Lanczos step run on two stage-1 workgroups and
+    eigsh_update_stage2 adds two partials (the other solves of this file stay on one).  ncv = 20, one cycle: T and beta within
+    T_RTOL = 1e-12 of max|T|, 700 times the spread of four summation orders on the CPU at this size (T 1.3e-15, beta 1.4e-15;
+    tests/test_eigsh_cases.py re-measures both).  No convergence is asserted here."""
+    rowptr, colidx, vals = ec.plain_poisson(orc, *ec.LARGE_SIZE)
+    n, m = len(rowptr) - 1, 20
+    A = _matrix(hp, gpu_backend_i32, rowptr, colidx, vals)
+    first = {}
+    _, _, ref = ec.eigsh(rowptr, colidx, vals, k=4, ncv=m, maxiter=1, first_T=first)
+    ws = hp.EigshWorkspace(hp.HPCVector.from_global(np.zeros(n), gpu_backend_i32), m)
+    _, _, info = hp.eigsh(A, k=4, ncv=m, maxiter=1, workspace=ws)
+    assert (info.status, info.iterations, info.restarts) == ("maxiter", m, 0) == (ref["status"], ref["iterations"], ref["restarts"])
+    T = ws.small_array("T").cpu().numpy().reshape(m, m).T
+    beta = ws.small_array("beta").cpu().numpy()
+    scale = np.abs(first["T"]).max()
+    dT = np.abs(np.triu(T) - np.triu(first["T"])).max() / scale
+    db = np.abs(beta - first["beta"]).max() / scale
+    print(f"{ec.LARGE_SIZE}: first-cycle T deviation {dT:.2e}, beta {db:.2e} (relative to max|T| = {scale:.3g})")
+    assert dT <= ec.T_RTOL and db <= ec.T_RTOL
+    assert not np.tril(T, -1).any()
     hp.clear_plan_cache()
 
 

@@ -9,7 +9,8 @@ Margins (none of them taken from the device's results; tests/test_lsqr_cases.py 
   * the two sums: 1e-12 of math.fsum relative to the sum of |terms| (n <= 4.2e6 terms in a two-stage tree of doubles; the
     project's margin for its reductions);
   * histories: HIST_RTOL = 1e-12 on the first HEAD = 13 entries of both: four summation orders on the CPU spread by <= 7.1e-15
-    there (140 times less); the tail of normal_residual_norms is rounding-dominated near the stop and is not compared;
+    there (140 times less), and by <= 1.2e-14 over the same head of the tall case at 65 x 63 (80 times less); the tail of
+    normal_residual_norms is rounding-dominated near the stop and is not compared;
   * iteration counts: +-2 of the restatement's (identical across those orders except wide 16x16, 90-91);
   * x against numpy.linalg.lstsq on the dense augmented system: 1e-6 relative (restatement <= 1.8e-7); the true residual
     <= 2 rtol |b| where rule 1 stopped, the true normal residual <= 2 ntol |Abar|_F |rbar| where rule 2 stopped.
@@ -21,6 +22,7 @@ import numpy as np
 import pytest
 
 from tests import _bicgstab_cases as bc
+from tests import _grid_regimes as gr
 from tests import _lsqr_cases as lc
 from tests import _pcg_cases as pc
 
@@ -61,13 +63,16 @@ def _sum_err(got, terms):
     return abs(got - math.fsum(terms.tolist())) / float(np.abs(terms).sum())
 
 
-@pytest.mark.parametrize("n", [1, 2, 511, 515, 2049, 2051, 4194307])
+@pytest.mark.parametrize("n", gr.LSQR_ALONE)
 def test_gated_kernels_alone(hp, n):
     """The reductions (lsqr_u, lsqr_v) use the grid of the existing stage-1 reductions, ceil(floor(n / 2) / 1024) capped at
     2048: 2049 is the last size on one workgroup with a scalar tail, 2051 the first odd size on two, 4 194 307 =
     2 * 256 * 4 * 2048 + 3 caps the grid and is odd.  The elementwise kernel (lsqr_xw) uses ceil(floor(n / 2) / 256) capped at
     4096: 511 is the last odd size on one workgroup, 515 the first on two, and the largest size makes every thread stride
-    twice.  These are the sizes of test_gated_kernels_alone in tests/test_gpu_bicgstab.py: the grids are the same."""
+    twice.  614 403 is odd with 301 partials: the gated second stages walk them in two trips of 256 lanes, the last one ragged
+    (45 lanes), and lsqr_xw has 1201 workgroups.  These are the sizes of test_gated_kernels_alone in
+    tests/test_gpu_bicgstab.py: the grids are the same (tests/_grid_regimes.py holds the sizes, tests/test_grid_regimes.py
+    checks that they reach every regime)."""
     import torch
     lib = hp._capi.load()
     rng = np.random.default_rng(n)
@@ -228,6 +233,27 @@ def test_history_heads_match_the_restatement(hp, cases, gpu_backend_i32, gpu_bac
                        for g, w_ in zip(got[:lc.HEAD], want[:lc.HEAD]))
             print(f"{which} {kind} damp {damp}: head deviation {head:.2e}")
             assert head <= lc.HIST_RTOL, (kind, damp, head)
+    hp.clear_plan_cache()
+
+
+def test_history_heads_at_the_large_size(hp, orc, gpu_backend_i32):
+    """The tall case at 65 x 63: 8190 x 4095, so lsqr_u runs on four stage-1 workgroups and lsqr_v, over an odd length, on two,
+    and the gated second stages add four and two partials (the other solves of this file stay on one).  The first HEAD = 13
+    entries of both histories within HIST_RTOL = 1e-12: 80 times the spread of four summation orders on the CPU at this size
+    (1.2e-14 at damp 0, 1.0e-14 at damp 0.3; tests/test_lsqr_cases.py re-measures both).  No convergence or count is asserted."""
+    case = lc.tall(orc, *lc.LARGE_SIZE)
+    A = _matrix(hp, gpu_backend_i32, *case[:4])
+    b = hp.HPCVector.from_global(case[4], gpu_backend_i32)
+    for damp in lc.DAMPS:
+        _, its_ref, status_ref, hr, hn, _ = lc.lsqr(*case, damp=damp, rtol=0.0, ntol=0.0, maxiter=lc.HEAD)
+        assert (its_ref, status_ref, len(hr), len(hn)) == (lc.HEAD, "maxiter", lc.HEAD + 1, lc.HEAD + 1)
+        x, info = hp.lsqr(A, b, damp=damp, rtol=0.0, ntol=0.0, maxiter=lc.HEAD)
+        assert (info.iterations, info.status, info.converged) == (lc.HEAD, "maxiter", False)
+        assert len(info.residual_norms) == len(info.normal_residual_norms) == lc.HEAD + 1
+        head = max(abs(g - w_) / w_ for got, want in ((info.residual_norms, hr), (info.normal_residual_norms, hn))
+                   for g, w_ in zip(got[:lc.HEAD], want[:lc.HEAD]))
+        print(f"tall {lc.LARGE_SIZE} damp {damp}: head deviation {head:.2e}")
+        assert head <= lc.HIST_RTOL, (damp, head)
     hp.clear_plan_cache()
 
 

@@ -10,7 +10,7 @@ Margins (none of them taken from the device's results; tests/test_minres_cases.p
   * the sum bb: 1e-12 of math.fsum relative to the sum of |terms| (a two-stage tree of doubles in reduce_stage1's grid and
     order; the project's margin for its reductions);
   * history: HIST_RTOL = 1e-12 (the project's history margin) on the first HEAD = 13 entries: four summation orders on the CPU
-    spread by <= 5.6e-15 there (180 times less);
+    spread by <= 5.6e-15 there (180 times less), and by <= 1.1e-14 over the same head at 65 x 63 (90 times less);
   * iteration counts: within the fewest and the most of those four orders (``_minres_cases.EXPECTED``), 2 more either way;
   * x against numpy.linalg.solve: 10 times the restatement's own error on the same case (one more summation order); the true
     residual in the tested norm, sqrt(r . M r) <= 2 max(rtol sqrt(b . M b), atol) (the restatement: <= 0.97 of the limit).
@@ -21,6 +21,7 @@ import os
 import numpy as np
 import pytest
 
+from tests import _grid_regimes as gr
 from tests import _minres_cases as mc
 from tests import _pcg_cases as pc
 
@@ -63,11 +64,17 @@ def _solve(hp, backend, case, **kw):
 
 # ---- 1. the kernels on their own ----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("precond", [False, True])
-@pytest.mark.parametrize("n", [1, 2, 3, 1023, 2046])
+@pytest.mark.parametrize("n", gr.MINRES_ALONE)
 def test_gated_kernels_alone(hp, n, precond):
-    """n = 1: the scalar tail alone; 2: one double2 and no tail; 3: both; 1023: a body and a tail on one workgroup of either
-    kernel (the grids are ceil(floor(n / 2) / 1024) and ceil(floor(n / 2) / 256)); 2046: no tail, four workgroups of the
-    elementwise kernel."""
+    """The grids are ceil(floor(n / 2) / 1024) capped at 2048 for minres_r, whose partials minres_r_stage2 walks 256 at a time,
+    and ceil(floor(n / 2) / 256) capped at 4096 for minres_xw (tests/_grid_regimes.py restates both and
+    tests/test_grid_regimes.py checks that these sizes reach every regime).
+    n = 1: the scalar tail alone; 2: one double2 and no tail; 3: both; 1023: a body and a tail on one workgroup of minres_r and
+    two of minres_xw; 2046: no tail, one workgroup of minres_r and four of minres_xw; 2049: the last odd size on one workgroup of
+    minres_r; 2051: two partials, so the first size at which minres_r_stage2 adds anything; 614 403: 301 partials, a second and
+    ragged trip (45 lanes) of minres_r_stage2, 1201 workgroups of minres_xw; 4 194 307: 2048 partials, eight full trips of
+    minres_r_stage2, five grid-stride trips in minres_r, minres_xw capped at 4096 workgroups with a third trip; all four odd.
+    Every phase of the body runs at every size: the whole body takes 0.9 s at the largest (measured on the MI355X)."""
     import torch
     lib = hp._capi.load()
     rng = np.random.default_rng(n)
@@ -203,6 +210,23 @@ def test_history_heads_match_the_restatement(hp, cases, gpu_backend_i32, gpu_bac
         head = max(abs(g - w_) / w_ for g, w_ in zip(info.residual_norms[:mc.HEAD], hist_ref[:mc.HEAD]))
         print(f"{which} {key}: head deviation {head:.2e}")
         assert head <= mc.HIST_RTOL, (key, head)
+    hp.clear_plan_cache()
+
+
+def test_history_heads_at_the_large_size(hp, orc, gpu_backend_i32):
+    """65 x 63: 8190 rows for the two saddle cases (minres_r on four stage-1 workgroups, minres_r_stage2 adding four partials)
+    and 4095, odd, for the shifted one (two); the other solves of this file stay on one.  The first HEAD = 13 entries within
+    HIST_RTOL = 1e-12: 90 times the spread of four summation orders on the CPU at this size (saddle 6.3e-15, scaled saddle
+    1.1e-14, shifted 9.1e-15; tests/test_minres_cases.py re-measures them).  No convergence or count is asserted here."""
+    for name, case, dinv in mc.large_cases(orc):
+        _, its_ref, status_ref, hist_ref = mc.minres(*case, dinv=dinv, rtol=0.0, maxiter=mc.HEAD)
+        assert (its_ref, status_ref, len(hist_ref)) == (mc.HEAD, "maxiter", mc.HEAD + 1)
+        x, info = _solve(hp, gpu_backend_i32, (*case, dinv), rtol=0.0, maxiter=mc.HEAD)
+        assert (info.iterations, info.status, info.converged) == (mc.HEAD, "maxiter", False)
+        assert len(info.residual_norms) == mc.HEAD + 1
+        head = max(abs(g - w_) / w_ for g, w_ in zip(info.residual_norms[:mc.HEAD], hist_ref[:mc.HEAD]))
+        print(f"{name} {mc.LARGE_SIZE}: head deviation {head:.2e}")
+        assert head <= mc.HIST_RTOL, (name, head)
     hp.clear_plan_cache()
 
 

@@ -17,6 +17,8 @@ import sys
 import numpy as np
 import pytest
 
+from tests import _grid_regimes as gr
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL_REF = 1e-10      # reference absolute tolerance on its O(10) fixtures
@@ -172,6 +174,52 @@ def test_spmv_whole_pass_rows_split_and_dot_epilogue(hp, orc, Ti):
         assert abs(out.item() - ref) <= 1e-12 * float(np.abs(x) @ np.abs(want))
     finally:
         pass
+
+
+@pytest.mark.parametrize("nblk", gr.PARTIAL_BLOCKS)
+@pytest.mark.parametrize("Ti", [np.int32, np.int64])
+def test_spmv_dot_epilogue_at_the_branch_of_the_partial_sums(hp, orc, Ti, nblk):
+    """The x.y epilogue of the fused SpMV leaves one partial per row block, which reduce_partials_sum adds in one stage up to
+    4 * 256 = 1024 partials and in two above.  Row counts, with rpb rows per block: 1024 rpb is the last one-stage count (four
+    full trips of the one workgroup); 1024 rpb + 1 the first two-stage count: 1025 partials, so one stage-1 workgroup whose
+    lane 0 adds the odd last partial as the scalar tail; 2051 rpb + 1 gives 2052 partials on two stage-1 workgroups
+    (tests/test_grid_regimes.py checks these counts against the branch).  A tridiagonal matrix with seeded random values, so
+    every block's partial differs from the others; raw ABI, no plan and no block lists.  y: the oracle's bits; x.y: the project's
+    margin for its reductions against math.fsum, relative to the sum of |x_i y_i|; two runs: the same bits."""
+    import torch
+    lib = hp._capi.load()
+    rpb = lib.hpcla_spmv_rows_per_block()
+    n = (nblk - 1) * rpb + (rpb if nblk == gr.PARTIAL_BLOCKS[0] else 1)
+    assert (n + rpb - 1) // rpb == nblk
+    rng = np.random.default_rng(1000 + nblk)
+    lens = np.full(n, 3, dtype=np.int64)
+    lens[0] = lens[-1] = 2
+    rowptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    cols = (np.repeat(np.arange(n, dtype=np.int64), 3) + np.tile(np.array([-1, 0, 1], dtype=np.int64), n))[1:-1]
+    vals = rng.standard_normal(len(cols))
+    x = rng.standard_normal(n)
+    want = orc.spmv(rowptr.astype(Ti), cols.astype(Ti), vals, x)
+    terms = x * want
+    blocks = np.add.reduceat(terms, np.arange(0, n, rpb))
+    assert len(blocks) == nblk and len(np.unique(blocks)) == nblk
+    sfx = "i32" if Ti == np.int32 else "i64"
+    s = torch.cuda.current_stream().cuda_stream
+    rp, cv, nz, xs = _t(rowptr.astype(Ti)), _t(cols.astype(Ti)), _t(vals), _t(x)
+    work = torch.empty(lib.hpcla_spmv_dot_work_bytes(n) // 8 + 1, dtype=torch.float64, device="cuda")
+    got = []
+    for _ in range(2):
+        y = torch.full((n,), float("nan"), dtype=torch.float64, device="cuda")
+        out = torch.full((1,), float("nan"), dtype=torch.float64, device="cuda")
+        work.fill_(float("nan"))
+        hp._capi.call(f"hpcla_spmv_dist_dot_f64_{sfx}", None, None, rp.data_ptr(), cv.data_ptr(), nz.data_ptr(), xs.data_ptr(), n,
+                      y.data_ptr(), n, len(vals), 0, None, 0, None, 0, out.data_ptr(), work.data_ptr(), s)
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(y.cpu().numpy(), want)
+        got.append(out.item())
+    err = abs(got[0] - math.fsum(terms.tolist())) / float(np.abs(terms).sum())
+    print(f"{sfx}, {nblk} partials: x.y off by {err:.2e} of the sum of |terms|")
+    assert err <= RTOL_RED
+    assert np.float64(got[0]).view(np.uint64) == np.float64(got[1]).view(np.uint64)
 
 
 @pytest.mark.parametrize("Ti", [np.int32, np.int64])
@@ -549,7 +597,9 @@ def test_dot_norm_golden_and_random(hp, orc, golden, gpu_backend_i32):
     assert abs(hp.norm(v, 3) - nm["norm3"]) < TOL_REF and abs(hp.norm(v, 1.5) - nm["norm1p5"]) < TOL_REF
     with pytest.raises(ValueError):
         hp.norm(v, -1)
-    for n in (1, 2, 3, 511, 512, 513, 100_003, 4_000_001):
+    # 100 003: 49 partials; 4 000 001: 1954, a ragged eighth trip of reduce_stage2; 4 194 307: the cap of 2048 workgroups, each
+    # lane in four grid-stride trips and lane 0 in a fifth, and odd (tests/_grid_regimes.py, tests/test_grid_regimes.py)
+    for n in gr.PLAIN_F64:
         xg, yg = orc.fill_uniform(0, n, 1) - 0.5, orc.fill_uniform(0, n, 2) - 0.25
         xv, yv = hp.HPCVector.from_global(xg, b), hp.HPCVector.from_global(yg, b)
         scale = float(np.abs(xg) @ np.abs(yg))
@@ -571,9 +621,12 @@ def test_dot_norm_golden_and_random(hp, orc, golden, gpu_backend_i32):
     assert hp.dot(xv, yv) == hp.dot(xv, yv)
 
 
-@pytest.mark.parametrize("n,where", [(1, 0), (64, 63), (513, 0), (513, 512), (100_003, 50_001), (4_000_001, 3_999_999)])
+@pytest.mark.parametrize("n,where", gr.PLAIN_F64_NAN)
 def test_max_reductions_propagate_nan(hp, orc, gpu_backend_i32, n, where):
-    """`v > s ? v : s` never selected a NaN, so norm(v, Inf) / maximum / minimum of a vector holding one NaN
+    """At n = 4 194 307 the grid is capped at 2048 workgroups, so a trip of stage 1 is 524 288 double2: element 4 194 303 is read
+    by the last lane of the last workgroup in its last trip, 4 194 305 by lane 0 of workgroup 0 in a fifth trip of its own and
+    4 194 306 is the scalar tail (tests/test_grid_regimes.py checks these positions against the grid).
+    ADVICE r4: `v > s ? v : s` never selected a NaN, so norm(v, Inf) / maximum / minimum of a vector holding one NaN
     returned a finite number -- and with it the NaN rows an expired halo wait leaves in y.  Julia's maximum and
     norm(., Inf) return NaN (src/vectors.jl:769-772, 815-836)."""
     xg = orc.fill_uniform(0, n, 3) - 0.5
@@ -1195,6 +1248,44 @@ def test_fused_spmv_dot_and_cg_update(hp, orc, gpu_backend_i32):
         np.testing.assert_array_equal(X2.local_values(), wx)
         wp = pg.copy(); orc.xpay(wr, 1.0 * 0.3 / 0.7, wp)                 # p = r + t p
         np.testing.assert_array_equal(P2.local_values(), wp)
+
+
+@pytest.mark.parametrize("n", gr.CG_TRIO_ALONE)
+def test_cg_update_trio_on_vectors_alone(hp, orc, gpu_backend_i32, n):
+    """The cg_update_ / cg_residual_ / cg_direction_ block of test_fused_spmv_dot_and_cg_update without a matrix, at sizes that
+    test's matrices do not reach (its largest has 120 000 rows: 59 partials, 235 elementwise workgroups).  1 is the scalar tail
+    alone, 511 one workgroup of either grid with a tail, 2051 two partials and five elementwise workgroups, 614 403 gives 301
+    partials (a ragged second trip of the second stage) and 1201 elementwise workgroups, 4 194 307 caps both grids (2048
+    partials in five grid-stride trips, 4096 elementwise workgroups in three); all odd.  Elements: the bits of the oracle's
+    axpy / xpay; the sum: the project's margin for its reductions, relative to the sum of the (positive) terms."""
+    import torch
+    b = gpu_backend_i32
+    pg, apg = orc.fill_uniform(0, n, 6), orc.fill_uniform(0, n, 7)
+    xx, rrv = orc.fill_uniform(0, n, 8), orc.fill_uniform(0, n, 9)
+    dev = lambda v: torch.tensor([v], dtype=torch.float64, device="cuda")
+    num, den, bnum, bden = dev(0.75), dev(1.5), dev(0.3), dev(0.7)
+    s = 1.0 * 0.75 / 1.5
+    X, R = hp.HPCVector.from_global(xx, b), hp.HPCVector.from_global(rrv, b)
+    P, AP = hp.HPCVector.from_global(pg, b), hp.HPCVector.from_global(apg, b)
+    rr = torch.zeros(1, dtype=torch.float64, device="cuda")
+    hp.cg_update_(X, R, P, AP, 1.0, num, den, rr)
+    wx = xx.copy(); orc.axpy(s, pg, wx)
+    wr = rrv.copy(); orc.axpy(-s, apg, wr)
+    np.testing.assert_array_equal(X.local_values(), wx)
+    np.testing.assert_array_equal(R.local_values(), wr)
+    want = math.fsum((wr * wr).tolist())
+    err = abs(rr.item() - want) / want
+    print(f"n = {n}: sum r^2 off by {err:.2e} of the sum of the terms")
+    assert err <= RTOL_RED
+    X2, R2, P2 = hp.HPCVector.from_global(xx, b), hp.HPCVector.from_global(rrv, b), hp.HPCVector.from_global(pg, b)
+    rr2 = torch.zeros(1, dtype=torch.float64, device="cuda")
+    hp.cg_residual_(R2, AP, 1.0, num, den, rr2)
+    np.testing.assert_array_equal(R2.local_values(), wr)
+    assert rr2.item() == rr.item()                                    # same reduction tree as cg_update_
+    hp.cg_direction_(X2, P2, R2, 1.0, num, den, 1.0, bnum, bden)
+    np.testing.assert_array_equal(X2.local_values(), wx)
+    wp = pg.copy(); orc.xpay(wr, 1.0 * 0.3 / 0.7, wp)                 # p = r + t p
+    np.testing.assert_array_equal(P2.local_values(), wp)
 
 
 def test_cg_fused_equals_unfused(hp, orc, gpu_backend_i32):

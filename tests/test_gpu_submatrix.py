@@ -9,7 +9,9 @@ Products over the result are compared bitwise with the oracle's loops over the r
 is a NaN the product must be a NaN (which NaN an Inf - Inf yields is the hardware's choice, not a copied bit).
 
 The scan behind the new rowptr and col_indices works in chunks of SCAN_CHUNK = 1 024 elements (csrc/scan.h; asserted below
-against the library); the 70 001-row band matrix crosses 68 chunk boundaries in both scans."""
+against the library); the 70 001-row band matrix crosses 68 chunk boundaries in both scans.  One workgroup scans the chunks'
+sums 256 at a time with a carry between the trips: the two band_long cases (tests/_submatrix_cases.py) select more than
+256 * 1 024 = 262 144 rows and a column range wider than that, with unequal chunk sums on both sides of the first carry."""
 import ctypes
 import os
 

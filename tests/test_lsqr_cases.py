@@ -208,3 +208,16 @@ def test_restatement_on_the_exact_and_degenerate_cases(orc):
     x, its, status, hr, hn, _ = lc.lsqr(*case, x0=np.full(case[3], 1e-3))
     dense = lc.dense_of(*case[:4])
     assert status == "converged" and np.linalg.norm(case[4] - dense @ x) <= 2e-8 * np.linalg.norm(case[4])
+
+
+def test_head_spread_at_the_large_size(orc):
+    """The tall case at 65 x 63 (8190 x 4095: four and two reduction workgroups on the device): the first HEAD entries of both
+    histories under the four summation orders.  HIST_RTOL, which tests/test_gpu_lsqr.py asks there, must be at least 10 times
+    the spread (measured: 1.2e-14 at damp 0, 1.0e-14 at damp 0.3: 80 times)."""
+    case = lc.tall(orc, *lc.LARGE_SIZE)
+    assert (len(case[0]) - 1, case[3]) == (8190, 4095)
+    for damp in lc.DAMPS:
+        runs = [lc.lsqr(*case, damp=damp, rtol=0.0, ntol=0.0, maxiter=lc.HEAD, dot=dot) for dot in lc.DOTS.values()]
+        spread = max((max(col) - min(col)) / min(col) for which in (3, 4) for col in zip(*[r[which][:lc.HEAD] for r in runs]))
+        print(f"tall {lc.LARGE_SIZE} damp {damp}: spread over the first {lc.HEAD} entries of both histories {spread:.2e}")
+        assert pc.LARGE_MARGIN_FACTOR * spread <= lc.HIST_RTOL

@@ -107,3 +107,18 @@ def test_restatement_on_the_freeze_and_breakdown_cases(orc):
     x, its, status, h = pc.pcg(*eye, np.zeros(5))
     assert (its, status, h) == (0, "converged", [0.0]) and not x.any()
     assert math.isfinite(h[0])
+
+
+def test_head_spread_at_the_large_size(orc):
+    """65 x 63 (4095 rows, two reduction workgroups on the device): the first HEAD entries under the four summation orders of
+    ``_bicgstab_cases.DOTS``.  CG_RTOL, which tests/test_gpu_pcg.py asks there, must be at least LARGE_MARGIN_FACTOR = 10 times the
+    spread (measured: 6.9e-15 with Jacobi, 2.2e-14 without: 45 times)."""
+    from tests import _bicgstab_cases as bc
+    rowptr, colidx, vals, b = pc.scaled_poisson(orc, *pc.LARGE_SIZE)
+    assert len(b) == 4095
+    d = pc.host_diag(rowptr, colidx, vals)
+    for name, dinv in (("jacobi", 1.0 / d), ("none", None)):
+        hists = [pc.pcg(rowptr, colidx, vals, b, dinv=dinv, rtol=0.0, atol=0.0, maxiter=pc.HEAD, dot=dot)[3] for dot in bc.DOTS.values()]
+        spread = max((max(col) - min(col)) / min(col) for col in zip(*[h[:pc.HEAD] for h in hists]))
+        print(f"{pc.LARGE_SIZE} {name}: spread over the first {pc.HEAD} history entries {spread:.2e}")
+        assert pc.LARGE_MARGIN_FACTOR * spread <= pc.CG_RTOL

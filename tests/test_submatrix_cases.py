@@ -44,6 +44,19 @@ def test_the_matrices_hold_what_the_cases_need():
     assert len(set(names)) == len(names)
     counts = {c[3] - c[2] for c in sc.CASES}
     assert {0, 1, 63, 64, 65, 255, 256, 257, 1000, 70001} <= counts
+    # the two cases past the scan's first trip of chunk sums: more than SCAN_TRIP selected rows, more than SCAN_TRIP columns, and
+    # entries (rows) / occurring columns on both sides of element SCAN_TRIP, with empty chunks before it
+    assert sc.matrix(sc.BAND_LONG).shape == (sc.BAND_LONG_ROWS, sc.BAND_LONG_ROWS)
+    long = {c[0]: c for c in sc.CASES if c[1] == sc.BAND_LONG}
+    _, key, r0, r1, c0, c1 = long["band_long_rows"]
+    got = sc.restate(sc.matrix(key), r0, r1, c0, c1)
+    per_row = np.diff(got["rowptr"])
+    assert r1 - r0 > sc.SCAN_TRIP and per_row[:sc.SCAN_TRIP].sum() > 0 and per_row[sc.SCAN_TRIP:].sum() > 0
+    assert per_row[:sc.SCAN_CHUNK].sum() == 0 and c1 - c0 < sc.SCAN_TRIP
+    _, key, r0, r1, c0, c1 = long["band_long_cols"]
+    got = sc.restate(sc.matrix(key), r0, r1, c0, c1)
+    assert c1 - c0 > sc.SCAN_TRIP and r1 - r0 < sc.SCAN_TRIP
+    assert 0 < (got["col_indices"] < sc.SCAN_TRIP).sum() < len(got["col_indices"]) and got["col_indices"].min() > sc.SCAN_CHUNK
 
 
 @pytest.mark.parametrize("case", sc.CASES, ids=[c[0] for c in sc.CASES])
