@@ -118,6 +118,17 @@ def checks_of(family, hp, orc, backend, large):
         for k in (16, 6, 3):
             for Ti in (I32, I64):
                 add(test_gpu_parity.test_spmm_panel_accumulate_is_one_running_sum, hp, orc, backend, k, Ti)
+        # the pass, tile and lane-group edges of tests/test_gpu_spmm_edges.py under every HPCLA_SPMM_* setting: other kernel
+        # instances on the same matrices.  Under HPCLA_SPMM_CHUNK the passes are the forced size, so only the matrix laid out
+        # for that size has its straddling rows on the real boundaries; the other one still has multi-pass blocks and is
+        # compared bit for bit, and both matrices run under both settings
+        from tests import _spmm_edge_cases as sc, test_gpu_spmm_edges
+        for CH in (sc.CHUNK_V_SMALL, sc.CHUNK_V_LARGE):
+            for Ti, base in ((I32, 0), (I64, 1)):
+                add(test_gpu_spmm_edges.test_vector_kernel_at_pass_edges, hp, orc, CH, Ti, base)
+        for Ti, base in ((I32, 1), (I64, 0)):
+            add(test_gpu_spmm_edges.test_generic_kernel_at_pass_edges, hp, orc, Ti, base)
+        add(test_gpu_spmm_edges.test_switch_between_the_two_pass_sizes, hp, orc, I32)
     elif family == "colmajor":
         from tests import test_gpu_colmajor
         for k in (2, 8, 16, 17, 40):
@@ -202,6 +213,18 @@ def fingerprints(hp, orc, backend):
             C = dC.cpu().numpy()
             # (column-major B and C: hpcla_spmm_csr_f64_* routes to csrc/colmajor.hip)
             fp[f"{'colmajor' if layout == 'col' else 'spmm'}/spmm(k={k}, {layout}).C"] = sha(C[:, :k] if layout == "row" else C)
+
+    # C of the raw-ABI SpMM on the pass matrix of 512-record passes (tests/_spmm_edge_cases.py) at k = 16
+    from tests import _spmm_edge_cases as sc
+    M = sc.pass_matrix(sc.CHUNK_V_SMALL)
+    n, k = M["nrows"], 16
+    d = (t(M["rowptr"].astype(I32)), t(M["colval"].astype(I32)), t(M["vals"]))
+    dB = t(sc.master_B()[:, :k])
+    dC = torch.full((n, k), float("nan"), dtype=torch.float64, device="cuda")
+    hp._capi.call("hpcla_spmm_csr_f64_i32", d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), dB.data_ptr(), k, ROW, dC.data_ptr(), k,
+                  ROW, n, len(M["vals"]), k, 0, s)
+    torch.cuda.synchronize()
+    fp[f"spmm/pass matrix(CH={sc.CHUNK_V_SMALL}, k={k}).C"] = sha(dC.cpu().numpy())
 
     # C of the column-major SpMM with long and empty rows at k = 3, 16, 17
     rng = np.random.default_rng(3)

@@ -110,7 +110,7 @@ def test_baseline_runs_every_check_under_the_default_environment(children):
     report = _passed(children["baseline"])
     assert report["env"] == {}
     assert set(report["checks"]) == set(FAMILY_SETTINGS) and all(report["checks"].values())
-    assert len(report["fingerprints"]) >= 40
+    assert len(report["fingerprints"]) >= 41
 
 
 @pytest.mark.parametrize("i", range(N_CHILDREN), ids=NAMES)

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from tests import _grid_regimes as gr
+from tests import _spmm_edge_cases as sc
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -2007,26 +2008,8 @@ def test_spmm_run_tiles_raw_abi(hp, orc, gpu_backend_i32, Ti):
                       ctypes.byref(n_fit), s)
         nblk = (n + 63) // 64
         d = desc.cpu().numpy().view(np.int32).reshape(nblk, 8)
-        # the descriptors against a host restatement
-        fit_ref = 0
-        for b in range(nblk):
-            lo, hi = rows.rowptr[b * 64], rows.rowptr[min((b + 1) * 64, n)]
-            cols = np.unique(cv[lo:hi])
-            if len(cols) == 0:
-                assert (d[b] == 0).all()
-                fit_ref += 1
-                continue
-            brk = np.flatnonzero((np.diff(cols) != 1) | ((cols[:-1] < n_own) & (cols[1:] >= n_own))) + 1
-            starts = np.concatenate([[0], brk])
-            lens = np.diff(np.concatenate([starts, [len(cols)]]))
-            ok = len(starts) <= 4 and len(cols) <= 200 and hi - lo <= 512
-            assert (d[b, 4] >= 0) == ok, (b, d[b], len(starts), len(cols), hi - lo)
-            if ok:
-                fit_ref += 1
-                np.testing.assert_array_equal(d[b, :len(starts)], cols[starts])
-                np.testing.assert_array_equal(d[b, 4:4 + len(starts)], lens)
-                assert (d[b, 4 + len(starts):] == 0).all()
-        assert n_fit.value == fit_ref
+        # the descriptors against the host restatement (tests/_spmm_edge_cases.py)
+        fit_ref = sc.check_descriptors(d, n_fit.value, sc.run_descriptors(rows.rowptr, cv, n, n_own))
         if expect_fit is not None:
             assert (fit_ref == nblk) == expect_fit, (fit_ref, nblk)
         perm = np.random.default_rng(4).permutation(nblk).astype(np.int32)
