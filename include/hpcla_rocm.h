@@ -1291,6 +1291,38 @@ int hpcla_eigsh_steps_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const
                               int64_t n_interior, const int32_t *boundary_blocks, int64_t n_boundary, double *V, int64_t ldv,
                               double *w, double *small_dev, void *work, int ncv, int first_col, int count, int64_t first_iter,
                               void *stream);
+/* ---- the block eigensolver (hp.lobpcg, csrc/lobpcg.hip): LOBPCG with B = I for the k <= 16 smallest or largest eigenpairs of
+ * a symmetric A.  The host enqueues, per iteration: lobpcg_residual, the SpMM A*W (hpcla_spmm_*), ONE hpcla_gram_f64 of
+ * S = [X W P] against [S | AS], reads the residual sums and the Gram matrices back once, solves the whitened Rayleigh-Ritz
+ * problem in numpy, uploads (theta, C) and runs lobpcg_combine.  Every block is row-major with a pitch (in doubles) of its own,
+ * so the blocks may be column ranges of one wider buffer; every array is 8-byte aligned, and where all the pitches of a call
+ * are even and its bases 16-byte aligned the accesses are 16 bytes per lane.  1 <= k <= 16.
+ *   lobpcg_residual  per element, separately rounded:  t = theta_dev[j] * X[r,j];  d = AX[r,j] - t;  W[r,j] = minv[r] * d
+ *                    (minv == NULL: W[r,j] = d).  W2 != NULL: the same values go to a second block on the pitch ldw2 (the
+ *                    SpMM's operand on spmm_pitch; padding columns of any block are neither read nor written).
+ *                    rn2_dev[j] = sum_r d[r,j]^2 (the residual before minv): per-workgroup partials over chunks of hpcla_lobpcg_chunk_rows(n) rows, then
+ *                    one workgroup adds the chunks in 16 phases of ascending chunks and the phases ascending -- an order that
+ *                    depends on (n, k) only, so the same inputs give the same bits on every call -- then one all-reduce of the
+ *                    k sums (comm != NULL).  n == 0: the sums are zero and the rank still reduces; no pointer but rn2_dev is
+ *                    looked at.  work: hpcla_lobpcg_work_bytes(n, k) device bytes.  Bytes per row: read 8 (2k + 1 with minv),
+ *                    write 8k (16k with W2).
+ *   lobpcg_combine   [X | P] <- S C in place, one pass.  S holds [X W P] in columns 0..3k-1 of which the first k + c_rest are
+ *                    read, c_rest in {0, k, 2k}; C_dev is (k + c_rest) x k, row i at C_dev + 16 i (the 16 - k doubles behind a
+ *                    row are read and ignored).  Per row r and column j, products and sums separately rounded:
+ *                      px = 0;  px = px + S[r,i] * C[i,j], i = 0 .. k-1 ascending
+ *                      pp = 0;  pp = pp + S[r,i] * C[i,j], i = k .. k + c_rest - 1 ascending
+ *                      X'[r,j] = px + pp (columns 0..k-1);  P'[r,j] = pp (columns 2k..3k-1; not written with c_rest = 0)
+ *                    and the same for AS != NULL (its own pitch).  Columns k..2k-1 (W) and everything behind 3k keep their
+ *                    bits.  In place is safe because a row belongs to one workgroup, which holds the row in LDS before a
+ *                    barrier and stores only behind it.  Pitches: at least k, and at least 3k with c_rest > 0.  Returns at
+ *                    n == 0.  Bytes per row: read 16 (k + c_rest), write 32k (16k with c_rest = 0); half of both without AS. */
+int64_t hpcla_lobpcg_chunk_rows(int64_t n);
+int64_t hpcla_lobpcg_work_bytes(int64_t n, int k);
+int hpcla_lobpcg_residual_f64(hpcla_comm_t *comm, const double *X, int64_t ldx, const double *AX, int64_t ldax,
+                              const double *theta_dev, const double *minv, double *W, int64_t ldw, double *W2, int64_t ldw2,
+                              int64_t n, int k, double *rn2_dev, void *work, void *stream);
+int hpcla_lobpcg_combine_f64(double *S, int64_t lds, double *AS, int64_t ldas, const double *C_dev, int k, int c_rest,
+                             int64_t n, void *stream);
 int hpcla_divide_f64(const double *x, double a_host, double *y, int64_t n, void *stream);
 int hpcla_axpby_f64(double a, const double *x, double b, const double *y, double *z, int64_t n,
                     void *stream);

@@ -19,6 +19,8 @@ Layout
                      (minres_* kernels)
   eigsh.py           eigsh(): extreme eigenpairs of a symmetric A by thick-restart Lanczos on the GMRES kernels; the restart
                      rotates the basis in place in one pass (csrc/eigsh.hip)
+  lobpcg.py          lobpcg(): the k <= 16 smallest or largest eigenpairs with their multiplicities by LOBPCG (optionally
+                     Jacobi-preconditioned): the SpMM, one Gram pass, a host Rayleigh-Ritz, two block kernels (csrc/lobpcg.hip)
   indexing.py        v[a:b], X[r, c], A[r, c], A[:, k], diag(A) and SubmatrixPlan (csrc/submatrix.hip)
   transpose.py matmat.py addition.py repartition.py   the SURVEY 8f "next" rows and their plans
 
@@ -48,6 +50,7 @@ from .gmres import GMRESWorkspace, gmres
 from .lsqr import LSQRInfo, LSQRWorkspace, lsqr
 from .minres import MinresWorkspace, minres
 from .eigsh import EigshInfo, EigshWorkspace, eigsh
+from .lobpcg import LobpcgInfo, LobpcgWorkspace, lobpcg
 from .convert import to_backend
 from .transpose import (HostTransposeStructure, TransposedHPCSparseMatrix, TransposedHPCVector, TransposePlan,
                         DenseTransposeLists, HostSpmmTPlan, adjoint, clear_transpose_plan_cache, get_transpose_plan,

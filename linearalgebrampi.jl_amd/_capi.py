@@ -214,6 +214,11 @@ _SIGNATURES = {
                                   _vp, _vp, _i32, _i32, _i32, _i64, _vp],
     "hpcla_eigsh_steps_f64_i64": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp,
                                   _vp, _vp, _i32, _i32, _i32, _i64, _vp],
+    # the block eigensolver (hp.lobpcg): the residual block with its column norms, the in-place combine (csrc/lobpcg.hip)
+    "hpcla_lobpcg_chunk_rows": [_i64],
+    "hpcla_lobpcg_work_bytes": [_i64, _i32],
+    "hpcla_lobpcg_residual_f64": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp],
+    "hpcla_lobpcg_combine_f64": [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _i64, _vp],
     "hpcla_colspace_work_bytes": [_i64],
     "hpcla_compress_columns_i32": [_vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
     "hpcla_compress_columns_i64": [_vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
@@ -327,6 +332,8 @@ _RESTYPES = {
     "hpcla_gmres_work_bytes": _i64,
     "hpcla_gmres_small_offset": _i64,
     "hpcla_eigsh_small_offset": _i64,
+    "hpcla_lobpcg_chunk_rows": _i64,
+    "hpcla_lobpcg_work_bytes": _i64,
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

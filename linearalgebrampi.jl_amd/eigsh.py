@@ -213,7 +213,8 @@ def eigsh(A, k: int = 6, which: str = "LA", ncv: Optional[int] = None, tol: floa
     Limits.  The gates are exact-zero and NaN tests, as everywhere in this package.  Single-vector Lanczos finds ONE vector per
     distinct eigenvalue: a multiple eigenvalue is returned once, and the copies it misses are replaced by the next distinct
     values.  The square 16 x 16 Poisson grid has ``lambda_ij = lambda_ji``; a ``k = 4`` run returns a wrong set there while
-    every residual is within ``tol``.  Block Lanczos would be the remedy and is not here.
+    every residual is within ``tol``.  A block method is the remedy: ``hp.lobpcg`` (lobpcg.py) finds a multiple eigenvalue with
+    its multiplicity.
 
     The host reads back once per cycle and never inside one.  With N ranks every rank computes the same T from all-reduced
     values; still only rank 0's decision and rank 0's S are used (broadcast), so no rank leaves the loop alone and no two ranks
