@@ -1291,6 +1291,63 @@ int hpcla_eigsh_steps_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const
                               int64_t n_interior, const int32_t *boundary_blocks, int64_t n_boundary, double *V, int64_t ldv,
                               double *w, double *small_dev, void *work, int ncv, int first_col, int count, int64_t first_iter,
                               void *stream);
+/* ---- The largest singular triplets of a rectangular A: thick-restart Golub-Kahan-Lanczos bidiagonalisation (Baglama and
+ * Reichel; SLEPc's TRLBD) with full two-sided reorthogonalisation by twice-applied classical Gram-Schmidt (no reference
+ * counterpart: the reference has no SVD, its svd would be a dense LAPACK call; a caller of its operators composes the method
+ * from A*v, src/sparse.jl:2096-2128, transpose(A)*u, src/sparse.jl:2136-2142, dot, src/vectors.jl:798-812, and the broadcasts,
+ * src/vectors.jl:1203-1226: 4c dots, 4c axpys and 4c + 2 host read-backs in the step that orthogonalises against c columns on
+ * each side, and the restart as two dense products plus their copies back).
+ * Two bases of the GMRES kind: U, ncv columns of nrows doubles, and V, ncv + 1 columns of nrows_t doubles, each at an even
+ * pitch of its own and 16-byte aligned.  Each half of a step reuses gmres_dots, the first pass of gmres_update and gmres_next as
+ * they are; the restart is two launches of hpcla_eigsh_rotate_f64; the state is the eigensolver's (done_iter, status, not used,
+ * reserved) with status 2 = breakdown and 4 = invariant.
+ * The small arrays of a solve live in ONE buffer of hpcla_svds_small_offset(ncv, 9) doubles; the offset of each is
+ * hpcla_svds_small_offset(ncv, which), which = 0 .. 8:  B (ncv x ncv, column j at B + j*ncv: the projected matrix's upper
+ * triangle as the device computed it, alpha_j on its diagonal; the strict lower triangle is never written), beta (ncv), g1, g2
+ * (the left half's two passes' coefficients), h1, h2 (the right half's), aa (u.u), bb (v.v), dv (the divisor of
+ * hpcla_gmres_next_f64).  -1 for ncv outside 1..64.  Scratch and state: hpcla_gmres_work_bytes(ncv) bytes.
+ *   svds_update     the second pass of one half of column j at step iter (1-based over the solve): w = ((w - h_dev[0]*W_0) -
+ *                   h_dev[1]*W_1) - ..., nn = w.w, one all-reduce (comm != NULL), then by one thread the small step of that side.
+ *                   side 0 (left: W = U, ncols = j, 0 <= ncols <= ncv - 1; ncols == 0 is the norm and the small step alone, W
+ *                   and h_dev may then be NULL), nn goes to aa:
+ *                     gate N   aa != aa:  status = 2, done_iter = iter - 1, nothing of column j is stored
+ *                     B[i, j] = g1[i] + g2[i] for i < j;  B[j, j] = dv = sqrt(aa)
+ *                     gate Z   aa == 0:   status = 4, done_iter = iter - 1 (j triplets are finished; column j of B is stored)
+ *                   side 1 (right: W = V, ncols = j + 1, 1 <= ncols <= ncv), nn goes to bb:
+ *                     gate N'  bb != bb:  status = 2, done_iter = iter - 1, beta[j] is not stored
+ *                     beta[j] = dv = sqrt(bb)
+ *                     gate Z'  bb == 0:   status = 4, done_iter = iter (j + 1 triplets are finished; beta[j] = 0 is stored)
+ *                   With c = done_iter - (steps before the cycle) + p finished columns the gate was Z' when c > p and
+ *                   beta[c - 1] == 0, else Z.  The sum's order is hpcla_dot_f64's and does not depend on ncols.
+ *                   Once status != 0 it writes no byte with comm == NULL; with a communicator the all-reduce between the two
+ *                   gated launches still runs and rewrites aa or bb (scratch: nothing reads it behind a stop), and nothing else. */
+int64_t hpcla_svds_small_offset(int ncv, int which);
+int hpcla_svds_update_f64(hpcla_comm_t *comm, const double *W, int64_t ldw, int ncols, const double *h_dev, double *w, int64_t n,
+                          int64_t iter, int ncv, int side, double *small_dev, int64_t *state_dev, void *work, void *stream);
+/* Columns first_col .. first_col + count - 1 of a cycle (steps first_iter .. of the solve) enqueued by ONE host call.  The two
+ * matrix blocks are A's and its materialised transpose's, as hpcla_lsqr_iterations_* takes them.  Per column j: u = A*V_j
+ * (always executed), over U's j columns (nothing at j == 0) gmres_dots into g1, gmres_update (first pass), gmres_dots into g2,
+ * then svds_update (side 0) and gmres_next into U_j; v = At*U_j (always executed), over V's j + 1 columns gmres_dots into h1,
+ * gmres_update, gmres_dots into h2, svds_update (side 1) and gmres_next into V_{j+1} (also at j + 1 == ncv).  The state lives in
+ * the last 32 bytes of work and is set up by the caller.  Only enqueues. */
+int hpcla_svds_steps_f64_i32(hpcla_comm_t *comm, hpcla_halo_plan_t *plan, const int32_t *rowptr, const int32_t *colval_split,
+                             const int16_t *cols16, const hpcla_block_patterns_t *patterns, const double *nzval, int64_t nrows,
+                             int64_t nnz, int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                             const int32_t *boundary_blocks, int64_t n_boundary, hpcla_halo_plan_t *plan_t,
+                             const int32_t *rowptr_t, const int32_t *colval_split_t, const int16_t *cols16_t,
+                             const hpcla_block_patterns_t *patterns_t, const double *nzval_t, int64_t nrows_t, int64_t nnz_t,
+                             int index_base_t, const int32_t *interior_blocks_t, int64_t n_interior_t,
+                             const int32_t *boundary_blocks_t, int64_t n_boundary_t, double *U, int64_t ldu, double *V,
+                             int64_t ldv, double *u, double *v, double *small_dev, void *work, int ncv, int first_col, int count,
+                             int64_t first_iter, void *stream);
+int hpcla_svds_steps_f64_i64(hpcla_comm_t *comm, hpcla_halo_plan_t *plan, const int64_t *rowptr, const int64_t *colval_split,
+                             const double *nzval, int64_t nrows, int64_t nnz, int index_base, const int32_t *interior_blocks,
+                             int64_t n_interior, const int32_t *boundary_blocks, int64_t n_boundary, hpcla_halo_plan_t *plan_t,
+                             const int64_t *rowptr_t, const int64_t *colval_split_t, const double *nzval_t, int64_t nrows_t,
+                             int64_t nnz_t, int index_base_t, const int32_t *interior_blocks_t, int64_t n_interior_t,
+                             const int32_t *boundary_blocks_t, int64_t n_boundary_t, double *U, int64_t ldu, double *V,
+                             int64_t ldv, double *u, double *v, double *small_dev, void *work, int ncv, int first_col, int count,
+                             int64_t first_iter, void *stream);
 /* ---- the block eigensolver (hp.lobpcg, csrc/lobpcg.hip): LOBPCG with B = I for the k <= 16 smallest or largest eigenpairs of
  * a symmetric A.  The host enqueues, per iteration: lobpcg_residual, the SpMM A*W (hpcla_spmm_*), ONE hpcla_gram_f64 of
  * S = [X W P] against [S | AS], reads the residual sums and the Gram matrices back once, solves the whitened Rayleigh-Ritz

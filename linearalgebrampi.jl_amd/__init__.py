@@ -21,6 +21,9 @@ Layout
                      rotates the basis in place in one pass (csrc/eigsh.hip)
   lobpcg.py          lobpcg(): the k <= 16 smallest or largest eigenpairs with their multiplicities by LOBPCG (optionally
                      Jacobi-preconditioned): the SpMM, one Gram pass, a host Rayleigh-Ritz, two block kernels (csrc/lobpcg.hip)
+  svds.py            svds(): the largest singular triplets of a rectangular A by thick-restart Golub-Kahan bidiagonalisation on A
+                     and its materialised transpose: the GMRES kernels on two bases, a small step of its own (svds_* kernels), the
+                     eigensolver's rotate for both restarts
   indexing.py        v[a:b], X[r, c], A[r, c], A[:, k], diag(A) and SubmatrixPlan (csrc/submatrix.hip)
   transpose.py matmat.py addition.py repartition.py   the SURVEY 8f "next" rows and their plans
 
@@ -51,6 +54,7 @@ from .lsqr import LSQRInfo, LSQRWorkspace, lsqr
 from .minres import MinresWorkspace, minres
 from .eigsh import EigshInfo, EigshWorkspace, eigsh
 from .lobpcg import LobpcgInfo, LobpcgWorkspace, lobpcg
+from .svds import SvdsInfo, SvdsWorkspace, svds
 from .convert import to_backend
 from .transpose import (HostTransposeStructure, TransposedHPCSparseMatrix, TransposedHPCVector, TransposePlan,
                         DenseTransposeLists, HostSpmmTPlan, adjoint, clear_transpose_plan_cache, get_transpose_plan,

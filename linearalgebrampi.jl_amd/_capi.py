@@ -214,6 +214,17 @@ _SIGNATURES = {
                                   _vp, _vp, _i32, _i32, _i32, _i64, _vp],
     "hpcla_eigsh_steps_f64_i64": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp,
                                   _vp, _vp, _i32, _i32, _i32, _i64, _vp],
+    # thick-restart Golub-Kahan bidiagonalisation (hp.svds): the second pass of either side, the columns of a cycle
+    "hpcla_svds_small_offset": [_i32, _i32],
+    "hpcla_svds_update_f64": [_vp, _vp, _i64, _i32, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp],
+    "hpcla_svds_steps_f64_i32": [_vp,
+                                 _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
+                                 _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
+                                 _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _vp],
+    "hpcla_svds_steps_f64_i64": [_vp,
+                                 _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
+                                 _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
+                                 _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _vp],
     # the block eigensolver (hp.lobpcg): the residual block with its column norms, the in-place combine (csrc/lobpcg.hip)
     "hpcla_lobpcg_chunk_rows": [_i64],
     "hpcla_lobpcg_work_bytes": [_i64, _i32],
@@ -332,6 +343,7 @@ _RESTYPES = {
     "hpcla_gmres_work_bytes": _i64,
     "hpcla_gmres_small_offset": _i64,
     "hpcla_eigsh_small_offset": _i64,
+    "hpcla_svds_small_offset": _i64,
     "hpcla_lobpcg_chunk_rows": _i64,
     "hpcla_lobpcg_work_bytes": _i64,
 }

@@ -1665,3 +1665,116 @@ HPCLA_API int hpcla_eigsh_steps_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *c
                                      nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks, n_boundary, V, ldv, w,
                                      small_dev, work, ncv, first_col, count, first_iter, stream);
 }
+
+// ---- columns of a thick-restart Golub-Kahan cycle in ONE host call (the truncated SVD, hp.svds) ------------------------------
+// A of any shape nrows x nrows_t, At its materialised transpose (a matrix and a plan of its own, as for hpcla_lsqr_iterations_*).
+// Two bases: U (ncv columns of nrows doubles at the even pitch ldu) and V (ncv + 1 columns of nrows_t doubles at ldv); full
+// two-sided reorthogonalisation by twice-applied classical Gram-Schmidt on the GMRES kernels.  Column j = first_col ..
+// first_col + count - 1 of a cycle of ncv columns, step first_iter + (j - first_col) of the solve:
+//   1. u = A V_j                    hpcla_spmv_dist_* on A's plan -- always executed, not gated
+//   2. g1 = U^T u; u = u - U g1; g2 = U^T u          gmres_dots, gmres_update (first pass), gmres_dots over j columns (none at j = 0)
+//   3. u = u - U g2, aa = u.u       hpcla_svds_update_f64, side 0: one all-reduce [aa], B's column j and alpha_j, gates N and Z
+//   4. U_j = u / alpha_j            hpcla_gmres_next_f64
+//   5. v = At U_j                   the SpMV on At's plan -- always executed
+//   6. h1 = V^T v; v = v - V h1; h2 = V^T v          the same three over j + 1 columns
+//   7. v = v - V h2, bb = v.v       hpcla_svds_update_f64, side 1: one all-reduce [bb], beta_j, gates N' and Z'
+//   8. V_{j+1} = v / beta_j         hpcla_gmres_next_f64, also at j + 1 == ncv: the right basis has ncv + 1 columns
+// One rank: 2 SpMV + 12 + 2 ceil(j / 8) + 2 ceil((j + 1) / 8) launches per step (11 at j = 0), no read-back.  The host reads the small buffer
+// once per cycle.
+template <typename I, typename F, typename G>
+static int svds_steps_impl(F split_fn, G fused_fn, hpcla_comm_t *comm, hpcla_halo_plan_t *plan, const I *rowptr, const I *colval,
+                           const int16_t *cols16, const hpcla_block_patterns *patterns, const double *nzval, int64_t nrows,
+                           int64_t nnz, int index_base, const int32_t *interior, int64_t n_interior, const int32_t *boundary,
+                           int64_t n_boundary, hpcla_halo_plan_t *plan_t, const I *rowptr_t, const I *colval_t,
+                           const int16_t *cols16_t, const hpcla_block_patterns *patterns_t, const double *nzval_t,
+                           int64_t nrows_t, int64_t nnz_t, int index_base_t, const int32_t *interior_t, int64_t n_interior_t,
+                           const int32_t *boundary_t, int64_t n_boundary_t, double *U, int64_t ldu, double *V, int64_t ldv,
+                           double *u, double *v, double *small_dev, void *work, int ncv, int first_col, int count,
+                           int64_t first_iter, void *stream)
+{
+    if (nrows < 0 || nnz < 0 || nrows_t < 0 || nnz_t < 0) return set_error(HPCLA_ERR_INVALID, "svds_steps: negative size");
+    if (ncv < 1 || ncv > 64) return set_error(HPCLA_ERR_INVALID, "svds_steps: ncv must be in 1..64");
+    if (first_col < 0 || count < 0 || first_col + count > ncv || first_iter < 1)
+        return set_error(HPCLA_ERR_INVALID, "svds_steps: columns outside 0..ncv-1 or first_iter < 1");
+    if (ldu < nrows || (ldu & 1) || ldv < nrows_t || (ldv & 1))
+        return set_error(HPCLA_ERR_INVALID, "svds_steps: both pitches must be even and at least the local length");
+    if (!small_dev || !work) return set_error(HPCLA_ERR_INVALID, "svds_steps: null small arrays / work");
+    if ((nrows > 0 && (!U || !u)) || (nrows_t > 0 && (!V || !v))) return set_error(HPCLA_ERR_INVALID, "svds_steps: null vector");
+    if ((reinterpret_cast<uintptr_t>(U) | reinterpret_cast<uintptr_t>(V) | reinterpret_cast<uintptr_t>(u) |
+         reinterpret_cast<uintptr_t>(v)) & 15)
+        return set_error(HPCLA_ERR_INVALID, "svds_steps: vectors must be 16-byte aligned");
+    int64_t *state = reinterpret_cast<int64_t *>(static_cast<char *>(work) + hpcla_gmres_work_bytes(ncv)) - 4;
+    double *g1 = small_dev + hpcla_svds_small_offset(ncv, 2), *g2 = small_dev + hpcla_svds_small_offset(ncv, 3);
+    double *h1 = small_dev + hpcla_svds_small_offset(ncv, 4), *h2 = small_dev + hpcla_svds_small_offset(ncv, 5);
+    double *dv = small_dev + hpcla_svds_small_offset(ncv, 8);
+    for (int j = first_col; j < first_col + count; ++j) {
+        const int64_t k = first_iter + (j - first_col);
+        double *Uj = U + (int64_t)j * ldu;
+        int rc = spmv_dist_impl<I>(split_fn, fused_fn, plan, rowptr, colval, nzval, V + (int64_t)j * ldv, nrows_t, u, nrows, nnz,
+                                   index_base, interior, n_interior, boundary, n_boundary, stream, nullptr, cols16, patterns);
+        if (rc) return rc;
+        if (j > 0) {
+            rc = hpcla_gmres_dots_f64(comm, U, ldu, j, u, nrows, state, g1, work, stream);
+            if (rc) return rc;
+            rc = hpcla_gmres_update_f64(comm, U, ldu, j, g1, u, nrows, k, ncv, nullptr, nullptr, state, work, stream);
+            if (rc) return rc;
+            rc = hpcla_gmres_dots_f64(comm, U, ldu, j, u, nrows, state, g2, work, stream);
+            if (rc) return rc;
+        }
+        rc = hpcla_svds_update_f64(comm, U, ldu, j, g2, u, nrows, k, ncv, 0, small_dev, state, work, stream);
+        if (rc) return rc;
+        rc = hpcla_gmres_next_f64(u, dv, nullptr, Uj, nullptr, nrows, state, stream);
+        if (rc) return rc;
+        rc = spmv_dist_impl<I>(split_fn, fused_fn, plan_t, rowptr_t, colval_t, nzval_t, Uj, nrows, v, nrows_t, nnz_t,
+                               index_base_t, interior_t, n_interior_t, boundary_t, n_boundary_t, stream, nullptr, cols16_t,
+                               patterns_t);
+        if (rc) return rc;
+        rc = hpcla_gmres_dots_f64(comm, V, ldv, j + 1, v, nrows_t, state, h1, work, stream);
+        if (rc) return rc;
+        rc = hpcla_gmres_update_f64(comm, V, ldv, j + 1, h1, v, nrows_t, k, ncv, nullptr, nullptr, state, work, stream);
+        if (rc) return rc;
+        rc = hpcla_gmres_dots_f64(comm, V, ldv, j + 1, v, nrows_t, state, h2, work, stream);
+        if (rc) return rc;
+        rc = hpcla_svds_update_f64(comm, V, ldv, j + 1, h2, v, nrows_t, k, ncv, 1, small_dev, state, work, stream);
+        if (rc) return rc;
+        rc = hpcla_gmres_next_f64(v, dv, nullptr, V + (int64_t)(j + 1) * ldv, nullptr, nrows_t, state, stream);
+        if (rc) return rc;
+    }
+    return HPCLA_OK;
+}
+
+HPCLA_API int hpcla_svds_steps_f64_i32(hpcla_comm_t *comm, hpcla_halo_plan_t *plan, const int32_t *rowptr,
+                                       const int32_t *colval_split, const int16_t *cols16,
+                                       const hpcla_block_patterns_t *patterns, const double *nzval, int64_t nrows, int64_t nnz,
+                                       int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                       const int32_t *boundary_blocks, int64_t n_boundary, hpcla_halo_plan_t *plan_t,
+                                       const int32_t *rowptr_t, const int32_t *colval_split_t, const int16_t *cols16_t,
+                                       const hpcla_block_patterns_t *patterns_t, const double *nzval_t, int64_t nrows_t,
+                                       int64_t nnz_t, int index_base_t, const int32_t *interior_blocks_t, int64_t n_interior_t,
+                                       const int32_t *boundary_blocks_t, int64_t n_boundary_t, double *U, int64_t ldu, double *V,
+                                       int64_t ldv, double *u, double *v, double *small_dev, void *work, int ncv, int first_col,
+                                       int count, int64_t first_iter, void *stream)
+{
+    return svds_steps_impl<int32_t>(spmv_split_i32, spmv_fused_i32, comm, plan, rowptr, colval_split, cols16, patterns, nzval,
+                                    nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks, n_boundary, plan_t,
+                                    rowptr_t, colval_split_t, cols16_t, patterns_t, nzval_t, nrows_t, nnz_t, index_base_t,
+                                    interior_blocks_t, n_interior_t, boundary_blocks_t, n_boundary_t, U, ldu, V, ldv, u, v,
+                                    small_dev, work, ncv, first_col, count, first_iter, stream);
+}
+
+HPCLA_API int hpcla_svds_steps_f64_i64(hpcla_comm_t *comm, hpcla_halo_plan_t *plan, const int64_t *rowptr,
+                                       const int64_t *colval_split, const double *nzval, int64_t nrows, int64_t nnz,
+                                       int index_base, const int32_t *interior_blocks, int64_t n_interior,
+                                       const int32_t *boundary_blocks, int64_t n_boundary, hpcla_halo_plan_t *plan_t,
+                                       const int64_t *rowptr_t, const int64_t *colval_split_t, const double *nzval_t,
+                                       int64_t nrows_t, int64_t nnz_t, int index_base_t, const int32_t *interior_blocks_t,
+                                       int64_t n_interior_t, const int32_t *boundary_blocks_t, int64_t n_boundary_t, double *U,
+                                       int64_t ldu, double *V, int64_t ldv, double *u, double *v, double *small_dev, void *work,
+                                       int ncv, int first_col, int count, int64_t first_iter, void *stream)
+{
+    return svds_steps_impl<int64_t>(spmv_split_i64, spmv_fused_i64, comm, plan, rowptr, colval_split, nullptr, nullptr, nzval,
+                                    nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks, n_boundary, plan_t,
+                                    rowptr_t, colval_split_t, nullptr, nullptr, nzval_t, nrows_t, nnz_t, index_base_t,
+                                    interior_blocks_t, n_interior_t, boundary_blocks_t, n_boundary_t, U, ldu, V, ldv, u, v,
+                                    small_dev, work, ncv, first_col, count, first_iter, stream);
+}

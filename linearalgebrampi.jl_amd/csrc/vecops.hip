@@ -2455,6 +2455,125 @@ HPCLA_API int hpcla_eigsh_update_f64(hpcla_comm_t *comm, const double *V, int64_
     return HPCLA_OK;
 }
 
+// ---- the Golub-Kahan step of hp.svds (thick-restart bidiagonalisation, full two-sided CGS2; hpcla_svds_steps_*) --------------
+// Column j of a cycle of m = ncv columns, iter 1-based over the whole solve, is two halves on two bases: the left half on U
+// (j columns: u = A V_j against U_0..U_{j-1}) and the right half on V (j + 1 columns: v = At U_j against V_0..V_j).  Each half
+// is gmres_dots, gmres_update (first pass), gmres_dots, then THIS second pass -- gmres_update_kernel<true> as it is (with
+// c == 0 columns it is the norm alone) and the small step of that side.  It keeps the projected matrix: B (m x m, column j at
+// B + j*m, upper triangle), beta (m):
+//   side 0   N   aa != aa  -> status 2 (breakdown), done_iter = iter - 1; nothing of column j is stored
+//            B[i, j] = g1[i] + g2[i], i < j;  B[j, j] = dv = sqrt(aa)
+//            Z   aa == 0   -> status 4 (invariant), done_iter = iter - 1: j finished triplets, column j of B is stored
+//   side 1   N'  bb != bb  -> status 2, done_iter = iter - 1; beta[j] is not stored
+//            beta[j] = dv = sqrt(bb)
+//            Z'  bb == 0   -> status 4, done_iter = iter: j + 1 finished triplets, beta[j] = 0 is stored
+// The host tells Z from Z' by done_iter and beta: with c = p + (done_iter - iterations before the cycle) finished columns the
+// gate was Z' when c > p and beta[c - 1] == 0, and Z otherwise (behind Z' at column c - 1 nothing runs, so a Z at column c
+// has a beta[c - 1] != 0 of this cycle, and c == p is a cycle whose first left half stopped).
+// gmres_next then writes U_j = u / dv or V_{j+1} = v / dv (gated: not behind a stop).
+struct SvdsSmall {
+    double *B, *beta, *g1, *g2, *h1, *h2, *aa, *bb, *dv;     // B: m x m;  beta, g1, g2, h1, h2: m;  aa, bb, dv: 1
+};
+
+static void svds_small_offsets(int m, int64_t off[10])          // off[9]: the buffer's length
+{
+    const int64_t len[9] = {(int64_t)m * m, m, m, m, m, m, 1, 1, 1};
+    off[0] = 0;
+    for (int i = 0; i < 9; ++i) off[i + 1] = off[i] + len[i];
+}
+
+static void svds_small_layout(int m, double *base, SvdsSmall *q)
+{
+    int64_t off[10];
+    svds_small_offsets(m, off);
+    *q = SvdsSmall{base + off[0], base + off[1], base + off[2], base + off[3], base + off[4],
+                   base + off[5], base + off[6], base + off[7], base + off[8]};
+}
+
+__device__ void svds_small_step(const SvdsSmall &q, int j, int m, int side, double nn, int64_t iter, int64_t *state)
+{
+    if (nn != nn) {                                              // gates N and N'
+        state[0] = iter - 1;
+        state[1] = PCG_BREAKDOWN;
+        return;
+    }
+    const double r = sqrt(nn);
+    if (side == 0) {
+        double *Bj = q.B + (int64_t)j * m;
+        for (int i = 0; i < j; ++i) Bj[i] = q.g1[i] + q.g2[i];
+        Bj[j] = r;
+    } else {
+        q.beta[j] = r;
+    }
+    q.dv[0] = r;
+    if (nn == 0.0) {                                             // gates Z and Z'
+        state[0] = side == 0 ? iter - 1 : iter;
+        state[1] = EIGSH_INVARIANT;
+    }
+}
+
+// second stage of the norm, one workgroup; runs the small step where no all-reduce follows (gate != 0)
+__global__ __launch_bounds__(RT) void svds_update_stage2_kernel(const double *__restrict__ partial, int np, SvdsSmall q, int j,
+                                                                int m, int side, int64_t iter, int gate,
+                                                                int64_t *__restrict__ state)
+{
+    if (state[1] != PCG_RUNNING) return;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < np; i += RT) acc = acc + partial[i];
+    const double nn = block_reduce<RED_SUM>(acc);
+    if (threadIdx.x == 0) {
+        (side == 0 ? q.aa : q.bb)[0] = nn;
+        if (gate) svds_small_step(q, j, m, side, nn, iter, state);
+    }
+}
+
+__global__ void svds_small_step_kernel(SvdsSmall q, int j, int m, int side, int64_t iter, int64_t *__restrict__ state)
+{
+    if (threadIdx.x == 0 && state[1] == PCG_RUNNING) svds_small_step(q, j, m, side, (side == 0 ? q.aa : q.bb)[0], iter, state);
+}
+
+// where the small arrays of hp.svds live in the solve's one buffer of doubles: which = 0 .. 8 for B, beta, g1, g2, h1, h2, aa,
+// bb, dv; which = 9: the buffer's length
+HPCLA_API int64_t hpcla_svds_small_offset(int ncv, int which)
+{
+    if (ncv < 1 || ncv > GMRES_MAX_RESTART || which < 0 || which > 9) return -1;
+    int64_t off[10];
+    svds_small_offsets(ncv, off);
+    return off[which];
+}
+
+// the second pass of one half of column j: w = w - W h, nn = w.w (one all-reduce), then the small step of that side.
+// side 0: W = U, ncols = j in 0..ncv-1 (0: the norm and the small step alone);  side 1: W = V, ncols = j + 1 in 1..ncv
+HPCLA_API int hpcla_svds_update_f64(hpcla_comm_t *comm, const double *W, int64_t ldw, int ncols, const double *h_dev, double *w,
+                                    int64_t n, int64_t iter, int ncv, int side, double *small_dev, int64_t *state_dev,
+                                    void *work, void *stream)
+{
+    if (side != 0 && side != 1) return set_error(HPCLA_ERR_INVALID, "svds_update: side must be 0 (left) or 1 (right)");
+    if (n < 0 || ldw < n || (ldw & 1) || ncv < 1 || ncv > GMRES_MAX_RESTART || iter < 1 || ncols < side ||
+        ncols > ncv - 1 + side)
+        return set_error(HPCLA_ERR_INVALID, "svds_update: negative size, odd or short pitch, bad column count or iteration < 1");
+    if (!state_dev || !small_dev || !work || (ncols > 0 && !h_dev))
+        return set_error(HPCLA_ERR_INVALID, "svds_update: null coefficients / state / small arrays / work");
+    if (n > 0 && (!w || (ncols > 0 && !W))) return set_error(HPCLA_ERR_INVALID, "svds_update: null vector");
+    if (bicg_misaligned({W, w})) return set_error(HPCLA_ERR_INVALID, "svds_update: vectors must be 16-byte aligned");
+    double *partial = reinterpret_cast<double *>(work);
+    const int g = reduce_grid(n);
+    const int j = ncols - side;
+    hipStream_t s = as_stream(stream);
+    SvdsSmall q;
+    svds_small_layout(ncv, small_dev, &q);
+    gmres_update_kernel<true><<<g, RT, 0, s>>>(W, ldw, ncols, h_dev, w, n, state_dev, partial);
+    HPCLA_CHECK_LAUNCH();
+    svds_update_stage2_kernel<<<1, RT, 0, s>>>(partial, g, q, j, ncv, side, iter, comm ? 0 : 1, state_dev);
+    HPCLA_CHECK_LAUNCH();
+    if (!comm) return HPCLA_OK;
+    const int rc = allreduce_on(comm, side == 0 ? q.aa : q.bb, 1, 0, stream);
+    if (rc) return rc;
+    svds_small_step_kernel<<<1, 64, 0, s>>>(q, j, ncv, side, iter, state_dev);
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
 // merge-combine: the five addition kernels of the reference (_copy_a_only_/_copy_b_only_/
 // _negate_b_only_/_add_both_/_sub_both_kernel!, src/sparse.jl:1258-1303) as ONE pass over the result:
 // entry i of the merged pattern takes a[ia[i]] (ia[i] >= 0) and/or b[ib[i]] (ib[i] >= 0); an entry that
