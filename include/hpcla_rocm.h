@@ -1380,6 +1380,30 @@ int hpcla_lobpcg_residual_f64(hpcla_comm_t *comm, const double *X, int64_t ldx, 
                               int64_t n, int k, double *rn2_dev, void *work, void *stream);
 int hpcla_lobpcg_combine_f64(double *S, int64_t lds, double *AS, int64_t ldas, const double *C_dev, int k, int c_rest,
                              int64_t n, void *stream);
+/* ---- tall-skinny Householder QR (hp.qr, hp.lstsq; csrc/qr.hip): X = Q R for a row-major n x k block, 1 <= k <= 32, by a
+ * communication-avoiding tree of Householder panel factorisations (TSQR).  Reflectors are stored and Q is formed by applying
+ * them, so Q'Q = I to rounding whatever the condition number of X is (no Gram matrix, no X inv(R)).
+ *   qr_panel_rows    P: the rows of a level-0 panel (one 256-lane workgroup, one lane per row).
+ *   qr_fan           F(k) = P / KT, KT = 4, 8, 16 or 32 >= k: the triangles a node of an upper level stacks (0 for a k outside 1..32).
+ *   qr_work_bytes    device bytes of `work` for nloc local rows on nranks ranks (tau and a k x k triangle per node of the rank's
+ *                    tree, two k x k blocks, and with nranks > 1 the (nranks k) x k stack and its tree); want_q does not raise it.
+ *   qr_f64           X: nloc rows on the pitch ldx (>= k), read only.  Q != NULL: nloc rows on the pitch ldq receive the panels'
+ *                    reflectors and then, in place, this rank's rows of Q; Q == NULL: R only, nothing of size nloc is written.
+ *                    R_dev: k x k on pitch k, upper triangular with exact zeros below and a non-negative diagonal (the signs
+ *                    go into Q).  Level 0 factors panels of P rows, level l >= 1 stacks F triangles of the level below, until
+ *                    one is left; partial panels are zero-padded, and a column whose sum of squares below the diagonal is
+ *                    exactly zero gets tau = 0.  comm with more than one rank: the rank's triangle (zero for nloc == 0) goes
+ *                    into its slot of a zeroed (nranks k) x k stack, ONE all-reduce (sum: every slot arrives bit-exact), and
+ *                    every rank factors the stack with the same code -- R has the same bits on every rank.  Every sum has an
+ *                    order fixed by (nloc, k): the same input gives the same bits on every call.  One launch per level and
+ *                    direction; no kernel waits on another workgroup.  Non-finite input propagates into R and Q.  Returns 0
+ *                    or a negative status; never aborts.  Bytes per row: 8k read, and with Q 24k more (reflectors written,
+ *                    read, Q written). */
+int hpcla_qr_panel_rows(void);
+int hpcla_qr_fan(int k);
+int64_t hpcla_qr_work_bytes(int64_t nloc, int k, int nranks, int want_q);
+int hpcla_qr_f64(hpcla_comm_t *comm, const double *X, int64_t ldx, int64_t nloc, int k, double *Q, int64_t ldq, double *R_dev,
+                 double *work, void *stream);
 int hpcla_divide_f64(const double *x, double a_host, double *y, int64_t n, void *stream);
 int hpcla_axpby_f64(double a, const double *x, double b, const double *y, double *z, int64_t n,
                     void *stream);

@@ -24,6 +24,8 @@ Layout
   svds.py            svds(): the largest singular triplets of a rectangular A by thick-restart Golub-Kahan bidiagonalisation on A
                      and its materialised transpose: the GMRES kernels on two bases, a small step of its own (svds_* kernels), the
                      eigensolver's rotate for both restarts
+  qr.py              qr(), lstsq(): tall-skinny Householder QR (TSQR) of a dense HPCMatrix of k <= 32 columns, Q formed from the
+                     stored reflectors, and dense least squares through the augmented block [X b] (csrc/qr.hip)
   indexing.py        v[a:b], X[r, c], A[r, c], A[:, k], diag(A) and SubmatrixPlan (csrc/submatrix.hip)
   transpose.py matmat.py addition.py repartition.py   the SURVEY 8f "next" rows and their plans
 
@@ -55,6 +57,7 @@ from .minres import MinresWorkspace, minres
 from .eigsh import EigshInfo, EigshWorkspace, eigsh
 from .lobpcg import LobpcgInfo, LobpcgWorkspace, lobpcg
 from .svds import SvdsInfo, SvdsWorkspace, svds
+from .qr import lstsq, qr
 from .convert import to_backend
 from .transpose import (HostTransposeStructure, TransposedHPCSparseMatrix, TransposedHPCVector, TransposePlan,
                         DenseTransposeLists, HostSpmmTPlan, adjoint, clear_transpose_plan_cache, get_transpose_plan,
