@@ -26,7 +26,7 @@ from typing import Optional, Tuple
 from . import _capi
 from .cg import CGInfo, _PairHistory, _residual_norms, _run_chunks, _solver_arguments, _stop_rule_or_done
 from .sparse import get_vector_plan, mul_
-from .vectors import HPCVector, current_stream_ptr, dptr, norm
+from .vectors import HPCVector, current_stream_ptr, dptr, norm, rd16_vector
 
 _STATUS = {0: "maxiter", 1: "converged", 2: "breakdown", 3: "converged"}     # 3: converged at the half step
 
@@ -79,7 +79,7 @@ def _bicgstab_dinv(A, b: HPCVector, M, name: str = "bicgstab") -> Optional[HPCVe
     if not isinstance(M, HPCVector):
         raise ValueError(f"{name}: M must be None, 'jacobi' or an HPCVector on A's row partition")
     b._same_partition(M)
-    return M
+    return rd16_vector(M)                                        # the step kernels read it 16 bytes at a time
 
 
 def bicgstab(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, atol: float = 0.0,

@@ -35,7 +35,7 @@ import numpy as np
 
 from . import _capi
 from .sparse import get_vector_plan, mul_, mul_dot_
-from .vectors import HPCVector, _Scratch, cg_direction_, cg_residual_, current_stream_ptr, dot, dptr, norm
+from .vectors import HPCVector, _Scratch, cg_direction_, cg_residual_, current_stream_ptr, dot, dptr, norm, rd16_vector
 
 
 def _torch():
@@ -349,7 +349,7 @@ def _cg_dinv(A, b: HPCVector, M) -> Optional[HPCVector]:
     if not isinstance(M, HPCVector):
         raise ValueError("cg: M must be None, 'jacobi' or an HPCVector on A's row partition")
     b._same_partition(M)
-    return M
+    return rd16_vector(M)                                        # the step kernels read it 16 bytes at a time
 
 
 def cg(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, atol: float = 0.0,

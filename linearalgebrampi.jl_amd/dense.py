@@ -69,9 +69,9 @@ class HPCMatrix:
         return self._scaled(float(a), divide=True)
 
     def _scaled(self, a: float, divide: bool) -> "HPCMatrix":
-        src = self.A if self.A.is_contiguous() else self.A.contiguous()
+        from .vectors import rd16, sfx_of
+        src = rd16(self.A if self.A.is_contiguous() else self.A.contiguous())     # the vector kernels' 16-byte accesses
         out = _torch().empty_like(src)
-        from .vectors import sfx_of
         if divide:
             _capi.call(f"hpcla_divide_{sfx_of(self.backend)}", dptr(src), a, dptr(out), src.numel(), current_stream_ptr())
         else:

@@ -44,7 +44,7 @@ from . import _capi
 from .backends import comm_bcast_bytes, comm_rank, comm_size
 from .partition import compute_partition_hash, uniform_partition
 from .sparse import get_vector_plan
-from .vectors import HPCVector, current_stream_ptr, dptr, f64_only, norm
+from .vectors import HPCVector, current_stream_ptr, dptr, f64_only, norm, rd16_vector
 
 _BREAKDOWN, _INVARIANT = 2, 4                               # the device's statuses next to 0 = running: include/hpcla_rocm.h
 _SMALL = ("T", "beta", "h1", "h2", "nn", "hn")
@@ -231,6 +231,7 @@ def eigsh(A, k: int = 6, which: str = "LA", ncv: Optional[int] = None, tol: floa
         v0 = HPCVector.from_global(np.random.default_rng(seed).uniform(-1.0, 1.0, n), A.backend, partition=A.row_partition)
     elif not isinstance(v0, HPCVector) or v0.structural_hash != compute_partition_hash(A.row_partition):
         raise ValueError("eigsh: v0 must be an HPCVector partitioned like the rows of A")
+    v0 = rd16_vector(v0)                                         # the start kernel reads it 16 bytes at a time
     ws = workspace if workspace is not None and workspace.fits(v0, m) else EigshWorkspace(v0, m)
     plan = get_vector_plan(A, ws.w)
     if plan.result_partition_hash != ws.w.structural_hash:

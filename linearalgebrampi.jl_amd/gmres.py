@@ -31,7 +31,7 @@ from . import _capi
 from .bicgstab import _bicgstab_dinv
 from .cg import CGInfo, _PairHistory, _residual_norms, _run_chunks, _solver_arguments, _stop_rule_or_done
 from .sparse import get_vector_plan
-from .vectors import HPCVector, current_stream_ptr, dptr, norm
+from .vectors import HPCVector, current_stream_ptr, dptr, norm, rd16_vector
 
 _STATUS = {0: "maxiter", 1: "converged", 2: "breakdown", 3: "converged"}     # 3: converged at a restart
 _SMALL = ("R", "c", "s", "g", "h1", "h2", "col", "y", "nn", "hn")
@@ -123,6 +123,7 @@ def gmres(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, a
     m = _check_restart(restart)
     if int(b.partition[-1]) != int(A.shape[0]):
         raise ValueError("gmres: b must be partitioned like the rows of A")
+    b = rd16_vector(b)                                           # every cycle's residual kernel reads b 16 bytes at a time
     ws = workspace if workspace is not None and workspace.fits(b, m) else GMRESWorkspace(b, m)
     plan = get_vector_plan(A, ws.x)
     if plan.result_partition_hash != ws.x.structural_hash:

@@ -188,7 +188,7 @@ def _minv(A, M):
     """The inverse-diagonal weights as an HPCVector on A's row partition, or None."""
     import math
     from .partition import compute_partition_hash
-    from .vectors import HPCVector, maximum, minimum
+    from .vectors import HPCVector, maximum, minimum, rd16_vector
     if M is None:
         return None
     if isinstance(M, str):
@@ -203,6 +203,7 @@ def _minv(A, M):
         return mag
     if not isinstance(M, HPCVector) or M.structural_hash != compute_partition_hash(A.row_partition):
         raise ValueError("lobpcg: M must be None, 'jacobi' or an HPCVector on A's row partition")
+    M = rd16_vector(M)                                           # one clone of misaligned weights for the check and the solve
     if not (minimum(M) > 0):
         raise ValueError("lobpcg: M must be positive definite (minimum(M) > 0)")
     return M

@@ -33,7 +33,7 @@ from . import _capi
 from .cg import CGInfo, _PairHistory, _residual_norms, _run_chunks, _solver_arguments, _STATUS
 from .partition import compute_partition_hash
 from .sparse import get_vector_plan, mul_
-from .vectors import HPCVector, current_stream_ptr, dot, dptr, maximum, minimum, norm
+from .vectors import HPCVector, current_stream_ptr, dot, dptr, maximum, minimum, norm, rd16_vector
 
 # slots of the scalar buffer (include/hpcla_rocm.h); _B2 is its reserved slot, used by the setup only (b.M b for a given x0)
 _BETA, _BB, _CS, _PHIBAR, _B2, _SCALARS = 0, 3, 5, 14, 15, 16
@@ -83,6 +83,7 @@ def _minres_dinv(A, b: HPCVector, M) -> Optional[HPCVector]:
     if not isinstance(M, HPCVector):
         raise ValueError("minres: M must be None, 'jacobi' or an HPCVector on A's row partition")
     b._same_partition(M)
+    M = rd16_vector(M)                                           # the check below and the step kernels read it 16 bytes at a time
     if not (minimum(M) > 0):
         raise ValueError("minres: M must be positive definite (minimum(M) > 0)")
     return M

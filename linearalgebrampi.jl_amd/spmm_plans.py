@@ -477,6 +477,9 @@ def spmm(A, B: HPCMatrix) -> HPCMatrix:
         return out
     s = current_stream_ptr()
     Bc = _rows_on_pitch(B.A, kw)
+    # a contiguous view 8 bytes off a 16-byte boundary is read where it is: the run tiles (16-byte staging only) are then not
+    # taken and the product goes to the kernels that have an 8-byte form
+    aligned = Bc.data_ptr() % 16 == 0
     if A.T == np.dtype(np.float32):
         _spmm_f32(A, plan, ent, Bc, C, k, s)
         return out
@@ -488,7 +491,7 @@ def spmm(A, B: HPCMatrix) -> HPCMatrix:
     if not _exchanges(ent):
         # every column owned: split indices == offsets into B's local rows
         sfx = "i64" if plan.is_i64 else "i32"
-        runs = _spmm_runs(A, plan, plan.rowptr_of(A), plan.colval_split, plan.is_i64) if k == 16 else None
+        runs = _spmm_runs(A, plan, plan.rowptr_of(A), plan.colval_split, plan.is_i64) if (k == 16 and aligned) else None
         if runs is not None:
             # banded / stencil structure: the blocks' B rows are staged as contiguous runs (csrc/spmm.hip, RUN TILES)
             _capi.call(f"hpcla_spmm_runs_k16_f64_{sfx}", dptr(plan.rowptr_of(A)), dptr(plan.colval_split), dptr(A.nzval),
@@ -498,12 +501,13 @@ def spmm(A, B: HPCMatrix) -> HPCMatrix:
         _capi.call(f"hpcla_spmm_csr_f64_{sfx}", dptr(plan.rowptr_of(A)), dptr(plan.colval_split),
                    dptr(A.nzval), dptr(Bc), kw, _capi.LAYOUT_ROW, dptr(Cbuf), kw, _capi.LAYOUT_ROW,
                    A.nrows_local, A.nnz, k, 0, s)
-        _spmm_block_order(A, plan, plan.rowptr_of(A), plan.colval_split, plan.is_i64, Bc, None, Cbuf, k, None, kw)
+        if aligned:                  # (an order measured on the 8-byte kernel would stay cached for the aligned products)
+            _spmm_block_order(A, plan, plan.rowptr_of(A), plan.colval_split, plan.is_i64, Bc, None, Cbuf, k, None, kw)
         return out
     colval_split, ghost = ent.colval_split, ent.ghost
     sfx = "i64" if ent.is_i64 else "i32"
     rowptr = ent.rowptr(A, plan)
-    runs = _spmm_runs(A, plan, rowptr, colval_split, ent.is_i64) if (k == 16 and ghost) else None
+    runs = _spmm_runs(A, plan, rowptr, colval_split, ent.is_i64) if (k == 16 and ghost and aligned) else None
 
     def blocks_launch(blocks):
         if runs is not None:
@@ -524,6 +528,7 @@ def spmm(A, B: HPCMatrix) -> HPCMatrix:
     if runs is not None:
         return out
     # (local launches only -- no exchange: the ranks need not agree on the order, every order is a bijection)
-    _spmm_block_order(A, plan, rowptr, colval_split, ent.is_i64, Bc, ghost, Cbuf, k,
-                      ent.boundary if ent.boundary.numel() >= ent.interior.numel() else ent.interior, kw)
+    if aligned:
+        _spmm_block_order(A, plan, rowptr, colval_split, ent.is_i64, Bc, ghost, Cbuf, k,
+                          ent.boundary if ent.boundary.numel() >= ent.interior.numel() else ent.interior, kw)
     return out

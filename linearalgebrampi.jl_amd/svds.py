@@ -59,7 +59,7 @@ from .lsqr import _matrix_block
 from .partition import compute_partition_hash, uniform_partition
 from .sparse import get_vector_plan
 from .transpose import TransposedHPCSparseMatrix
-from .vectors import HPCVector, current_stream_ptr, dptr, f64_only, norm
+from .vectors import HPCVector, current_stream_ptr, dptr, f64_only, norm, rd16_vector
 
 _BREAKDOWN, _INVARIANT = 2, 4                               # the device's statuses next to 0 = running: include/hpcla_rocm.h
 _SMALL = ("B", "beta", "g1", "g2", "h1", "h2", "aa", "bb", "dv")
@@ -242,6 +242,7 @@ def svds(A, k: int = 6, which: str = "LM", ncv: Optional[int] = None, tol: float
         v0 = HPCVector.from_global(np.random.default_rng(seed).uniform(-1.0, 1.0, N), backend, partition=A.col_partition)
     elif not isinstance(v0, HPCVector) or v0.structural_hash != compute_partition_hash(A.col_partition):
         raise ValueError("svds: v0 must be an HPCVector partitioned like the columns of A")
+    v0 = rd16_vector(v0)                                         # the start kernel reads it 16 bytes at a time
     At = TransposedHPCSparseMatrix(A).materialize()
     ws = workspace if workspace is not None and workspace.fits(A, m) else SvdsWorkspace(A, m)
     plan, plan_t = get_vector_plan(A, ws.v), get_vector_plan(At, ws.u)

@@ -43,6 +43,41 @@ def dptr(t) -> ctypes.c_void_p:
     return ctypes.c_void_p(t.data_ptr())
 
 
+def rd16(t):
+    """A read-only operand of a 16-byte (double2 / four-float) vector kernel: ``t`` itself when its device pointer is
+    16-byte aligned -- one integer test, nothing else -- and otherwise a device clone in fresh storage (one copy).  The
+    constructors keep a caller's tensor as it is, so a view such as ``buf[1:1 + n]`` arrives here 8 bytes off; the C ABI
+    refuses such a pointer (HPCLA_ERR_INVALID) and has no 8-byte form of these kernels.
+
+    Keep the returned tensor in a local until the library call has been enqueued: a clone that is dropped earlier goes back to
+    the caching allocator, and the next clone of the same call may be handed its memory."""
+    if t is None or not (t.data_ptr() & 15):
+        return t
+    return t.clone()
+
+
+def wr16(t):
+    """A written (or read and written) operand of a 16-byte vector kernel: ``(w, land)``.  Aligned: ``w`` is ``t`` and
+    ``land()`` does nothing.  Otherwise ``w`` is an aligned scratch holding t's values and ``land()`` copies it back into
+    the caller's tensor on the current stream, so the caller's buffer still receives the result (aliasing is kept)."""
+    if not (t.data_ptr() & 15):
+        return t, _nothing
+    w = t.clone()
+    return w, lambda: t.copy_(w)
+
+
+def _nothing():
+    return None
+
+
+def rd16_vector(v):
+    """An HPCVector operand a solver only reads (``b``, ``x0``, a start vector, inverse-diagonal weights), on an aligned
+    buffer: ``v`` itself when it is, else the same vector around a device clone.  None and strings pass through."""
+    if not isinstance(v, HPCVector) or v.v.device.type != "cuda" or not (v.v.data_ptr() & 15):
+        return v
+    return HPCVector(v.structural_hash, v.partition, v.v.clone(), v.backend)
+
+
 def sfx_of(backend: HPCBackend) -> str:
     """Suffix of the C entry points for the backend's element type (``_f64`` kernels, or csrc/f32.hip's ``_f32``)."""
     return "f32" if backend.T == np.dtype(np.float32) else "f64"
@@ -180,7 +215,10 @@ class HPCVector:
     def _axpby(self, a: float, other: "HPCVector", b: float) -> "HPCVector":
         other = self._aligned(other)
         out = self.similar()
-        _capi.call(f"hpcla_axpby_{sfx_of(self.backend)}", float(a), dptr(self.v), float(b), dptr(other.v), dptr(out.v),
+        xv, yv = self.v, other.v
+        if sfx_of(self.backend) == "f32":       # four-float accesses; the Float64 entry is a scalar kernel and takes any pointer
+            xv, yv = rd16(xv), rd16(yv)
+        _capi.call(f"hpcla_axpby_{sfx_of(self.backend)}", float(a), dptr(xv), float(b), dptr(yv), dptr(out.v),
                    self.local_length, current_stream_ptr())
         return out
 
@@ -197,7 +235,8 @@ class HPCVector:
         if isinstance(a, HPCVector):
             return NotImplemented
         out = self.similar()
-        _capi.call(f"hpcla_scale_{sfx_of(self.backend)}", float(a), dptr(self.v), dptr(out.v), self.local_length,
+        x = rd16(self.v)
+        _capi.call(f"hpcla_scale_{sfx_of(self.backend)}", float(a), dptr(x), dptr(out.v), self.local_length,
                    current_stream_ptr())
         return out
 
@@ -205,7 +244,8 @@ class HPCVector:
 
     def __truediv__(self, a):
         out = self.similar()
-        _capi.call(f"hpcla_divide_{sfx_of(self.backend)}", dptr(self.v), float(a), dptr(out.v), self.local_length,
+        x = rd16(self.v)
+        _capi.call(f"hpcla_divide_{sfx_of(self.backend)}", dptr(x), float(a), dptr(out.v), self.local_length,
                    current_stream_ptr())
         return out
 
@@ -214,16 +254,20 @@ class HPCVector:
         """self .= self .+ (a*num/den) .* x ; num/den optional device scalars (1-element tensors)."""
         self._same_partition(x)
         f64_only(self.backend, "axpy_")
-        _capi.call("hpcla_axpy_f64", float(a), dptr(num), dptr(den), dptr(x.v), dptr(self.v),
+        (y, land), xv = wr16(self.v), rd16(x.v)
+        _capi.call("hpcla_axpy_f64", float(a), dptr(num), dptr(den), dptr(xv), dptr(y),
                    self.local_length, current_stream_ptr())
+        land()
         return self
 
     def xpay_(self, x: "HPCVector", a: float, num=None, den=None) -> "HPCVector":
         """self .= x .+ (a*num/den) .* self."""
         self._same_partition(x)
         f64_only(self.backend, "xpay_")
-        _capi.call("hpcla_xpay_f64", dptr(x.v), float(a), dptr(num), dptr(den), dptr(self.v),
+        (y, land), xv = wr16(self.v), rd16(x.v)
+        _capi.call("hpcla_xpay_f64", dptr(xv), float(a), dptr(num), dptr(den), dptr(y),
                    self.local_length, current_stream_ptr())
+        land()
         return self
 
 
@@ -234,8 +278,10 @@ def cg_update_(x: HPCVector, r: HPCVector, p: HPCVector, Ap: HPCVector, a: float
     x._same_partition(r), x._same_partition(p), x._same_partition(Ap)
     f64_only(x.backend, "cg_update_")
     work, _ = _Scratch.get(x.v.device)
-    _capi.call("hpcla_cg_update_f64", x.backend.rccl, float(a), dptr(num), dptr(den), dptr(p.v), dptr(Ap.v),
-               dptr(x.v), dptr(r.v), x.local_length, dptr(rr_out), dptr(work), current_stream_ptr())
+    (xw, land_x), (rw, land_r), pv, qv = wr16(x.v), wr16(r.v), rd16(p.v), rd16(Ap.v)
+    _capi.call("hpcla_cg_update_f64", x.backend.rccl, float(a), dptr(num), dptr(den), dptr(pv), dptr(qv),
+               dptr(xw), dptr(rw), x.local_length, dptr(rr_out), dptr(work), current_stream_ptr())
+    land_x(), land_r()
     return rr_out
 
 
@@ -244,8 +290,10 @@ def cg_residual_(r: HPCVector, Ap: HPCVector, a: float, num, den, rr_out):
     r._same_partition(Ap)
     f64_only(r.backend, "cg_residual_")
     work, _ = _Scratch.get(r.v.device)
-    _capi.call("hpcla_cg_residual_f64", r.backend.rccl, float(a), dptr(num), dptr(den), dptr(Ap.v), dptr(r.v),
+    (rw, land), qv = wr16(r.v), rd16(Ap.v)
+    _capi.call("hpcla_cg_residual_f64", r.backend.rccl, float(a), dptr(num), dptr(den), dptr(qv), dptr(rw),
                r.local_length, dptr(rr_out), dptr(work), current_stream_ptr())
+    land()
     return rr_out
 
 
@@ -254,8 +302,10 @@ def cg_direction_(x: HPCVector, p: HPCVector, r: HPCVector, a: float, a_num, a_d
     deferred x update of a CG iteration rides on the direction update, which reads the same p."""
     x._same_partition(p), x._same_partition(r)
     f64_only(x.backend, "cg_direction_")
+    (xw, land_x), (pw, land_p), rv = wr16(x.v), wr16(p.v), rd16(r.v)
     _capi.call("hpcla_cg_direction_f64", float(a), dptr(a_num), dptr(a_den), float(b), dptr(b_num), dptr(b_den),
-               dptr(r.v), dptr(x.v), dptr(p.v), x.local_length, current_stream_ptr())
+               dptr(rv), dptr(xw), dptr(pw), x.local_length, current_stream_ptr())
+    land_x(), land_p()
 
 
 def HPCVector_local(v_local, backend: HPCBackend) -> HPCVector:
@@ -287,14 +337,16 @@ def _reduce(kind: str, x: HPCVector, y: Optional[HPCVector], out=None):
     comm = x.backend.rccl
     s = current_stream_ptr()
     t = sfx_of(x.backend)                  # Float32 operands: the scalar is still formed and all-reduced in double (f32.hip)
+    xv = rd16(x.v)
     if kind == "dot":
-        _capi.call(f"hpcla_dot_{t}", comm, dptr(x.v), dptr(y.v), x.local_length, dptr(out), dptr(work), s)
+        yv = xv if y.v is x.v else rd16(y.v)
+        _capi.call(f"hpcla_dot_{t}", comm, dptr(xv), dptr(yv), x.local_length, dptr(out), dptr(work), s)
     elif kind == "nrm2sq":
-        _capi.call(f"hpcla_nrm2sq_{t}", comm, dptr(x.v), x.local_length, dptr(out), dptr(work), s)
+        _capi.call(f"hpcla_nrm2sq_{t}", comm, dptr(xv), x.local_length, dptr(out), dptr(work), s)
     elif kind == "asum":
-        _capi.call(f"hpcla_asum_{t}", comm, dptr(x.v), x.local_length, dptr(out), dptr(work), s)
+        _capi.call(f"hpcla_asum_{t}", comm, dptr(xv), x.local_length, dptr(out), dptr(work), s)
     elif kind == "amax":
-        _capi.call(f"hpcla_amax_{t}", comm, dptr(x.v), x.local_length, dptr(out), dptr(work), s)
+        _capi.call(f"hpcla_amax_{t}", comm, dptr(xv), x.local_length, dptr(out), dptr(work), s)
     else:  # pragma: no cover
         raise ValueError(kind)
     return out
@@ -304,7 +356,8 @@ def vsum(v: HPCVector, out=None):
     """``sum(v)`` (src/vectors.jl:838-845)."""
     work, scal = _Scratch.get(v.v.device)
     r = out if out is not None else scal[:1]
-    _capi.call(f"hpcla_sum_{sfx_of(v.backend)}", v.backend.rccl, dptr(v.v), v.local_length, dptr(r), dptr(work),
+    xv = rd16(v.v)
+    _capi.call(f"hpcla_sum_{sfx_of(v.backend)}", v.backend.rccl, dptr(xv), v.local_length, dptr(r), dptr(work),
                current_stream_ptr())
     return r if out is not None else _round_to(v.backend, _host_scalar(r, v.backend))
 
@@ -313,13 +366,15 @@ def prod(v: HPCVector) -> float:
     """``prod(v)`` (src/vectors.jl:853-858): local product (1 for an empty part), then an all-reduce with ``*``."""
     f64_only(v.backend, "prod")
     work, scal = _Scratch.get(v.v.device)
-    _capi.call("hpcla_prod_f64", v.backend.rccl, dptr(v.v), v.local_length, dptr(scal[:1]), dptr(work), current_stream_ptr())
+    xv = rd16(v.v)
+    _capi.call("hpcla_prod_f64", v.backend.rccl, dptr(xv), v.local_length, dptr(scal[:1]), dptr(work), current_stream_ptr())
     return _host_scalar(scal[:1], v.backend)
 
 
 def _maxval(v: HPCVector, negate: int) -> float:
     work, scal = _Scratch.get(v.v.device)
-    _capi.call(f"hpcla_maxval_{sfx_of(v.backend)}", v.backend.rccl, dptr(v.v), v.local_length, negate, dptr(scal[:1]), dptr(work),
+    xv = rd16(v.v)
+    _capi.call(f"hpcla_maxval_{sfx_of(v.backend)}", v.backend.rccl, dptr(xv), v.local_length, negate, dptr(scal[:1]), dptr(work),
                current_stream_ptr())
     return _host_scalar(scal[:1], v.backend)
 
@@ -361,6 +416,7 @@ def norm(v: HPCVector, p: float = 2, out=None):
     f64_only(v.backend, "norm(v, p) for p other than 1, 2, Inf")
     work, scal = _Scratch.get(v.v.device)                                        # general p (:774-779)
     r = out if out is not None else scal[:1]
-    _capi.call("hpcla_powsum_f64", v.backend.rccl, dptr(v.v), v.local_length, float(p), dptr(r), dptr(work),
+    xv = rd16(v.v)
+    _capi.call("hpcla_powsum_f64", v.backend.rccl, dptr(xv), v.local_length, float(p), dptr(r), dptr(work),
                current_stream_ptr())
     return r if out is not None else _host_scalar(r, v.backend) ** (1.0 / p)

@@ -19,6 +19,11 @@ import math
 import numpy as np
 
 CG_RTOL = 1e-12            # the project's CG history margin (tests/test_gpu_parity.py)
+# The stop rules test the RECURRENCE's residual; the convergence tests hold the TRUE residual (||b - A x||, an eigen or singular
+# residual), computed from the returned x, to this many times the rule's limit -- at their rtol = 1e-8: 2e-8 ||b||
+TRUE_RES_RTOL = 2e-8       # cg, bicgstab, gmres, lsqr: ||b - A x|| / ||b|| of a solve that converged at rtol = 1e-8
+TRUE_RES_FACTOR = 2.0      # minres, eigsh, svds, lobpcg: the true residual in units of their own limit (rtol ||b||_M, tol anorm); a
+#                            bound of its own: changing one of the two does not move the other
 SEED_SCALE = 0xD1A6
 SEED_RHS = 0xBEEF
 SIZES = [(16, 16), (24, 20), (33, 31)]

@@ -360,14 +360,14 @@ def test_convergence_on_the_convection_diffusion_cases(hp, cases, gpu_backend_i3
         print(f"{size} {name}: iterations {info.iterations} (restatement {its_ref}), true residual {true:.3e}")
         assert info.converged and info.status == "converged" and status_ref == "converged"
         assert len(info.residual_norms) == info.iterations + 1
-        assert true <= 2e-8
+        assert true <= pc.TRUE_RES_RTOL
         if name == "jacobi":
             assert abs(info.iterations - its_ref) <= 2
         its[name] = info.iterations
     assert 2 * its["jacobi"] <= its["none"], its
     x0 = hp.HPCVector.from_global(np.full(n, 1e-3), gpu_backend_i32)
     x, info = hp.bicgstab(A, b, x0=x0, rtol=1e-8, M="jacobi")
-    assert info.converged and hp.norm(b - A @ x) / bnorm <= 2e-8
+    assert info.converged and hp.norm(b - A @ x) / bnorm <= pc.TRUE_RES_RTOL
     hp.clear_plan_cache()
 
 

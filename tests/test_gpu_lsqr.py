@@ -349,7 +349,7 @@ def _check_answer(c, damp, xv, info, ref):
     if info.status == "converged":
         true = np.linalg.norm(b - dense @ xv) / np.linalg.norm(b)
         line += f", true relative residual {true:.2e}"
-        assert true <= 2e-8
+        assert true <= pc.TRUE_RES_RTOL
     else:
         normal = np.linalg.norm(Ab.T @ rbar) / (np.linalg.norm(Ab) * rn)
         rel = abs(info.residual_norms[-1] - rn) / rn
@@ -378,7 +378,7 @@ def test_convergence_on_the_tall_and_wide_cases(hp, cases, gpu_backend_i32, size
     x0 = hp.HPCVector.from_global(np.full(case[3], 1e-3), gpu_backend_i32)
     x, info = hp.lsqr(mats["wide"], b, x0=x0)
     assert info.converged and info.status == "converged"
-    assert np.linalg.norm(case[4] - c["dense"] @ x.local_values()) <= 2e-8 * np.linalg.norm(case[4])
+    assert np.linalg.norm(case[4] - c["dense"] @ x.local_values()) <= pc.TRUE_RES_RTOL * np.linalg.norm(case[4])
     # the lazy transpose of the wide matrix is the tall one
     tcase = cases["tall", size]["case"]
     for rp, ci in ((tcase[0], tcase[1]), (case[0], case[1])):

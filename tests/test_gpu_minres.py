@@ -253,7 +253,7 @@ def test_convergence_counts_and_answers(hp, cases, gpu_backend_i32, gpu_backend_
         assert len(hist) == info.iterations + 1 and all(h1 <= h0 for h0, h1 in zip(hist, hist[1:]))
         assert hist[-1] <= limit < hist[-2]
         assert err <= 10 * err_ref, (key, err, err_ref)
-        assert true <= 2.0, (key, true)
+        assert true <= pc.TRUE_RES_FACTOR, (key, true)
     hp.clear_plan_cache()
 
 
