@@ -1380,6 +1380,27 @@ int hpcla_lobpcg_residual_f64(hpcla_comm_t *comm, const double *X, int64_t ldx, 
                               int64_t n, int k, double *rn2_dev, void *work, void *stream);
 int hpcla_lobpcg_combine_f64(double *S, int64_t lds, double *AS, int64_t ldas, const double *C_dev, int k, int c_rest,
                              int64_t n, void *stream);
+/* ---- the block eigensolver on a pencil (hp.lobpcg with B; csrc/lobpcg.hip): A x = lambda B x, B symmetric positive definite.
+ * The reference has no eigensolver, so these entries have no counterpart there either.  The host keeps a third block
+ * BS = [BX BW BP] next to S and AS, takes [S'AS | S'BS] from ONE hpcla_gram_f64 of S against [AS | BS], and applies
+ * lobpcg_combine a second time to BS (AS == NULL).  Blocks, pitches and alignment as above.  1 <= k <= 16.
+ *   lobpcg_residual_gen  per element, separately rounded:  t = theta_dev[j] * BX[r,j];  d = AX[r,j] - t;  w = minv[r] * d
+ *                    (minv == NULL: w = d);  W[r,j] = w;  W2 != NULL: W2[r,j] = w (the SpMM's operand on spmm_pitch);
+ *                    bdiag != NULL (a diagonal B, given together with BW or not at all): BW[r,j] = bdiag[r] * w, so B W
+ *                    needs no product.  Padding columns of any block are neither read nor written.  Three sums per column,
+ *                    16 apart:  sums_dev[j] = sum_r d[r,j]^2 (the residual before minv),  sums_dev[16 + j] = sum_r AX[r,j]^2,
+ *                    sums_dev[32 + j] = sum_r BX[r,j]^2;  the entries j >= k of a group are not written (with comm != NULL
+ *                    they take part in the reduction).  The summation order is lobpcg_residual's -- chunks of
+ *                    hpcla_lobpcg_chunk_rows(n) rows, 16 phases of ascending chunks, the phases ascending, a function of
+ *                    (n, k) only: the same inputs give the same bits on every call -- then ONE all-reduce of the 48 doubles
+ *                    (comm != NULL).  n == 0: the 3k sums are zero and the rank still reduces; no pointer but sums_dev is
+ *                    looked at.  work: hpcla_lobpcg_gen_work_bytes(n, k) device bytes.  Bytes per row: read 16k (+8 with
+ *                    minv, +8 with bdiag), write 8k per output block (W, W2, BW). */
+int64_t hpcla_lobpcg_gen_work_bytes(int64_t n, int k);
+int hpcla_lobpcg_residual_gen_f64(hpcla_comm_t *comm, const double *AX, int64_t ldax, const double *BX, int64_t ldbx,
+                                  const double *theta_dev, const double *minv, const double *bdiag, double *W, int64_t ldw,
+                                  double *W2, int64_t ldw2, double *BW, int64_t ldbw, int64_t n, int k, double *sums_dev,
+                                  void *work, void *stream);
 /* ---- tall-skinny Householder QR (hp.qr, hp.lstsq; csrc/qr.hip): X = Q R for a row-major n x k block, 1 <= k <= 32, by a
  * communication-avoiding tree of Householder panel factorisations (TSQR).  Reflectors are stored and Q is formed by applying
  * them, so Q'Q = I to rounding whatever the condition number of X is (no Gram matrix, no X inv(R)).

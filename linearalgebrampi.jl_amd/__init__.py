@@ -20,7 +20,8 @@ Layout
   eigsh.py           eigsh(): extreme eigenpairs of a symmetric A by thick-restart Lanczos on the GMRES kernels; the restart
                      rotates the basis in place in one pass (csrc/eigsh.hip)
   lobpcg.py          lobpcg(): the k <= 16 smallest or largest eigenpairs with their multiplicities by LOBPCG (optionally
-                     Jacobi-preconditioned): the SpMM, one Gram pass, a host Rayleigh-Ritz, two block kernels (csrc/lobpcg.hip)
+                     Jacobi-preconditioned), of A or of the pencil A x = lambda B x (B sparse SPD, or positive weights): the SpMM,
+                     one Gram pass, a host Rayleigh-Ritz, the block kernels of csrc/lobpcg.hip
   svds.py            svds(): the largest singular triplets of a rectangular A by thick-restart Golub-Kahan bidiagonalisation on A
                      and its materialised transpose: the GMRES kernels on two bases, a small step of its own (svds_* kernels), the
                      eigensolver's rotate for both restarts

@@ -230,6 +230,10 @@ _SIGNATURES = {
     "hpcla_lobpcg_work_bytes": [_i64, _i32],
     "hpcla_lobpcg_residual_f64": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp],
     "hpcla_lobpcg_combine_f64": [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _i64, _vp],
+    # the same for the pencil A x = lambda B x: three sums per column, B W of a diagonal B
+    "hpcla_lobpcg_gen_work_bytes": [_i64, _i32],
+    "hpcla_lobpcg_residual_gen_f64": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp,
+                                      _vp],
     # tall-skinny Householder QR (hp.qr, hp.lstsq): the tree's constants, its workspace, the factorisation (csrc/qr.hip)
     "hpcla_qr_panel_rows": [],
     "hpcla_qr_fan": [_i32],
@@ -351,6 +355,7 @@ _RESTYPES = {
     "hpcla_svds_small_offset": _i64,
     "hpcla_lobpcg_chunk_rows": _i64,
     "hpcla_lobpcg_work_bytes": _i64,
+    "hpcla_lobpcg_gen_work_bytes": _i64,
     "hpcla_qr_work_bytes": _i64,
 }
 

@@ -1,8 +1,10 @@
-// lobpcg.hip -- the two tall-block kernels of the block eigensolver (hp.lobpcg): the residual block with its column norms, and
-// the in-place combine [X | P] <- S C of the Rayleigh-Ritz step.
+// lobpcg.hip -- the tall-block kernels of the block eigensolver (hp.lobpcg): the residual block with its column norms (one
+// kernel for A x = lambda x, one for the pencil A x = lambda B x), and the in-place combine [X | P] <- S C of the Rayleigh-Ritz
+// step.
 //
 // Every block is row-major: row r of a block is k doubles at a pitch (in doubles) of its own, so the blocks may be column
-// ranges of one wider buffer -- the solver keeps [X W P | AX AW AP] in one (n, 6k) buffer.  1 <= k <= 16.
+// ranges of one wider buffer -- the solver keeps [X W P | AX AW AP] in one (n, 6k) buffer, and [X W P | AX AW AP | BX BW BP]
+// in one (n, 9k) buffer with a B.  1 <= k <= 16.
 //
 // RESIDUAL.  t = theta[j] * X[r,j];  d = AX[r,j] - t;  W[r,j] = minv[r] * d (or d): three separately rounded operations
 // (-ffp-contract=off).  A lane owns a (row, column pair): with even pitches and 16-byte aligned bases a pair is one 16-byte
@@ -14,6 +16,18 @@
 // adds the chunks the same way (LOB_PHASES phases of ascending chunks, then the phases ascending).  Every order is fixed by
 // (n, k): the same inputs give the same bits on every call.  Then one all-reduce of the k sums (allreduce_on, comm.hip).
 // Bytes per row: read 8 (2k + 1 with minv), write 8k (16k with the second copy of W, which the SpMM reads on its own pitch).
+//
+// RESIDUAL OF THE PENCIL (lobpcg_residual_gen_kernel).  t = theta[j] * BX[r,j];  d = AX[r,j] - t;  w = minv[r] * d (or d);
+// W[r,j] = w;  W2[r,j] = w (if given);  BW[r,j] = bdiag[r] * w (if B is a diagonal: B W needs no product then): every operation
+// separately rounded.  Three sums per column, sum d^2, sum AX^2 and sum BX^2: the stop rule of the pencil,
+// ||A x - theta B x|| <= tol (||A x|| + |theta| ||B x||), takes all four norms from this one pass.  Mapping, chunking and both
+// fixed summation orders are those of the kernel above with three accumulators per column: a lane's rows ascending, the slots
+// through LDS in LOB_PHASES phases into partial[chunk][3][k], one workgroup over the chunks (a lane adds the three groups side by side, so
+// the loads of a chunk are one chain and not three), then ONE all-reduce of 48 doubles (group q at sums + 16 q; the entries j >= k of a group are not written by the
+// kernels).  LDS 18 KiB per workgroup of four waves would allow eight workgroups per CU; the six accumulators and the two
+// unrolled rows in flight take 80 VGPRs (78 on the 8-byte path), no spill, so the registers bound it at six waves per SIMD,
+// 24 per CU, which a streaming kernel of this kind does not feel (the kernel above: 52 VGPRs, eight waves).
+// Bytes per row: read 16k (+8 with minv, +8 with bdiag), write 8k per output block (W, W2, BW).
 //
 // COMBINE.  S = [X W P] holds k + c_rest input columns (c_rest = 0: X alone; k: [X W]; 2k: [X W P]); C is (k + c_rest) x k,
 // row i at C + 16 i.  Per row and output column j
@@ -144,6 +158,127 @@ __global__ __launch_bounds__(LOB_THREADS) void lobpcg_residual_stage2(const doub
         double s = ph[0][tid];
         for (int g = 1; g < LOB_PHASES; ++g) s = s + ph[g][tid];
         out[tid] = s;
+    }
+}
+
+// ---- residual of the pencil (A, B) ------------------------------------------------------------------------------------------
+constexpr int LOB_GEN_SUMS = 3;                // sum d^2, sum AX^2, sum BX^2 per column
+
+template <bool VEC>
+__global__ __launch_bounds__(LOB_THREADS) void lobpcg_residual_gen_kernel(const double *__restrict__ AX, int64_t ldax,
+                                                                          const double *__restrict__ BX, int64_t ldbx,
+                                                                          const double *__restrict__ theta,
+                                                                          const double *__restrict__ minv,
+                                                                          const double *__restrict__ bdiag, double *__restrict__ W,
+                                                                          int64_t ldw, double *__restrict__ W2, int64_t ldw2,
+                                                                          double *__restrict__ BW, int64_t ldbw, int64_t n, int k,
+                                                                          int64_t rows_per_chunk, double *__restrict__ partial)
+{
+    __shared__ double red[LOB_GEN_SUMS][LOB_THREADS][2];
+    __shared__ double ph[LOB_GEN_SUMS][LOB_PHASES][LOB_MAX_K];
+    const int tid = threadIdx.x;
+    const int kp = (k + 1) >> 1;                     // column pairs of a row
+    const int RP = LOB_THREADS / kp;                 // rows of one pass of the workgroup
+    const int slot = tid / kp, c = tid - slot * kp;
+    const int j0 = 2 * c;
+    const bool two = j0 + 1 < k;                     // the pair's second column exists
+    const int64_t r0 = (int64_t)blockIdx.x * rows_per_chunk;
+    const int64_t r1 = min(n, r0 + rows_per_chunk);
+    double d0 = 0.0, d1 = 0.0, a0 = 0.0, a1 = 0.0, b0 = 0.0, b1 = 0.0;
+    if (slot < RP) {
+        const double th0 = theta[j0], th1 = two ? theta[j0 + 1] : 0.0;
+#pragma unroll 2
+        for (int64_t r = r0 + slot; r < r1; r += RP) {
+            double x0, x1 = 0.0, y0, y1 = 0.0;       // x: B X, y: A X
+            if (VEC && two) {
+                const double2 xv = *reinterpret_cast<const double2 *>(BX + r * ldbx + j0);
+                const double2 yv = *reinterpret_cast<const double2 *>(AX + r * ldax + j0);
+                x0 = xv.x, x1 = xv.y, y0 = yv.x, y1 = yv.y;
+            } else {
+                x0 = BX[r * ldbx + j0], y0 = AX[r * ldax + j0];
+                if (two) x1 = BX[r * ldbx + j0 + 1], y1 = AX[r * ldax + j0 + 1];
+            }
+            const double t0 = th0 * x0, t1 = th1 * x1;
+            double w0 = y0 - t0, w1 = y1 - t1;
+            d0 = d0 + w0 * w0;                       // the norms are those of A X - B X diag(theta), not of M .* R
+            a0 = a0 + y0 * y0;
+            b0 = b0 + x0 * x0;
+            if (two) {
+                d1 = d1 + w1 * w1;
+                a1 = a1 + y1 * y1;
+                b1 = b1 + x1 * x1;
+            }
+            if (minv) {
+                const double mi = minv[r];
+                w0 = mi * w0, w1 = mi * w1;
+            }
+            if (VEC && two) {
+                *reinterpret_cast<double2 *>(W + r * ldw + j0) = make_double2(w0, w1);
+                if (W2) *reinterpret_cast<double2 *>(W2 + r * ldw2 + j0) = make_double2(w0, w1);
+            } else {
+                W[r * ldw + j0] = w0;
+                if (two) W[r * ldw + j0 + 1] = w1;
+                if (W2) {
+                    W2[r * ldw2 + j0] = w0;
+                    if (two) W2[r * ldw2 + j0 + 1] = w1;
+                }
+            }
+            if (bdiag) {                             // a diagonal B: B W is a row scaling of what was just stored
+                const double bd = bdiag[r];
+                const double v0 = bd * w0, v1 = bd * w1;
+                if (VEC && two) {
+                    *reinterpret_cast<double2 *>(BW + r * ldbw + j0) = make_double2(v0, v1);
+                } else {
+                    BW[r * ldbw + j0] = v0;
+                    if (two) BW[r * ldbw + j0 + 1] = v1;
+                }
+            }
+        }
+    }
+    red[0][tid][0] = d0, red[0][tid][1] = d1;
+    red[1][tid][0] = a0, red[1][tid][1] = a1;
+    red[2][tid][0] = b0, red[2][tid][1] = b1;
+    __syncthreads();
+    if (tid < LOB_PHASES * k) {                      // phase g of column j: slots g, g + 16, ... ascending, per group
+        const int g = tid / k, j = tid - g * k;
+        for (int q = 0; q < LOB_GEN_SUMS; ++q) {
+            double s = 0.0;
+            for (int sl = g; sl < RP; sl += LOB_PHASES) s = s + red[q][sl * kp + (j >> 1)][j & 1];
+            ph[q][g][j] = s;
+        }
+    }
+    __syncthreads();
+    if (tid < LOB_GEN_SUMS * k) {
+        const int q = tid / k, j = tid - q * k;
+        double s = ph[q][0][j];
+        for (int g = 1; g < LOB_PHASES; ++g) s = s + ph[q][g][j];
+        partial[((int64_t)blockIdx.x * LOB_GEN_SUMS + q) * k + j] = s;
+    }
+}
+
+// out[16 q + j] = sum over chunks of partial[chunk][q][j]: LOB_PHASES phases of ascending chunks, then the phases ascending
+__global__ __launch_bounds__(LOB_THREADS) void lobpcg_residual_gen_stage2(const double *__restrict__ partial, int64_t nchunks,
+                                                                          int k, double *__restrict__ out)
+{
+    __shared__ double ph[LOB_GEN_SUMS][LOB_PHASES][LOB_MAX_K];
+    const int tid = threadIdx.x;
+    if (tid < LOB_PHASES * k) {                      // the three groups side by side: one chain of loads, not three in a row
+        const int g = tid / k, j = tid - g * k;
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+        for (int64_t ch = g; ch < nchunks; ch += LOB_PHASES) {
+            const double *p = partial + ch * LOB_GEN_SUMS * k + j;
+            s0 = s0 + p[0];
+            s1 = s1 + p[k];
+            s2 = s2 + p[2 * k];
+        }
+        ph[0][g][j] = s0, ph[1][g][j] = s1, ph[2][g][j] = s2;
+    }
+    __syncthreads();
+    if (tid < LOB_GEN_SUMS * k) {
+        const int q = tid / k, j = tid - q * k;
+        double s = ph[q][0][j];
+        for (int g = 1; g < LOB_PHASES; ++g) s = s + ph[q][g][j];
+        out[q * LOB_MAX_K + j] = s;
     }
 }
 
@@ -283,6 +418,56 @@ HPCLA_API int hpcla_lobpcg_residual_f64(hpcla_comm_t *comm, const double *X, int
         HPCLA_CHECK_LAUNCH();
     }
     if (comm) return allreduce_on(comm, rn2_dev, k, 0, stream);
+    return HPCLA_OK;
+}
+
+HPCLA_API int64_t hpcla_lobpcg_gen_work_bytes(int64_t n, int k)
+{
+    if (n <= 0 || k < 1 || k > LOB_MAX_K) return 8;
+    const int64_t rpc = lob_rows_per_chunk(n);
+    return (n + rpc - 1) / rpc * LOB_GEN_SUMS * k * (int64_t)sizeof(double);
+}
+
+HPCLA_API int hpcla_lobpcg_residual_gen_f64(hpcla_comm_t *comm, const double *AX, int64_t ldax, const double *BX, int64_t ldbx,
+                                            const double *theta_dev, const double *minv, const double *bdiag, double *W,
+                                            int64_t ldw, double *W2, int64_t ldw2, double *BW, int64_t ldbw, int64_t n, int k,
+                                            double *sums_dev, void *work, void *stream)
+{
+    if (k < 1 || k > LOB_MAX_K) return set_error(HPCLA_ERR_INVALID, "lobpcg_residual_gen: needs 1 <= k <= 16");
+    if (n < 0 || ldax < k || ldbx < k || ldw < k || (W2 && ldw2 < k) || (BW && ldbw < k))
+        return set_error(HPCLA_ERR_INVALID, "lobpcg_residual_gen: negative size, or a pitch shorter than k");
+    if (!sums_dev || (reinterpret_cast<uintptr_t>(sums_dev) & 7))
+        return set_error(HPCLA_ERR_INVALID, "lobpcg_residual_gen: null or misaligned sums");
+    hipStream_t s = as_stream(stream);
+    if (n == 0) {                                    // no local rows: the partials are zero, the rank still reduces
+        for (int q = 0; q < LOB_GEN_SUMS; ++q)
+            HPCLA_CHECK_HIP(hipMemsetAsync(sums_dev + q * LOB_MAX_K, 0, (size_t)k * sizeof(double), s));
+    } else {
+        if (!AX || !BX || !W || !theta_dev || !work)
+            return set_error(HPCLA_ERR_INVALID, "lobpcg_residual_gen: null AX / BX / W / theta / work");
+        if (!bdiag != !BW)
+            return set_error(HPCLA_ERR_INVALID, "lobpcg_residual_gen: bdiag and BW are given together or not at all");
+        if ((reinterpret_cast<uintptr_t>(AX) | reinterpret_cast<uintptr_t>(BX) | reinterpret_cast<uintptr_t>(W) |
+             reinterpret_cast<uintptr_t>(W2) | reinterpret_cast<uintptr_t>(BW) | reinterpret_cast<uintptr_t>(theta_dev) |
+             reinterpret_cast<uintptr_t>(minv) | reinterpret_cast<uintptr_t>(bdiag) | reinterpret_cast<uintptr_t>(work)) & 7)
+            return set_error(HPCLA_ERR_INVALID, "lobpcg_residual_gen: every array must be 8-byte aligned");
+        const int64_t rpc = lob_rows_per_chunk(n);
+        const int64_t nchunks = (n + rpc - 1) / rpc;
+        HPCLA_CHECK_GRID(nchunks, "lobpcg_residual_gen");
+        double *partial = static_cast<double *>(work);
+        const bool vec = lob_even_aligned(AX, ldax) && lob_even_aligned(BX, ldbx) && lob_even_aligned(W, ldw) &&
+                         lob_even_aligned(W2, ldw2) && lob_even_aligned(BW, ldbw);
+        if (vec)
+            lobpcg_residual_gen_kernel<true><<<(unsigned)nchunks, LOB_THREADS, 0, s>>>(AX, ldax, BX, ldbx, theta_dev, minv, bdiag, W,
+                                                                                      ldw, W2, ldw2, BW, ldbw, n, k, rpc, partial);
+        else
+            lobpcg_residual_gen_kernel<false><<<(unsigned)nchunks, LOB_THREADS, 0, s>>>(AX, ldax, BX, ldbx, theta_dev, minv, bdiag, W,
+                                                                                       ldw, W2, ldw2, BW, ldbw, n, k, rpc, partial);
+        HPCLA_CHECK_LAUNCH();
+        lobpcg_residual_gen_stage2<<<1, LOB_THREADS, 0, s>>>(partial, nchunks, k, sums_dev);
+        HPCLA_CHECK_LAUNCH();
+    }
+    if (comm) return allreduce_on(comm, sums_dev, LOB_GEN_SUMS * LOB_MAX_K, 0, stream);
     return HPCLA_OK;
 }
 
