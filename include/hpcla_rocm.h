@@ -974,6 +974,63 @@ int hpcla_pcg_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, co
                                  const int32_t *boundary_blocks, int64_t n_boundary, const double *dinv, double *x,
                                  double *r, double *p, double *Ap, double *hist_dev, double *pAp_dev, void *dot_work,
                                  void *pcg_work, int64_t first_iter, int iters, void *stream);
+/* ---- factorised sparse approximate inverse (hp.fsai; csrc/fsai.hip): a sparse lower triangular G with diag(G A G') = 1 on a
+ * given pattern, M = G' G as the preconditioner of the CG solver above (no reference counterpart: the reference's only
+ * solver is MUMPS on the host, and it has no preconditioner).  Rows and columns of A are partitioned alike (n_own == nrows), so
+ * a split column < n_own is the local row it names; columns >= n_own are ghosts and are skipped: G couples a rank's own rows
+ * only.  Row i of G lives on J_i = the pattern columns < i of row i, ascending, then i (m = |J_i| <= 32): with S = A[J_i, J_i]
+ * (an unstored entry is 0, only the lower triangle is read) and S = L L', the row is inv(L') e_m.  p_* is the pattern's
+ * structure, a_* the matrix; they may be the same arrays.
+ *   fsai_work_bytes  device bytes of `work` for the count.
+ *   fsai_count       g_rowptr_dev: nrows + 1 entries, 0-based.  info_dev[0] = nnz(G), info_dev[1] = the largest m,
+ *                    info_dev[2] = the error word, reset here: all ones, or (local row << 2) | code of the smallest failing
+ *                    row -- 1: m > 32, 2: A stores no diagonal in the row, 3: a pivot of S that is not > 0 (NaN included).
+ *   fsai_factor      max_m: at least the largest m of the count (selects 4, 8, 16 or 32 lanes per row).  Writes G's global
+ *                    column ids (col_start + local column) and values at g_rowptr_dev's positions; a failing row gets zeros
+ *                    and lowers the error word.  The bits of a row do not depend on max_m, the launch or the call.
+ * Both only enqueue (vector atomic min / max on info_dev, no waiting). */
+int64_t hpcla_fsai_work_bytes(int64_t nrows);
+int hpcla_fsai_count_f64_i32(const int32_t *p_rowptr, const int32_t *p_colval_split, const int32_t *a_rowptr,
+                             const int32_t *a_colval_split, int64_t nrows, int64_t n_own, int index_base,
+                             int64_t *g_rowptr_dev, int64_t *info_dev, void *work, void *stream);
+int hpcla_fsai_count_f64_i64(const int64_t *p_rowptr, const int64_t *p_colval_split, const int64_t *a_rowptr,
+                             const int64_t *a_colval_split, int64_t nrows, int64_t n_own, int index_base,
+                             int64_t *g_rowptr_dev, int64_t *info_dev, void *work, void *stream);
+int hpcla_fsai_factor_f64_i32(const int32_t *p_rowptr, const int32_t *p_colval_split, const int32_t *a_rowptr,
+                              const int32_t *a_colval_split, const double *a_nzval, int64_t nrows, int64_t n_own,
+                              int index_base, int64_t col_start, int max_m, const int64_t *g_rowptr_dev,
+                              int64_t *g_cols_dev, double *g_vals_dev, int64_t *info_dev, void *stream);
+int hpcla_fsai_factor_f64_i64(const int64_t *p_rowptr, const int64_t *p_colval_split, const int64_t *a_rowptr,
+                              const int64_t *a_colval_split, const double *a_nzval, int64_t nrows, int64_t n_own,
+                              int index_base, int64_t col_start, int max_m, const int64_t *g_rowptr_dev,
+                              int64_t *g_cols_dev, double *g_vals_dev, int64_t *info_dev, void *stream);
+/* Iterations of the CG solver with M = Gt G, G and Gt matrices with plans of their own (the three plan / CSR blocks are A's,
+ * G's and Gt's, each as for hpcla_pcg_iterations_*): per iteration hpcla_spmv_dist_dot_*, hpcla_pcg_residual_f64 with
+ * dinv == NULL, u = G r and z = Gt u through hpcla_spmv_dist_* (always executed), hpcla_nrm2sq_f64 of u into
+ * hist_dev[2j+1] (r.M r = sum u^2, never negative; always executed), hpcla_pcg_direction_f64 with z in place of r.  State,
+ * history, scratch and stop rule are hpcla_pcg_iterations_*'s.  Only enqueues. */
+int hpcla_pcg_fsai_iterations_f64_i32(
+    hpcla_comm_t *comm, hpcla_halo_plan_t *plan, const int32_t *rowptr, const int32_t *colval_split, const int16_t *cols16,
+    const hpcla_block_patterns_t *patterns, const double *nzval, int64_t nrows, int64_t nnz, int index_base,
+    const int32_t *interior_blocks, int64_t n_interior, const int32_t *boundary_blocks, int64_t n_boundary,
+    hpcla_halo_plan_t *plan_g, const int32_t *rowptr_g, const int32_t *colval_split_g, const int16_t *cols16_g,
+    const hpcla_block_patterns_t *patterns_g, const double *nzval_g, int64_t nrows_g, int64_t nnz_g, int index_base_g,
+    const int32_t *interior_blocks_g, int64_t n_interior_g, const int32_t *boundary_blocks_g, int64_t n_boundary_g,
+    hpcla_halo_plan_t *plan_t, const int32_t *rowptr_t, const int32_t *colval_split_t, const int16_t *cols16_t,
+    const hpcla_block_patterns_t *patterns_t, const double *nzval_t, int64_t nrows_t, int64_t nnz_t, int index_base_t,
+    const int32_t *interior_blocks_t, int64_t n_interior_t, const int32_t *boundary_blocks_t, int64_t n_boundary_t, double *x,
+    double *r, double *p, double *Ap, double *u, double *z, double *hist_dev, double *pAp_dev, void *dot_work, void *pcg_work,
+    int64_t first_iter, int iters, void *stream);
+int hpcla_pcg_fsai_iterations_f64_i64(
+    hpcla_comm_t *comm, hpcla_halo_plan_t *plan, const int64_t *rowptr, const int64_t *colval_split, const double *nzval,
+    int64_t nrows, int64_t nnz, int index_base, const int32_t *interior_blocks, int64_t n_interior,
+    const int32_t *boundary_blocks, int64_t n_boundary, hpcla_halo_plan_t *plan_g, const int64_t *rowptr_g,
+    const int64_t *colval_split_g, const double *nzval_g, int64_t nrows_g, int64_t nnz_g, int index_base_g,
+    const int32_t *interior_blocks_g, int64_t n_interior_g, const int32_t *boundary_blocks_g, int64_t n_boundary_g,
+    hpcla_halo_plan_t *plan_t, const int64_t *rowptr_t, const int64_t *colval_split_t, const double *nzval_t, int64_t nrows_t,
+    int64_t nnz_t, int index_base_t, const int32_t *interior_blocks_t, int64_t n_interior_t, const int32_t *boundary_blocks_t,
+    int64_t n_boundary_t, double *x, double *r, double *p, double *Ap, double *u, double *z, double *hist_dev, double *pAp_dev,
+    void *dot_work, void *pcg_work, int64_t first_iter, int iters, void *stream);
 /* ---- BiCGStab for nonsymmetric A: gated steps of right-preconditioned BiCGStab, K = identity or dinv .* (no reference
  * counterpart: the reference solves a general A \ b through MUMPS on the host; a caller of its operators composes the
  * method from A*p, src/sparse.jl:2096-2128, dot, src/vectors.jl:798-812, and the broadcasts, src/vectors.jl:1203-1226).

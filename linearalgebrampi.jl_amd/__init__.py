@@ -10,7 +10,9 @@ Layout
   sparse.py          HPCSparseMatrix, VectorPlan (host lists + device plan), A*x, mul!
   dense.py           HPCMatrix, dense A*x and transpose(A)*x, transpose(X)*Y, X*A and transpose(X)*A
   spmm_plans.py      A*B for a sparse A and a dense B (SpMM): exchange entries, sequential and panel orders
-  cg.py              fixed-iteration CG harness; cg(): the converging solver (Jacobi preconditioner, device-side stop)
+  cg.py              fixed-iteration CG harness; cg(): the converging solver (Jacobi or FSAI preconditioner, device-side stop)
+  fsai.py            fsai(): the factorised sparse approximate inverse preconditioner G' G of an SPD A for cg(M=...): one small dense
+                     Cholesky per row on the device (csrc/fsai.hip), applied as two SpMVs; rank-local couplings, <= 32 entries per row
   bicgstab.py        bicgstab(): BiCGStab for nonsymmetric A, the same device-side stop (csrc/vecops.hip, bicg_* kernels)
   gmres.py           gmres(): restarted GMRES(m), fused twice-applied Gram-Schmidt, the same device-side stop (gmres_* kernels)
   lsqr.py            lsqr(): least squares for rectangular A on A and its materialised transpose, damped form, two stop rules
@@ -51,6 +53,7 @@ from .dense import (HPCMatrix, HPCMatrix_local, TransposedHPCMatrix, clear_dense
 from .spmm_plans import clear_spmm_cache, spmm, spmm_block_order_of, spmm_exchange_bytes, spmm_runs_fit_of
 from .matmat import clear_matrix_plan_cache, get_matrix_plan, spgemm
 from .cg import CGGraphPair, CGInfo, CGWorkspace, PCGWorkspace, cg, cg_fixed_iterations, cg_iterate, cg_setup
+from .fsai import FSAI, fsai
 from .bicgstab import BiCGStabWorkspace, bicgstab
 from .gmres import GMRESWorkspace, gmres
 from .lsqr import LSQRInfo, LSQRWorkspace, lsqr

@@ -156,6 +156,23 @@ _SIGNATURES = {
                                      _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
     "hpcla_pcg_iterations_f64_i64": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
                                      _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
+    # factorised sparse approximate inverse (hp.fsai, csrc/fsai.hip): G's structure, its values; the chunk of CG iterations
+    # with M = Gt G (the plan / CSR block three times: A, G, Gt)
+    "hpcla_fsai_work_bytes": [_i64],
+    "hpcla_fsai_count_f64_i32": [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp],
+    "hpcla_fsai_count_f64_i64": [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp],
+    "hpcla_fsai_factor_f64_i32": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp],
+    "hpcla_fsai_factor_f64_i64": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp],
+    "hpcla_pcg_fsai_iterations_f64_i32": [_vp,
+                                          _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
+                                          _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
+                                          _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
+                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
+    "hpcla_pcg_fsai_iterations_f64_i64": [_vp,
+                                          _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
+                                          _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
+                                          _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
+                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
     # BiCGStab for nonsymmetric A (hp.bicgstab): the gated steps and the chunk of iterations
     "hpcla_bicgstab_work_bytes": [],
     "hpcla_bicg_dot_f64": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
@@ -346,6 +363,7 @@ _RESTYPES = {
     "hpcla_spmv_longrows_work_bytes": _i64,
     "hpcla_cols16_padded_len": _i64,
     "hpcla_pcg_work_bytes": _i64,
+    "hpcla_fsai_work_bytes": _i64,
     "hpcla_bicgstab_work_bytes": _i64,
     "hpcla_lsqr_work_bytes": _i64,
     "hpcla_minres_work_bytes": _i64,

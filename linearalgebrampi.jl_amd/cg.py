@@ -21,9 +21,10 @@ The solve is split into ``cg_setup`` (x = 0, r = p = b, sum r0^2 -- allocation l
 ``CGWorkspace``) and ``cg_iterate`` (exactly k iterations, enqueue only), so a benchmark can time the
 iterations and nothing else; ``cg_fixed_iterations`` is the two together plus the history read-back.
 
-``cg`` is the solver built from the same launches: a stop rule, an optional diagonal preconditioner and a breakdown
-check, all decided on the device (csrc/vecops.hip, ``hpcla_pcg_iterations_f64_*``); the host reads 16 bytes of state once
-per ``check_every`` iterations, and the iterations enqueued behind the deciding one are no-ops.
+``cg`` is the solver built from the same launches: a stop rule, an optional preconditioner (a diagonal, or the factorised
+sparse approximate inverse of fsai.py: two more SpMVs and one reduction per iteration, ``hpcla_pcg_fsai_iterations_f64_*``) and
+a breakdown check, all decided on the device (csrc/vecops.hip, ``hpcla_pcg_iterations_f64_*``); the host reads 16 bytes of
+state once per ``check_every`` iterations, and the iterations enqueued behind the deciding one are no-ops.
 """
 from __future__ import annotations
 
@@ -34,6 +35,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _capi
+from .fsai import FSAI
 from .sparse import get_vector_plan, mul_, mul_dot_
 from .vectors import HPCVector, _Scratch, cg_direction_, cg_residual_, current_stream_ptr, dot, dptr, norm, rd16_vector
 
@@ -316,7 +318,8 @@ def _residual_norms(ws, backend, iterations: int) -> List[float]:
 class PCGWorkspace(_PairHistory):
     """What a ``cg`` solve allocates: x, r, p, Ap, the history of (sum r_j^2, sum r_j.(dinv r_j)) pairs (it IS the scalar
     storage of the iterations; it grows by doubling between chunks), pAp, and the scratch of the gated kernels whose last
-    32 bytes are the solve's device state (done_iter, status, thr).  Reusable: every solve resets all of it."""
+    32 bytes are the solve's device state (done_iter, status, thr).  Reusable: every solve resets all of it.  ``u`` and ``z``
+    (u = G r, z = Gt u) exist once a solve with ``M=<FSAI>`` has used the workspace."""
 
     def __init__(self, b: HPCVector, hist_iters: int = 254):
         torch = _torch()
@@ -330,6 +333,11 @@ class PCGWorkspace(_PairHistory):
         self.tmp = torch.ones(2, dtype=torch.float64, device=dev)      # [0]: |b|^2 for a given x0; [1]: the constant 1
         self.work = torch.zeros(_capi.load().hpcla_pcg_work_bytes() // 8, dtype=torch.float64, device=dev)
         self.state = self.work[-4:].view(torch.int64)                  # done_iter, status, thr (a double), reserved
+        self.u = self.z = None
+
+    def fsai_vectors(self) -> None:
+        if self.u is None:
+            self.u, self.z = self.r.similar(), self.r.similar()
 
     def fits(self, b: HPCVector) -> bool:
         return self.x.structural_hash == b.structural_hash and self.x.v.device == b.v.device
@@ -347,9 +355,16 @@ def _cg_dinv(A, b: HPCVector, M) -> Optional[HPCVector]:
             raise ValueError("cg: M='jacobi' needs a positive diagonal (minimum(diag(A)) > 0)")
         return diag(A, reciprocal=True)
     if not isinstance(M, HPCVector):
-        raise ValueError("cg: M must be None, 'jacobi' or an HPCVector on A's row partition")
+        raise ValueError("cg: M must be None, 'jacobi', an HPCVector on A's row partition or an FSAI (hp.fsai(A))")
     b._same_partition(M)
     return rd16_vector(M)                                        # the step kernels read it 16 bytes at a time
+
+
+def _matrix_block(A, plan) -> tuple:
+    """The plan and CSR arguments of one matrix, as hpcla_pcg_fsai_iterations_* takes them (three times)."""
+    narrow = () if plan.is_i64 else (dptr(plan.cols16), plan.patterns)
+    return (plan.halo if plan.has_halo else None, dptr(plan.rowptr_of(A)), dptr(plan.colval_split), *narrow, dptr(A.nzval),
+            A.nrows_local, A.nnz, 0, dptr(plan.interior), plan.n_interior, dptr(plan.boundary), plan.n_boundary)
 
 
 def cg(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, atol: float = 0.0,
@@ -359,8 +374,9 @@ def cg(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, atol
 
     Stops at the first iteration with ``||r_k|| <= max(rtol * ||b||, atol)`` (scipy's rule; r_k is the recurrence residual),
     after ``maxiter`` iterations (default ``10 n``), or on a breakdown (``p.Ap <= 0`` or NaN: A is not positive definite
-    along p).  ``M``: ``None``, ``"jacobi"`` (``1 ./ diag(A)``, formed on the device; the diagonal must be positive) or an
-    HPCVector holding the inverse diagonal to apply.  ``x0`` defaults to zero.  Returns ``(x, CGInfo)``; x is the
+    along p).  ``M``: ``None``, ``"jacobi"`` (``1 ./ diag(A)``, formed on the device; the diagonal must be positive), an
+    HPCVector holding the inverse diagonal to apply, or the ``FSAI`` object of ``hp.fsai(A)`` (``z = Gt (G r)``: two more SpMVs
+    per iteration, ``r.M r`` formed as ``sum (G r)^2``).  ``x0`` defaults to zero.  Returns ``(x, CGInfo)``; x is the
     workspace's vector.
 
     The stop test and the breakdown test run on the device.  The host enqueues ``check_every`` iterations in one library
@@ -373,7 +389,15 @@ def cg(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, atol
     plan = get_vector_plan(A, ws.p)
     if plan.result_partition_hash != ws.p.structural_hash:
         raise ValueError("cg: b must be partitioned like the rows of A")
-    dinv = _cg_dinv(A, b, M)
+    op = M if isinstance(M, FSAI) else None
+    dinv = None if op is not None else _cg_dinv(A, b, M)
+    if op is not None:
+        if not np.array_equal(op.G.row_partition, A.row_partition) or op.G.shape != A.shape:
+            raise ValueError("cg: the FSAI preconditioner was built for a matrix of another shape or partition")
+        ws.fsai_vectors()
+        plan_g, plan_t = get_vector_plan(op.G, ws.r), get_vector_plan(op.Gt, ws.u)
+        if not (plan.is_i64 == plan_g.is_i64 == plan_t.is_i64):
+            raise NotImplementedError("cg: the plans of A and of the FSAI factors use different index widths")
     if getattr(plan, "_dot_work", None) is None:
         nbytes = _capi.load().hpcla_spmv_dot_work_bytes(A.nrows_local)
         plan._dot_work = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=ws.p.v.device)
@@ -393,7 +417,12 @@ def cg(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, atol
         norm(b, 2, out=ws.tmp[0:1])
     norm(ws.r, 2, out=ws.hist[0:1])
     one = ws.tmp[1:2]
-    if dinv is None:
+    if op is not None:                                           # u = G r, z = Gt u, p = z, pair 0's second slot = sum u^2
+        mul_(ws.u, op.G, ws.r)
+        mul_(ws.z, op.Gt, ws.u)
+        ws.p.v.copy_(ws.z.v)
+        norm(ws.u, 2, out=ws.hist[1:2])
+    elif dinv is None:
         ws.p.v.copy_(ws.r.v)
         ws.hist[1:2].copy_(ws.hist[0:1])
     else:                                                        # p = dinv r + 1 * 0 through the direction kernel (x += 1 * 0)
@@ -409,13 +438,20 @@ def cg(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, atol
     sfx = "i64" if plan.is_i64 else "i32"
     narrow = () if plan.is_i64 else (dptr(plan.cols16), plan.patterns)
 
-    def enqueue(first, count):
+    def enqueue_diagonal(first, count):
         _capi.call(f"hpcla_pcg_iterations_f64_{sfx}", plan.halo if plan.has_halo else None, A.backend.rccl,
                    dptr(plan.rowptr_of(A)), dptr(plan.colval_split), *narrow, dptr(A.nzval), A.nrows_local, A.nnz, 0,
                    dptr(plan.interior), plan.n_interior, dptr(plan.boundary), plan.n_boundary,
                    dptr(dinv.v) if dinv is not None else None, dptr(ws.x.v), dptr(ws.r.v), dptr(ws.p.v), dptr(ws.Ap.v),
                    dptr(ws.hist), dptr(ws.pAp), dptr(plan._dot_work), dptr(ws.work), first, count, current_stream_ptr())
 
-    iterations, status = _run_chunks(ws, A.backend, maxiter, check_every, enqueue)
+    def enqueue_fsai(first, count):
+        _capi.call(f"hpcla_pcg_fsai_iterations_f64_{sfx}", A.backend.rccl, *blocks, dptr(ws.x.v), dptr(ws.r.v), dptr(ws.p.v),
+                   dptr(ws.Ap.v), dptr(ws.u.v), dptr(ws.z.v), dptr(ws.hist), dptr(ws.pAp), dptr(plan._dot_work), dptr(ws.work),
+                   first, count, current_stream_ptr())
+
+    if op is not None:
+        blocks = _matrix_block(A, plan) + _matrix_block(op.G, plan_g) + _matrix_block(op.Gt, plan_t)
+    iterations, status = _run_chunks(ws, A.backend, maxiter, check_every, enqueue_fsai if op is not None else enqueue_diagonal)
     h = _residual_norms(ws, b.backend, iterations)
     return ws.x, CGInfo(status == 1, iterations, _STATUS[status], h)

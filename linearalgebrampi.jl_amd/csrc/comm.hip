@@ -1183,6 +1183,110 @@ HPCLA_API int hpcla_pcg_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t
                                         iters, stream);
 }
 
+// ---- the same chunk with M = Gt G, a factorised sparse approximate inverse (hp.cg with M = hp.fsai(A)) -----------------
+// G and Gt are matrices with plans of their own.  Iteration j, in this order:
+//   1. Ap = A p, pAp      as above
+//   2. gate A, r -= a Ap, sum r^2, gate B     hpcla_pcg_residual_f64 with dinv == NULL (the pair's second slot is rewritten by 5)
+//   3. u = G r            hpcla_spmv_dist_* on G's plan  -- always executed, not gated
+//   4. z = Gt u           the same on Gt's plan          -- always executed
+//   5. rz = sum u^2       hpcla_nrm2sq_f64 into hist_dev[2 j + 1], one all-reduce: r.M r, never negative -- always executed
+//   6. x += a p, p = z + b p    hpcla_pcg_direction_f64 with z in place of r and dinv == NULL, gated
+// Behind the deciding iteration r is frozen, so 3-5 recompute what they computed and write pairs nobody reads.
+template <typename I>
+struct SpmvBlock {                                                  // the plan and CSR arguments of one matrix
+    hpcla_halo_plan_t *plan;
+    const I *rowptr, *colval;
+    const int16_t *cols16;
+    const hpcla_block_patterns *patterns;
+    const double *nzval;
+    int64_t nrows, nnz;
+    int index_base;
+    const int32_t *interior;
+    int64_t n_interior;
+    const int32_t *boundary;
+    int64_t n_boundary;
+};
+
+template <typename I, typename F, typename G>
+static int pcg_fsai_iterations_impl(F split_fn, G fused_fn, hpcla_comm_t *comm, const SpmvBlock<I> &a, const SpmvBlock<I> &g,
+                                    const SpmvBlock<I> &gt, double *x, double *r, double *p, double *Ap, double *u, double *z,
+                                    double *hist_dev, double *pAp_dev, void *dot_work, void *pcg_work, int64_t first_iter,
+                                    int iters, void *stream)
+{
+    if (iters < 0 || first_iter < 1)
+        return set_error(HPCLA_ERR_INVALID, "pcg_fsai_iterations: negative count or first_iter < 1");
+    if (!hist_dev || !pAp_dev || !dot_work || !pcg_work)
+        return set_error(HPCLA_ERR_INVALID, "pcg_fsai_iterations: null scalar / work buffer");
+    const int64_t n = a.nrows;
+    if (g.nrows != n || gt.nrows != n) return set_error(HPCLA_ERR_INVALID, "pcg_fsai_iterations: G and Gt must have A's rows");
+    if (n > 0 && (!x || !r || !p || !Ap || !u || !z)) return set_error(HPCLA_ERR_INVALID, "pcg_fsai_iterations: null vector");
+    int64_t *state = reinterpret_cast<int64_t *>(static_cast<char *>(pcg_work) + hpcla_pcg_work_bytes()) - 4;
+    for (int64_t j = first_iter; j < first_iter + iters; ++j) {
+        double *prev = hist_dev + 2 * (j - 1), *cur = hist_dev + 2 * j;
+        int rc = spmv_dist_dot_impl<I>(split_fn, fused_fn, a.plan, comm, a.rowptr, a.colval, a.nzval, p, n, Ap, n, a.nnz,
+                                       a.index_base, a.interior, a.n_interior, a.boundary, a.n_boundary, pAp_dev, dot_work,
+                                       stream, a.cols16, a.patterns);
+        if (rc) return rc;
+        rc = hpcla_pcg_residual_f64(comm, prev + 1, pAp_dev, Ap, nullptr, r, n, j, state, cur, pcg_work, stream);
+        if (rc) return rc;
+        rc = spmv_dist_impl<I>(split_fn, fused_fn, g.plan, g.rowptr, g.colval, g.nzval, r, n, u, n, g.nnz, g.index_base,
+                               g.interior, g.n_interior, g.boundary, g.n_boundary, stream, nullptr, g.cols16, g.patterns);
+        if (rc) return rc;
+        rc = spmv_dist_impl<I>(split_fn, fused_fn, gt.plan, gt.rowptr, gt.colval, gt.nzval, u, n, z, n, gt.nnz, gt.index_base,
+                               gt.interior, gt.n_interior, gt.boundary, gt.n_boundary, stream, nullptr, gt.cols16, gt.patterns);
+        if (rc) return rc;
+        rc = hpcla_nrm2sq_f64(comm, u, n, cur + 1, pcg_work, stream);
+        if (rc) return rc;
+        rc = hpcla_pcg_direction_f64(prev + 1, pAp_dev, cur + 1, prev + 1, z, nullptr, x, p, n, j, state, stream);
+        if (rc) return rc;
+    }
+    return HPCLA_OK;
+}
+
+HPCLA_API int hpcla_pcg_fsai_iterations_f64_i32(
+    hpcla_comm_t *comm, hpcla_halo_plan_t *plan, const int32_t *rowptr, const int32_t *colval_split, const int16_t *cols16,
+    const hpcla_block_patterns_t *patterns, const double *nzval, int64_t nrows, int64_t nnz, int index_base,
+    const int32_t *interior_blocks, int64_t n_interior, const int32_t *boundary_blocks, int64_t n_boundary,
+    hpcla_halo_plan_t *plan_g, const int32_t *rowptr_g, const int32_t *colval_split_g, const int16_t *cols16_g,
+    const hpcla_block_patterns_t *patterns_g, const double *nzval_g, int64_t nrows_g, int64_t nnz_g, int index_base_g,
+    const int32_t *interior_blocks_g, int64_t n_interior_g, const int32_t *boundary_blocks_g, int64_t n_boundary_g,
+    hpcla_halo_plan_t *plan_t, const int32_t *rowptr_t, const int32_t *colval_split_t, const int16_t *cols16_t,
+    const hpcla_block_patterns_t *patterns_t, const double *nzval_t, int64_t nrows_t, int64_t nnz_t, int index_base_t,
+    const int32_t *interior_blocks_t, int64_t n_interior_t, const int32_t *boundary_blocks_t, int64_t n_boundary_t, double *x,
+    double *r, double *p, double *Ap, double *u, double *z, double *hist_dev, double *pAp_dev, void *dot_work, void *pcg_work,
+    int64_t first_iter, int iters, void *stream)
+{
+    const SpmvBlock<int32_t> a{plan, rowptr, colval_split, cols16, patterns, nzval, nrows, nnz, index_base, interior_blocks,
+                               n_interior, boundary_blocks, n_boundary};
+    const SpmvBlock<int32_t> g{plan_g, rowptr_g, colval_split_g, cols16_g, patterns_g, nzval_g, nrows_g, nnz_g, index_base_g,
+                               interior_blocks_g, n_interior_g, boundary_blocks_g, n_boundary_g};
+    const SpmvBlock<int32_t> gt{plan_t, rowptr_t, colval_split_t, cols16_t, patterns_t, nzval_t, nrows_t, nnz_t, index_base_t,
+                                interior_blocks_t, n_interior_t, boundary_blocks_t, n_boundary_t};
+    return pcg_fsai_iterations_impl<int32_t>(spmv_split_i32, spmv_fused_i32, comm, a, g, gt, x, r, p, Ap, u, z, hist_dev, pAp_dev,
+                                             dot_work, pcg_work, first_iter, iters, stream);
+}
+
+HPCLA_API int hpcla_pcg_fsai_iterations_f64_i64(
+    hpcla_comm_t *comm, hpcla_halo_plan_t *plan, const int64_t *rowptr, const int64_t *colval_split, const double *nzval,
+    int64_t nrows, int64_t nnz, int index_base, const int32_t *interior_blocks, int64_t n_interior,
+    const int32_t *boundary_blocks, int64_t n_boundary, hpcla_halo_plan_t *plan_g, const int64_t *rowptr_g,
+    const int64_t *colval_split_g, const double *nzval_g, int64_t nrows_g, int64_t nnz_g, int index_base_g,
+    const int32_t *interior_blocks_g, int64_t n_interior_g, const int32_t *boundary_blocks_g, int64_t n_boundary_g,
+    hpcla_halo_plan_t *plan_t, const int64_t *rowptr_t, const int64_t *colval_split_t, const double *nzval_t, int64_t nrows_t,
+    int64_t nnz_t, int index_base_t, const int32_t *interior_blocks_t, int64_t n_interior_t, const int32_t *boundary_blocks_t,
+    int64_t n_boundary_t, double *x, double *r, double *p, double *Ap, double *u, double *z, double *hist_dev, double *pAp_dev,
+    void *dot_work, void *pcg_work, int64_t first_iter, int iters, void *stream)
+{
+    const SpmvBlock<int64_t> a{plan, rowptr, colval_split, nullptr, nullptr, nzval, nrows, nnz, index_base, interior_blocks,
+                               n_interior, boundary_blocks, n_boundary};
+    const SpmvBlock<int64_t> g{plan_g, rowptr_g, colval_split_g, nullptr, nullptr, nzval_g, nrows_g, nnz_g, index_base_g,
+                               interior_blocks_g, n_interior_g, boundary_blocks_g, n_boundary_g};
+    const SpmvBlock<int64_t> gt{plan_t, rowptr_t, colval_split_t, nullptr, nullptr, nzval_t, nrows_t, nnz_t, index_base_t,
+                                interior_blocks_t, n_interior_t, boundary_blocks_t, n_boundary_t};
+    return pcg_fsai_iterations_impl<int64_t>(spmv_split_i64, spmv_fused_i64, comm, a, g, gt, x, r, p, Ap, u, z, hist_dev, pAp_dev,
+                                             dot_work, pcg_work, first_iter, iters, stream);
+}
+
 // ---- a chunk of gated BiCGStab iterations in ONE host call (the solver, hp.bicgstab) ------------------------------
 // Right-preconditioned BiCGStab, K = identity (dinv == NULL: ph is p, sh is s) or dinv .*.  Iteration j = first_iter ..
 // first_iter + iters - 1 (1-based over the whole solve), in this order (the gates and the bytes: csrc/vecops.hip):
