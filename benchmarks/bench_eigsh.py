@@ -42,13 +42,11 @@ class FusedCycle:
 
     def __init__(self, hp, torch, A, ws):
         from hpcla_amd.sparse import get_vector_plan
-        from hpcla_amd.vectors import dptr
         plan = get_vector_plan(A, ws.w)
         assert not plan.is_i64
         self.hp, self.ws, self.torch = hp, ws, torch
-        self.spmv = (plan.halo if plan.has_halo else None, A.backend.rccl, dptr(plan.rowptr_of(A)), dptr(plan.colval_split),
-                     dptr(plan.cols16), plan.patterns, dptr(A.nzval), A.nrows_local, A.nnz, 0, dptr(plan.interior), plan.n_interior,
-                     dptr(plan.boundary), plan.n_boundary)
+        blk = plan.matrix_block(A)
+        self.spmv = (blk[0], A.backend.rccl, *blk[1:])
 
     def __call__(self):
         ws, P = self.ws, (lambda t: t.data_ptr())

@@ -37,12 +37,11 @@ class FusedCycle:
     """Columns 0 .. m-1 of a first cycle in one library call, from a normalised start in column 0 of V."""
 
     def __init__(self, hp, torch, A, At, ws):
-        from hpcla_amd.lsqr import _matrix_block
         from hpcla_amd.sparse import get_vector_plan
         plan, plan_t = get_vector_plan(A, ws.v), get_vector_plan(At, ws.u)
         assert not plan.is_i64 and not plan_t.is_i64
         self.hp, self.ws, self.torch = hp, ws, torch
-        self.blocks = _matrix_block(A, plan) + _matrix_block(At, plan_t)
+        self.blocks = plan.matrix_block(A) + plan_t.matrix_block(At)
         self.comm = A.backend.rccl
 
     def __call__(self):

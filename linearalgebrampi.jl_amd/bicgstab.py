@@ -135,13 +135,11 @@ def bicgstab(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8
 
     # -- chunks of check_every iterations; one 16-byte read-back each -------------------------------------------------------
     sfx = "i64" if plan.is_i64 else "i32"
-    narrow = () if plan.is_i64 else (dptr(plan.cols16), plan.patterns)
+    blk = plan.matrix_block(A)
     pre = (dptr(ws.ph.v), dptr(ws.sh.v)) if dinv is not None else (None, None)
 
     def enqueue(first, count):
-        _capi.call(f"hpcla_bicgstab_iterations_f64_{sfx}", plan.halo if plan.has_halo else None, A.backend.rccl,
-                   dptr(plan.rowptr_of(A)), dptr(plan.colval_split), *narrow, dptr(A.nzval), A.nrows_local, A.nnz, 0,
-                   dptr(plan.interior), plan.n_interior, dptr(plan.boundary), plan.n_boundary,
+        _capi.call(f"hpcla_bicgstab_iterations_f64_{sfx}", blk[0], A.backend.rccl, *blk[1:],
                    dptr(dinv.v) if dinv is not None else None, dptr(ws.x.v), dptr(ws.r.v), dptr(ws.rhat.v), dptr(ws.p.v),
                    pre[0], dptr(ws.v.v), dptr(ws.s.v), pre[1], dptr(ws.t.v), dptr(ws.hist), dptr(ws.scal), dptr(ws.work),
                    first, count, current_stream_ptr())

@@ -94,10 +94,7 @@ def cg_setup(A, b: HPCVector, ws: CGWorkspace, fused: bool = True):
     norm(ws.r, 2, out=ws.hist[0:1])            # out form leaves sum(r^2) on the device (8 B/elt)
     ws.done = 0
     if fused:                                  # the SpMV+dot scratch hangs off the plan
-        torch = _torch()
-        if getattr(plan, "_dot_work", None) is None:
-            nbytes = _capi.load().hpcla_spmv_dot_work_bytes(A.nrows_local)
-            plan._dot_work = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=ws.p.v.device)
+        plan.dot_work(A)
     return plan, fused
 
 
@@ -110,11 +107,10 @@ def cg_iterate(A, ws: CGWorkspace, plan, fused: bool, iters: int, native_loop: b
     if fused and native_loop and A._packed_for(plan) is None:
         sfx = "i64" if plan.is_i64 else "i32"
         work, _ = _Scratch.get(ws.r.v.device)
-        _capi.call(f"hpcla_cg_iterations_f64_{sfx}", plan.halo if plan.has_halo else None, A.backend.rccl,
-                   dptr(plan.rowptr_of(A)), dptr(plan.colval_split), dptr(A.nzval), A.nrows_local, A.nnz, 0,
-                   dptr(plan.interior), plan.n_interior, dptr(plan.boundary), plan.n_boundary,
+        blk = plan.matrix_block(A, narrow=False)
+        _capi.call(f"hpcla_cg_iterations_f64_{sfx}", blk[0], A.backend.rccl, *blk[1:],
                    dptr(ws.x.v), dptr(ws.r.v), dptr(ws.p.v), dptr(ws.Ap.v), dptr(hist[first:]), dptr(ws.pAp),
-                   dptr(plan._dot_work), dptr(work), int(iters), current_stream_ptr())
+                   dptr(plan.dot_work(A)), dptr(work), int(iters), current_stream_ptr())
     else:
         for k in range(first, first + iters):
             _cg_iteration(A, ws.x, ws.r, ws.p, ws.Ap, hist[k:k + 1], hist[k + 1:k + 2], ws.pAp, fused)
@@ -360,13 +356,6 @@ def _cg_dinv(A, b: HPCVector, M) -> Optional[HPCVector]:
     return rd16_vector(M)                                        # the step kernels read it 16 bytes at a time
 
 
-def _matrix_block(A, plan) -> tuple:
-    """The plan and CSR arguments of one matrix, as hpcla_pcg_fsai_iterations_* takes them (three times)."""
-    narrow = () if plan.is_i64 else (dptr(plan.cols16), plan.patterns)
-    return (plan.halo if plan.has_halo else None, dptr(plan.rowptr_of(A)), dptr(plan.colval_split), *narrow, dptr(A.nzval),
-            A.nrows_local, A.nnz, 0, dptr(plan.interior), plan.n_interior, dptr(plan.boundary), plan.n_boundary)
-
-
 def cg(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, atol: float = 0.0,
        maxiter: Optional[int] = None, M=None, check_every: int = 8,
        workspace: Optional[PCGWorkspace] = None) -> Tuple[HPCVector, CGInfo]:
@@ -384,7 +373,6 @@ def cg(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, atol
     no-ops, so the answer does not depend on ``check_every``.  With ``M=None`` the iterations produce the bits of
     ``cg_fixed_iterations``."""
     maxiter, check_every = _solver_arguments("cg", A, rtol, atol, maxiter, check_every)
-    torch = _torch()
     ws = workspace if workspace is not None and workspace.fits(b) else PCGWorkspace(b)
     plan = get_vector_plan(A, ws.p)
     if plan.result_partition_hash != ws.p.structural_hash:
@@ -398,9 +386,7 @@ def cg(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, atol
         plan_g, plan_t = get_vector_plan(op.G, ws.r), get_vector_plan(op.Gt, ws.u)
         if not (plan.is_i64 == plan_g.is_i64 == plan_t.is_i64):
             raise NotImplementedError("cg: the plans of A and of the FSAI factors use different index widths")
-    if getattr(plan, "_dot_work", None) is None:
-        nbytes = _capi.load().hpcla_spmv_dot_work_bytes(A.nrows_local)
-        plan._dot_work = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=ws.p.v.device)
+    dot_work = plan.dot_work(A)
 
     # -- setup: r0 = b - A x0, p0 = dinv r0, pair 0, the state ----------------------------------------------------------
     ws.hist.zero_()
@@ -436,22 +422,20 @@ def cg(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, atol
 
     # -- chunks of check_every iterations; one 16-byte read-back each ---------------------------------------------------------
     sfx = "i64" if plan.is_i64 else "i32"
-    narrow = () if plan.is_i64 else (dptr(plan.cols16), plan.patterns)
+    blk = plan.matrix_block(A)
 
     def enqueue_diagonal(first, count):
-        _capi.call(f"hpcla_pcg_iterations_f64_{sfx}", plan.halo if plan.has_halo else None, A.backend.rccl,
-                   dptr(plan.rowptr_of(A)), dptr(plan.colval_split), *narrow, dptr(A.nzval), A.nrows_local, A.nnz, 0,
-                   dptr(plan.interior), plan.n_interior, dptr(plan.boundary), plan.n_boundary,
+        _capi.call(f"hpcla_pcg_iterations_f64_{sfx}", blk[0], A.backend.rccl, *blk[1:],
                    dptr(dinv.v) if dinv is not None else None, dptr(ws.x.v), dptr(ws.r.v), dptr(ws.p.v), dptr(ws.Ap.v),
-                   dptr(ws.hist), dptr(ws.pAp), dptr(plan._dot_work), dptr(ws.work), first, count, current_stream_ptr())
+                   dptr(ws.hist), dptr(ws.pAp), dptr(dot_work), dptr(ws.work), first, count, current_stream_ptr())
 
     def enqueue_fsai(first, count):
         _capi.call(f"hpcla_pcg_fsai_iterations_f64_{sfx}", A.backend.rccl, *blocks, dptr(ws.x.v), dptr(ws.r.v), dptr(ws.p.v),
-                   dptr(ws.Ap.v), dptr(ws.u.v), dptr(ws.z.v), dptr(ws.hist), dptr(ws.pAp), dptr(plan._dot_work), dptr(ws.work),
+                   dptr(ws.Ap.v), dptr(ws.u.v), dptr(ws.z.v), dptr(ws.hist), dptr(ws.pAp), dptr(dot_work), dptr(ws.work),
                    first, count, current_stream_ptr())
 
     if op is not None:
-        blocks = _matrix_block(A, plan) + _matrix_block(op.G, plan_g) + _matrix_block(op.Gt, plan_t)
+        blocks = blk + plan_g.matrix_block(op.G) + plan_t.matrix_block(op.Gt)
     iterations, status = _run_chunks(ws, A.backend, maxiter, check_every, enqueue_fsai if op is not None else enqueue_diagonal)
     h = _residual_norms(ws, b.backend, iterations)
     return ws.x, CGInfo(status == 1, iterations, _STATUS[status], h)

@@ -48,6 +48,61 @@ int spmv_fused_i64(const int64_t *, const int64_t *, const double *, const doubl
 int reduce_partials_sum(const double *partial, int64_t np, double *scratch, double *out,
                         void *stream);   // vecops.hip
 
+// the two launchers by the index type of rowptr: a template on I names spmv_split / spmv_fused and overload resolution picks
+static inline int spmv_split(const int32_t *rowptr, const int32_t *colval, const double *nzval, const double *x_own,
+                             const double *x_ghost, int64_t n_own, double *y, int64_t nrows, int64_t nnz, int index_base,
+                             const int32_t *bl, int64_t nb, void *stream, double *dot_partial, int64_t block_base)
+{
+    return spmv_split_i32(rowptr, colval, nzval, x_own, x_ghost, n_own, y, nrows, nnz, index_base, bl, nb, stream, dot_partial,
+                          block_base);
+}
+static inline int spmv_split(const int64_t *rowptr, const int64_t *colval, const double *nzval, const double *x_own,
+                             const double *x_ghost, int64_t n_own, double *y, int64_t nrows, int64_t nnz, int index_base,
+                             const int32_t *bl, int64_t nb, void *stream, double *dot_partial, int64_t block_base)
+{
+    return spmv_split_i64(rowptr, colval, nzval, x_own, x_ghost, n_own, y, nrows, nnz, index_base, bl, nb, stream, dot_partial,
+                          block_base);
+}
+static inline int spmv_fused(const int32_t *rowptr, const int32_t *colval, const double *nzval, const double *x_own,
+                             const double *x_ghost, int64_t n_own, double *y, int64_t nrows, int64_t nnz, int index_base,
+                             const int32_t *interior_list, int64_t interior_base, int64_t n_interior,
+                             const int32_t *boundary_list, int64_t n_boundary, const HaloWait &hw, const PushArgs &pa,
+                             void *stream, double *dot_partial)
+{
+    return spmv_fused_i32(rowptr, colval, nzval, x_own, x_ghost, n_own, y, nrows, nnz, index_base, interior_list, interior_base,
+                          n_interior, boundary_list, n_boundary, hw, pa, stream, dot_partial);
+}
+static inline int spmv_fused(const int64_t *rowptr, const int64_t *colval, const double *nzval, const double *x_own,
+                             const double *x_ghost, int64_t n_own, double *y, int64_t nrows, int64_t nnz, int index_base,
+                             const int32_t *interior_list, int64_t interior_base, int64_t n_interior,
+                             const int32_t *boundary_list, int64_t n_boundary, const HaloWait &hw, const PushArgs &pa,
+                             void *stream, double *dot_partial)
+{
+    return spmv_fused_i64(rowptr, colval, nzval, x_own, x_ghost, n_own, y, nrows, nnz, index_base, interior_list, interior_base,
+                          n_interior, boundary_list, n_boundary, hw, pa, stream, dot_partial);
+}
+
+template <typename I>
+struct SpmvBlock {                                                  // the plan and CSR arguments of one matrix
+    hpcla_halo_plan_t *plan;
+    const I *rowptr, *colval;
+    const int16_t *cols16;
+    const hpcla_block_patterns *patterns;
+    const double *nzval;
+    int64_t nrows, nnz;
+    int index_base;
+    const int32_t *interior;
+    int64_t n_interior;
+    const int32_t *boundary;
+    int64_t n_boundary;
+};
+
+// the last 32 bytes of a solver's `work`: its device-resident state words
+static inline int64_t *solver_state(void *work, int64_t work_bytes)
+{
+    return reinterpret_cast<int64_t *>(static_cast<char *>(work) + work_bytes) - 4;
+}
+
 // ---- RCCL entry points, resolved at first use (RcclApi: comm_internal.h) ----------------------
 static RcclApi g_rccl;
 
@@ -771,30 +826,27 @@ static int probe_interior(hpcla_halo_plan_t *plan, const int32_t *interior, int6
     return HPCLA_OK;
 }
 
-template <typename I, typename F, typename G>
-static int spmv_dist_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, const I *rowptr, const I *colval,
-                          const double *nzval, const double *x, int64_t n_own, double *y,
-                          int64_t nrows, int64_t nnz, int index_base, const int32_t *interior,
-                          int64_t n_interior, const int32_t *boundary, int64_t n_boundary,
-                          void *stream, double *dot_partial = nullptr, const int16_t *cols16 = nullptr,
-                          const hpcla_block_patterns *patterns = nullptr)
+template <typename I>
+static int spmv_dist_impl(const SpmvBlock<I> &m, const double *x, int64_t n_own, double *y, void *stream,
+                          double *dot_partial = nullptr)
 {
-    // cols16 != null (Int32 plans only): the plan's 16-bit block-relative copy of the columns of its INTERIOR blocks (plans
+    hpcla_halo_plan_t *const plan = m.plan;
+    // m.cols16 != null (Int32 plans only): the plan's 16-bit block-relative copy of the columns of its INTERIOR blocks (plans
     // without neighbours: of every block).  Those blocks then go through the narrow form of the row-gather kernel
     // (spmv_cols16_i32: 10 instead of 12 bytes per stored entry, the same bits); boundary blocks keep the Int32 kernel.
-    // patterns != null: those narrow launches take the pattern form (the plan's table of repeating block patterns,
+    // m.patterns != null: those narrow launches take the pattern form (the plan's table of repeating block patterns,
     // patterns.hip) -- in every ordering below the same launches with one more argument.
-    const bool narrow = sizeof(I) == 4 && cols16_usable(cols16, nzval);
+    const bool narrow = sizeof(I) == 4 && cols16_usable(m.cols16, m.nzval);
     // the interior blocks in the narrow form on `st`: a contiguous run by its BASE (never through the list: probe_interior)
     auto interior_narrow = [&](void *st) -> int {
         if constexpr (sizeof(I) == 4) {
-            if (n_interior <= 0) return HPCLA_OK;
-            if (int rcq = probe_interior(plan, interior, n_interior)) return rcq;
+            if (m.n_interior <= 0) return HPCLA_OK;
+            if (int rcq = probe_interior(plan, m.interior, m.n_interior)) return rcq;
             if (plan->probed_contig)
-                return spmv_cols16_i32(rowptr, cols16, nzval, x, y, nrows, nnz, index_base, nullptr, n_interior, st, dot_partial,
-                                       plan->probed_first, patterns);
-            return spmv_cols16_i32(rowptr, cols16, nzval, x, y, nrows, nnz, index_base, interior, n_interior, st, dot_partial, -1,
-                                   patterns);
+                return spmv_cols16_i32(m.rowptr, m.cols16, m.nzval, x, y, m.nrows, m.nnz, m.index_base, nullptr, m.n_interior, st,
+                                       dot_partial, plan->probed_first, m.patterns);
+            return spmv_cols16_i32(m.rowptr, m.cols16, m.nzval, x, y, m.nrows, m.nnz, m.index_base, m.interior, m.n_interior, st,
+                                   dot_partial, -1, m.patterns);
         } else {
             (void)st;
             return set_error(HPCLA_ERR_INVALID, "spmv_dist: 16-bit columns need an Int32 plan");
@@ -805,12 +857,12 @@ static int spmv_dist_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, const
         // no neighbours: every column is owned; one launch over all row blocks
         if constexpr (sizeof(I) == 4)
             if (narrow)
-                return spmv_cols16_i32(rowptr, cols16, nzval, x, y, nrows, nnz, index_base, nullptr, 0, stream, dot_partial, -1,
-                                       patterns);
-        return split_fn(rowptr, colval, nzval, x, plan ? plan->ghost : nullptr, n_own, y, nrows,
-                        nnz, index_base, nullptr, 0, stream, dot_partial, -1);
+                return spmv_cols16_i32(m.rowptr, m.cols16, m.nzval, x, y, m.nrows, m.nnz, m.index_base, nullptr, 0, stream,
+                                       dot_partial, -1, m.patterns);
+        return spmv_split(m.rowptr, m.colval, m.nzval, x, plan ? plan->ghost : nullptr, n_own, y, m.nrows, m.nnz, m.index_base,
+                          nullptr, 0, stream, dot_partial, -1);
     }
-    if ((n_interior > 0 && !interior) || (n_boundary > 0 && !boundary))
+    if ((m.n_interior > 0 && !m.interior) || (m.n_boundary > 0 && !m.boundary))
         return set_error(HPCLA_ERR_INVALID, "spmv_dist: null block list");
     // side stream: exchange, then the boundary row blocks (they need the ghosts); caller's stream:
     // the interior row blocks, concurrently.  Both write disjoint rows of y; the caller's stream
@@ -831,8 +883,8 @@ static int spmv_dist_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, const
         //           follow; the boundary blocks come last and poll the local flag lines before their first ghost
         //           gather (window.hip, halo_wait.h, spmv.hip).  No RCCL kernel, no side stream, no events, no
         //           extra launch; the exchange overlaps all interior blocks.
-        if (n_interior > 0) {
-            int rcq = probe_interior(plan, interior, n_interior);
+        if (m.n_interior > 0) {
+            int rcq = probe_interior(plan, m.interior, m.n_interior);
             if (rcq) return rcq;
         }
         if (narrow) {
@@ -841,23 +893,23 @@ static int spmv_dist_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, const
             //  (the ordering of hpcla_spmv_dist_packed_f64_i32).  Both column widths in one kernel body would cost the
             //  stencil path registers at the 64-VGPR edge; two more launches on one stream buy 2 B per interior entry.
             //  Everything that can be refused is checked BEFORE the exchange is posted: push_post commits the step's readers.
-            const int64_t all_blocks = (nrows + hpcla_spmv_rows_per_block() - 1) / hpcla_spmv_rows_per_block();
-            if (nrows < 0 || nnz < 0 || (index_base != 0 && index_base != 1))
+            const int64_t all_blocks = (m.nrows + hpcla_spmv_rows_per_block() - 1) / hpcla_spmv_rows_per_block();
+            if (m.nrows < 0 || m.nnz < 0 || (m.index_base != 0 && m.index_base != 1))
                 return set_error(HPCLA_ERR_INVALID, "spmv_dist: bad size or index_base");
-            if (n_interior < 0 || n_boundary < 0 || n_interior + n_boundary > all_blocks)
+            if (m.n_interior < 0 || m.n_boundary < 0 || m.n_interior + m.n_boundary > all_blocks)
                 return set_error(HPCLA_ERR_INVALID, "spmv_dist: block counts out of range");
-            if (!rowptr || !y || (nnz > 0 && (!colval || !nzval || !x)))
+            if (!m.rowptr || !y || (m.nnz > 0 && (!m.colval || !m.nzval || !x)))
                 return set_error(HPCLA_ERR_INVALID, "spmv_dist: null array");
-            int rcn = push_post(plan, x, n_boundary, stream);
+            int rcn = push_post(plan, x, m.n_boundary, stream);
             if (rcn) return rcn;
             rcn = interior_narrow(stream);
-            if (rcn) { (void)push_abandon_waiters(plan, n_boundary, stream); return rcn; }   // the posted readers still release
-            if (n_boundary > 0) {
+            if (rcn) { (void)push_abandon_waiters(plan, m.n_boundary, stream); return rcn; }   // the posted readers still release
+            if (m.n_boundary > 0) {
                 PushArgs nopush;
                 memset(&nopush, 0, sizeof(nopush));
-                rcn = fused_fn(rowptr, colval, nzval, x, plan->ghost, n_own, y, nrows, nnz, index_base, nullptr, 0, 0, boundary,
-                               n_boundary, push_wait_args(plan, n_boundary), nopush, stream, dot_partial);
-                if (rcn) { (void)push_abandon_waiters(plan, n_boundary, stream); return rcn; }
+                rcn = spmv_fused(m.rowptr, m.colval, m.nzval, x, plan->ghost, n_own, y, m.nrows, m.nnz, m.index_base, nullptr, 0, 0,
+                                 m.boundary, m.n_boundary, push_wait_args(plan, m.n_boundary), nopush, stream, dot_partial);
+                if (rcn) { (void)push_abandon_waiters(plan, m.n_boundary, stream); return rcn; }
             }
             return HPCLA_OK;
         }
@@ -865,20 +917,20 @@ static int spmv_dist_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, const
         int rcp;
         const bool own_push_kernel = (plan->idx_is_i64 != 0) != (sizeof(I) == 8);
         if (!own_push_kernel) {
-            rcp = push_begin(plan, x, n_boundary, &pa);    // the push rides in the leading workgroups of the launch
-        } else {                                           // send lists typed unlike the matrix: push kernel of its own
-            rcp = push_post(plan, x, n_boundary, stream);  // (commits the step's epoch readers: see below)
+            rcp = push_begin(plan, x, m.n_boundary, &pa);    // the push rides in the leading workgroups of the launch
+        } else {                                             // send lists typed unlike the matrix: push kernel of its own
+            rcp = push_post(plan, x, m.n_boundary, stream);  // (commits the step's epoch readers: see below)
             memset(&pa, 0, sizeof(pa));
         }
         if (rcp) return rcp;
-        const bool contig = n_interior > 0 && plan->probed_contig;
+        const bool contig = m.n_interior > 0 && plan->probed_contig;
         // (the ghost argument is buffer 0; a boundary workgroup computes the buffer of its epoch after its wait)
-        const int rcf = fused_fn(rowptr, colval, nzval, x, plan->ghost, n_own, y, nrows, nnz, index_base,
-                                 contig ? nullptr : interior, contig ? plan->probed_first : 0, n_interior, boundary,
-                                 n_boundary, push_wait_args(plan, n_boundary), pa, stream, dot_partial);
+        const int rcf = spmv_fused(m.rowptr, m.colval, m.nzval, x, plan->ghost, n_own, y, m.nrows, m.nnz, m.index_base,
+                                   contig ? nullptr : m.interior, contig ? plan->probed_first : 0, m.n_interior, m.boundary,
+                                   m.n_boundary, push_wait_args(plan, m.n_boundary), pa, stream, dot_partial);
         // a refused launch behind an ALREADY POSTED push would strand the exchange's waiting readers (the step counter
         // never advances, every later exchange of the plan reuses the epoch): release them without computing
-        if (rcf && own_push_kernel) (void)push_abandon_waiters(plan, n_boundary, stream);
+        if (rcf && own_push_kernel) (void)push_abandon_waiters(plan, m.n_boundary, stream);
         return rcf;
     }
     if (mode == HALO_SERIAL) {
@@ -886,12 +938,12 @@ static int spmv_dist_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, const
         if (rc0) return rc0;
         if (narrow) {      // same stream: the interior blocks narrow, then the boundary blocks (ghost columns) on Int32 columns
             rc0 = interior_narrow(stream);
-            if (rc0 || n_boundary <= 0) return rc0;
-            return split_fn(rowptr, colval, nzval, x, plan->ghost, n_own, y, nrows, nnz, index_base, boundary, n_boundary,
-                            stream, dot_partial, -1);
+            if (rc0 || m.n_boundary <= 0) return rc0;
+            return spmv_split(m.rowptr, m.colval, m.nzval, x, plan->ghost, n_own, y, m.nrows, m.nnz, m.index_base, m.boundary,
+                              m.n_boundary, stream, dot_partial, -1);
         }
-        return split_fn(rowptr, colval, nzval, x, plan->ghost, n_own, y, nrows, nnz, index_base, nullptr, 0,
-                        stream, dot_partial, -1);
+        return spmv_split(m.rowptr, m.colval, m.nzval, x, plan->ghost, n_own, y, m.nrows, m.nnz, m.index_base, nullptr, 0,
+                          stream, dot_partial, -1);
     }
     int rc = halo_post(plan, x, stream, false);
     if (rc) return rc;
@@ -902,24 +954,24 @@ static int spmv_dist_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, const
         (void)hipStreamWaitEvent(as_stream(stream), plan->ev_done, 0);
         return code;
     };
-    if (n_boundary > 0) {
-        rc = split_fn(rowptr, colval, nzval, x, plan->ghost, n_own, y, nrows, nnz, index_base,
-                      boundary, n_boundary, plan->side, dot_partial, -1);
+    if (m.n_boundary > 0) {
+        rc = spmv_split(m.rowptr, m.colval, m.nzval, x, plan->ghost, n_own, y, m.nrows, m.nnz, m.index_base,
+                        m.boundary, m.n_boundary, plan->side, dot_partial, -1);
         if (rc) return join_and_fail(rc);
     }
     HPCLA_CHECK_HIP(hipEventRecord(plan->ev_done, plan->side));
-    if (n_interior > 0 && narrow) {
+    if (m.n_interior > 0 && narrow) {
         rc = interior_narrow(stream);
         if (rc) return join_and_fail(rc);
-    } else if (n_interior > 0) {
-        rc = probe_interior(plan, interior, n_interior);
+    } else if (m.n_interior > 0) {
+        rc = probe_interior(plan, m.interior, m.n_interior);
         if (rc) return join_and_fail(rc);
         if (plan->probed_contig)
-            rc = split_fn(rowptr, colval, nzval, x, plan->ghost, n_own, y, nrows, nnz, index_base,
-                          nullptr, n_interior, stream, dot_partial, plan->probed_first);
+            rc = spmv_split(m.rowptr, m.colval, m.nzval, x, plan->ghost, n_own, y, m.nrows, m.nnz, m.index_base,
+                            nullptr, m.n_interior, stream, dot_partial, plan->probed_first);
         else
-            rc = split_fn(rowptr, colval, nzval, x, plan->ghost, n_own, y, nrows, nnz, index_base,
-                          interior, n_interior, stream, dot_partial, -1);
+            rc = spmv_split(m.rowptr, m.colval, m.nzval, x, plan->ghost, n_own, y, m.nrows, m.nnz, m.index_base,
+                            m.interior, m.n_interior, stream, dot_partial, -1);
         if (rc) return join_and_fail(rc);
     }
     return hpcla_halo_end(plan, stream);
@@ -928,26 +980,21 @@ static int spmv_dist_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, const
 // y = A*x and out = x.y in one pass over A (CG's p.Ap): the SpMV workgroups leave per-row-block
 // partials in `work`, summed in index order afterwards, then all-reduced.  Needs x partitioned like
 // A's rows (n_own == nrows) and interior+boundary lists that cover every row block exactly once.
-template <typename I, typename F, typename G>
-static int spmv_dist_dot_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const I *rowptr,
-                              const I *colval, const double *nzval, const double *x, int64_t n_own,
-                              double *y, int64_t nrows, int64_t nnz, int index_base,
-                              const int32_t *interior, int64_t n_interior, const int32_t *boundary,
-                              int64_t n_boundary, double *dot_out_dev, void *work, void *stream,
-                              const int16_t *cols16 = nullptr, const hpcla_block_patterns *patterns = nullptr)
+template <typename I>
+static int spmv_dist_dot_impl(const SpmvBlock<I> &m, hpcla_comm_t *comm, const double *x, int64_t n_own, double *y,
+                              double *dot_out_dev, void *work, void *stream)
 {
     if (!dot_out_dev || !work) return set_error(HPCLA_ERR_INVALID, "spmv_dist_dot: null out/work");
-    if (n_own != nrows)
+    if (n_own != m.nrows)
         return set_error(HPCLA_ERR_INVALID, "spmv_dist_dot: x must be partitioned like the rows of A");
     const int rpb = hpcla_spmv_rows_per_block();
-    const int64_t all_blocks = (nrows + rpb - 1) / rpb;
-    const bool has_halo = plan && !(plan->send_ranks.empty() && plan->recv_ranks.empty());
-    if (has_halo && n_interior + n_boundary != all_blocks)
+    const int64_t all_blocks = (m.nrows + rpb - 1) / rpb;
+    const bool has_halo = m.plan && !(m.plan->send_ranks.empty() && m.plan->recv_ranks.empty());
+    if (has_halo && m.n_interior + m.n_boundary != all_blocks)
         return set_error(HPCLA_ERR_INVALID, "spmv_dist_dot: block lists must cover every row block");
     double *scratch = reinterpret_cast<double *>(work);          // 2048 doubles of stage-1 scratch
     double *partial = scratch + 2048;                            // then one double per row block
-    int rc = spmv_dist_impl<I>(split_fn, fused_fn, plan, rowptr, colval, nzval, x, n_own, y, nrows, nnz, index_base,
-                               interior, n_interior, boundary, n_boundary, stream, partial, cols16, patterns);
+    int rc = spmv_dist_impl<I>(m, x, n_own, y, stream, partial);
     if (rc) return rc;
     rc = reduce_partials_sum(partial, all_blocks, scratch, dot_out_dev, stream);
     if (rc) return rc;
@@ -969,9 +1016,9 @@ HPCLA_API int hpcla_spmv_dist_dot_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t 
                                           const int32_t *boundary_blocks, int64_t n_boundary,
                                           double *dot_out_dev, void *work, void *stream)
 {
-    return spmv_dist_dot_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, comm, rowptr, colval_split, nzval, x, n_own,
-                                       y, nrows, nnz, index_base, interior_blocks, n_interior,
-                                       boundary_blocks, n_boundary, dot_out_dev, work, stream);
+    return spmv_dist_dot_impl<int32_t>({plan, rowptr, colval_split, nullptr, nullptr, nzval, nrows, nnz, index_base, interior_blocks,
+                                        n_interior, boundary_blocks, n_boundary},
+                                       comm, x, n_own, y, dot_out_dev, work, stream);
 }
 
 HPCLA_API int hpcla_spmv_dist_dot_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm,
@@ -982,9 +1029,9 @@ HPCLA_API int hpcla_spmv_dist_dot_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t 
                                           const int32_t *boundary_blocks, int64_t n_boundary,
                                           double *dot_out_dev, void *work, void *stream)
 {
-    return spmv_dist_dot_impl<int64_t>(spmv_split_i64, spmv_fused_i64, plan, comm, rowptr, colval_split, nzval, x, n_own,
-                                       y, nrows, nnz, index_base, interior_blocks, n_interior,
-                                       boundary_blocks, n_boundary, dot_out_dev, work, stream);
+    return spmv_dist_dot_impl<int64_t>({plan, rowptr, colval_split, nullptr, nullptr, nzval, nrows, nnz, index_base, interior_blocks,
+                                        n_interior, boundary_blocks, n_boundary},
+                                       comm, x, n_own, y, dot_out_dev, work, stream);
 }
 
 HPCLA_API int hpcla_spmv_dist_f64_i32(hpcla_halo_plan_t *plan, const int32_t *rowptr,
@@ -994,9 +1041,9 @@ HPCLA_API int hpcla_spmv_dist_f64_i32(hpcla_halo_plan_t *plan, const int32_t *ro
                                       int64_t n_interior, const int32_t *boundary_blocks,
                                       int64_t n_boundary, void *stream)
 {
-    return spmv_dist_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, rowptr, colval_split, nzval, x, n_own, y,
-                                   nrows, nnz, index_base, interior_blocks, n_interior,
-                                   boundary_blocks, n_boundary, stream);
+    return spmv_dist_impl<int32_t>({plan, rowptr, colval_split, nullptr, nullptr, nzval, nrows, nnz, index_base, interior_blocks,
+                                    n_interior, boundary_blocks, n_boundary},
+                                   x, n_own, y, stream);
 }
 
 HPCLA_API int hpcla_spmv_dist_f64_i64(hpcla_halo_plan_t *plan, const int64_t *rowptr,
@@ -1006,9 +1053,9 @@ HPCLA_API int hpcla_spmv_dist_f64_i64(hpcla_halo_plan_t *plan, const int64_t *ro
                                       int64_t n_interior, const int32_t *boundary_blocks,
                                       int64_t n_boundary, void *stream)
 {
-    return spmv_dist_impl<int64_t>(spmv_split_i64, spmv_fused_i64, plan, rowptr, colval_split, nzval, x, n_own, y,
-                                   nrows, nnz, index_base, interior_blocks, n_interior,
-                                   boundary_blocks, n_boundary, stream);
+    return spmv_dist_impl<int64_t>({plan, rowptr, colval_split, nullptr, nullptr, nzval, nrows, nnz, index_base, interior_blocks,
+                                    n_interior, boundary_blocks, n_boundary},
+                                   x, n_own, y, stream);
 }
 
 // The two products above for a plan that holds a 16-bit copy of its interior blocks' columns (hpcla_cols16_encode_i32).
@@ -1019,8 +1066,9 @@ HPCLA_API int hpcla_spmv_dist_cols16_f64_i32(hpcla_halo_plan_t *plan, const int3
                                              const int32_t *interior_blocks, int64_t n_interior,
                                              const int32_t *boundary_blocks, int64_t n_boundary, void *stream)
 {
-    return spmv_dist_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, rowptr, colval_split, nzval, x, n_own, y, nrows, nnz,
-                                   index_base, interior_blocks, n_interior, boundary_blocks, n_boundary, stream, nullptr, cols16);
+    return spmv_dist_impl<int32_t>({plan, rowptr, colval_split, cols16, nullptr, nzval, nrows, nnz, index_base, interior_blocks,
+                                    n_interior, boundary_blocks, n_boundary},
+                                   x, n_own, y, stream);
 }
 
 HPCLA_API int hpcla_spmv_dist_dot_cols16_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int32_t *rowptr,
@@ -1030,9 +1078,9 @@ HPCLA_API int hpcla_spmv_dist_dot_cols16_f64_i32(hpcla_halo_plan_t *plan, hpcla_
                                                  const int32_t *boundary_blocks, int64_t n_boundary, double *dot_out_dev,
                                                  void *work, void *stream)
 {
-    return spmv_dist_dot_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, comm, rowptr, colval_split, nzval, x, n_own, y,
-                                       nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks, n_boundary,
-                                       dot_out_dev, work, stream, cols16);
+    return spmv_dist_dot_impl<int32_t>({plan, rowptr, colval_split, cols16, nullptr, nzval, nrows, nnz, index_base, interior_blocks,
+                                        n_interior, boundary_blocks, n_boundary},
+                                       comm, x, n_own, y, dot_out_dev, work, stream);
 }
 
 // ... and for a plan that also holds a table of repeating block patterns over those blocks (hpcla_block_patterns_create_i32).
@@ -1043,9 +1091,9 @@ HPCLA_API int hpcla_spmv_dist_patterns_f64_i32(hpcla_halo_plan_t *plan, const in
                                                int64_t nnz, int index_base, const int32_t *interior_blocks, int64_t n_interior,
                                                const int32_t *boundary_blocks, int64_t n_boundary, void *stream)
 {
-    return spmv_dist_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, rowptr, colval_split, nzval, x, n_own, y, nrows, nnz,
-                                   index_base, interior_blocks, n_interior, boundary_blocks, n_boundary, stream, nullptr, cols16,
-                                   patterns);
+    return spmv_dist_impl<int32_t>({plan, rowptr, colval_split, cols16, patterns, nzval, nrows, nnz, index_base, interior_blocks,
+                                    n_interior, boundary_blocks, n_boundary},
+                                   x, n_own, y, stream);
 }
 
 HPCLA_API int hpcla_spmv_dist_dot_patterns_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int32_t *rowptr,
@@ -1056,9 +1104,9 @@ HPCLA_API int hpcla_spmv_dist_dot_patterns_f64_i32(hpcla_halo_plan_t *plan, hpcl
                                                    const int32_t *boundary_blocks, int64_t n_boundary, double *dot_out_dev,
                                                    void *work, void *stream)
 {
-    return spmv_dist_dot_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, comm, rowptr, colval_split, nzval, x, n_own, y,
-                                       nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks, n_boundary,
-                                       dot_out_dev, work, stream, cols16, patterns);
+    return spmv_dist_dot_impl<int32_t>({plan, rowptr, colval_split, cols16, patterns, nzval, nrows, nnz, index_base, interior_blocks,
+                                        n_interior, boundary_blocks, n_boundary},
+                                       comm, x, n_own, y, dot_out_dev, work, stream);
 }
 
 // ---- k fused CG iterations in ONE host call ----------------------------------------------------------
@@ -1068,22 +1116,18 @@ HPCLA_API int hpcla_spmv_dist_dot_patterns_f64_i32(hpcla_halo_plan_t *plan, hpcl
 // hpcla_spmv_dist_dot_* (Ap = A p, pAp), hpcla_cg_residual_f64 (r -= a Ap, rr') and hpcla_cg_direction_f64
 // (x += a p, p = r + (rr'/rr) p) -- the same kernels with the same arguments as the three separate calls,
 // hence the same bits.  rr_hist_dev[j] holds sum r_j^2: [0] on entry, [1..iters] written here.
-template <typename I, typename F, typename G>
-static int cg_iterations_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const I *rowptr,
-                              const I *colval, const double *nzval, int64_t nrows, int64_t nnz, int index_base,
-                              const int32_t *interior, int64_t n_interior, const int32_t *boundary,
-                              int64_t n_boundary, double *x, double *r, double *p, double *Ap, double *rr_hist_dev,
-                              double *pAp_dev, void *dot_work, void *reduce_work, int iters, void *stream)
+template <typename I>
+static int cg_iterations_impl(const SpmvBlock<I> &a, hpcla_comm_t *comm, double *x, double *r, double *p, double *Ap,
+                              double *rr_hist_dev, double *pAp_dev, void *dot_work, void *reduce_work, int iters, void *stream)
 {
+    const int64_t nrows = a.nrows;
     if (iters < 0) return set_error(HPCLA_ERR_INVALID, "cg_iterations: negative iteration count");
     if (!rr_hist_dev || !pAp_dev || !dot_work || !reduce_work)
         return set_error(HPCLA_ERR_INVALID, "cg_iterations: null scalar / work buffer");
     if (nrows > 0 && (!x || !r || !p || !Ap)) return set_error(HPCLA_ERR_INVALID, "cg_iterations: null vector");
     for (int j = 0; j < iters; ++j) {
         double *rr = rr_hist_dev + j;
-        int rc = spmv_dist_dot_impl<I>(split_fn, fused_fn, plan, comm, rowptr, colval, nzval, p, nrows, Ap, nrows, nnz,
-                                       index_base, interior, n_interior, boundary, n_boundary, pAp_dev, dot_work,
-                                       stream);
+        int rc = spmv_dist_dot_impl<I>(a, comm, p, nrows, Ap, pAp_dev, dot_work, stream);
         if (rc) return rc;
         rc = hpcla_cg_residual_f64(comm, 1.0, rr, pAp_dev, Ap, r, nrows, rr + 1, reduce_work, stream);
         if (rc) return rc;
@@ -1101,9 +1145,9 @@ HPCLA_API int hpcla_cg_iterations_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t 
                                           double *pAp_dev, void *dot_work, void *reduce_work, int iters,
                                           void *stream)
 {
-    return cg_iterations_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, comm, rowptr, colval_split, nzval, nrows,
-                                       nnz, index_base, interior_blocks, n_interior, boundary_blocks, n_boundary, x, r,
-                                       p, Ap, rr_hist_dev, pAp_dev, dot_work, reduce_work, iters, stream);
+    return cg_iterations_impl<int32_t>({plan, rowptr, colval_split, nullptr, nullptr, nzval, nrows, nnz, index_base, interior_blocks,
+                                        n_interior, boundary_blocks, n_boundary},
+                                       comm, x, r, p, Ap, rr_hist_dev, pAp_dev, dot_work, reduce_work, iters, stream);
 }
 
 HPCLA_API int hpcla_cg_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int64_t *rowptr,
@@ -1114,9 +1158,9 @@ HPCLA_API int hpcla_cg_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t 
                                           double *pAp_dev, void *dot_work, void *reduce_work, int iters,
                                           void *stream)
 {
-    return cg_iterations_impl<int64_t>(spmv_split_i64, spmv_fused_i64, plan, comm, rowptr, colval_split, nzval, nrows,
-                                       nnz, index_base, interior_blocks, n_interior, boundary_blocks, n_boundary, x, r,
-                                       p, Ap, rr_hist_dev, pAp_dev, dot_work, reduce_work, iters, stream);
+    return cg_iterations_impl<int64_t>({plan, rowptr, colval_split, nullptr, nullptr, nzval, nrows, nnz, index_base, interior_blocks,
+                                        n_interior, boundary_blocks, n_boundary},
+                                       comm, x, r, p, Ap, rr_hist_dev, pAp_dev, dot_work, reduce_work, iters, stream);
 }
 
 // ---- a chunk of gated, diagonally preconditioned CG iterations in ONE host call (the solver, hp.cg) -------------
@@ -1129,24 +1173,20 @@ HPCLA_API int hpcla_cg_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t 
 // Gate A is the residual kernel's own predicate and is recorded by the single-workgroup second stage; gate B is folded
 // into that second stage where no all-reduce follows it (comm == NULL), else it is one 64-lane launch behind the
 // all-reduce.  hist_dev[2 j], hist_dev[2 j + 1] = sum r_j^2, sum r_j (dinv r_j): the pair is all-reduced in place.
-template <typename I, typename F, typename G>
-static int pcg_iterations_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const I *rowptr,
-                               const I *colval, const int16_t *cols16, const hpcla_block_patterns *patterns,
-                               const double *nzval, int64_t nrows, int64_t nnz, int index_base, const int32_t *interior,
-                               int64_t n_interior, const int32_t *boundary, int64_t n_boundary, const double *dinv, double *x,
-                               double *r, double *p, double *Ap, double *hist_dev, double *pAp_dev, void *dot_work,
-                               void *pcg_work, int64_t first_iter, int iters, void *stream)
+template <typename I>
+static int pcg_iterations_impl(const SpmvBlock<I> &a, hpcla_comm_t *comm, const double *dinv, double *x, double *r, double *p,
+                               double *Ap, double *hist_dev, double *pAp_dev, void *dot_work, void *pcg_work,
+                               int64_t first_iter, int iters, void *stream)
 {
+    const int64_t nrows = a.nrows;
     if (iters < 0 || first_iter < 1) return set_error(HPCLA_ERR_INVALID, "pcg_iterations: negative count or first_iter < 1");
     if (!hist_dev || !pAp_dev || !dot_work || !pcg_work)
         return set_error(HPCLA_ERR_INVALID, "pcg_iterations: null scalar / work buffer");
     if (nrows > 0 && (!x || !r || !p || !Ap)) return set_error(HPCLA_ERR_INVALID, "pcg_iterations: null vector");
-    int64_t *state = reinterpret_cast<int64_t *>(static_cast<char *>(pcg_work) + hpcla_pcg_work_bytes()) - 4;
+    int64_t *state = solver_state(pcg_work, hpcla_pcg_work_bytes());
     for (int64_t j = first_iter; j < first_iter + iters; ++j) {
         double *prev = hist_dev + 2 * (j - 1), *cur = hist_dev + 2 * j;
-        int rc = spmv_dist_dot_impl<I>(split_fn, fused_fn, plan, comm, rowptr, colval, nzval, p, nrows, Ap, nrows, nnz,
-                                       index_base, interior, n_interior, boundary, n_boundary, pAp_dev, dot_work,
-                                       stream, cols16, patterns);
+        int rc = spmv_dist_dot_impl<I>(a, comm, p, nrows, Ap, pAp_dev, dot_work, stream);
         if (rc) return rc;
         rc = hpcla_pcg_residual_f64(comm, prev + 1, pAp_dev, Ap, dinv, r, nrows, j, state, cur, pcg_work, stream);
         if (rc) return rc;
@@ -1164,10 +1204,9 @@ HPCLA_API int hpcla_pcg_iterations_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t
                                            double *r, double *p, double *Ap, double *hist_dev, double *pAp_dev,
                                            void *dot_work, void *pcg_work, int64_t first_iter, int iters, void *stream)
 {
-    return pcg_iterations_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, comm, rowptr, colval_split, cols16, patterns,
-                                        nzval, nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks,
-                                        n_boundary, dinv, x, r, p, Ap, hist_dev, pAp_dev, dot_work, pcg_work, first_iter,
-                                        iters, stream);
+    return pcg_iterations_impl<int32_t>({plan, rowptr, colval_split, cols16, patterns, nzval, nrows, nnz, index_base, interior_blocks,
+                                         n_interior, boundary_blocks, n_boundary},
+                                        comm, dinv, x, r, p, Ap, hist_dev, pAp_dev, dot_work, pcg_work, first_iter, iters, stream);
 }
 
 HPCLA_API int hpcla_pcg_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int64_t *rowptr,
@@ -1177,10 +1216,9 @@ HPCLA_API int hpcla_pcg_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t
                                            double *r, double *p, double *Ap, double *hist_dev, double *pAp_dev,
                                            void *dot_work, void *pcg_work, int64_t first_iter, int iters, void *stream)
 {
-    return pcg_iterations_impl<int64_t>(spmv_split_i64, spmv_fused_i64, plan, comm, rowptr, colval_split, nullptr, nullptr,
-                                        nzval, nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks,
-                                        n_boundary, dinv, x, r, p, Ap, hist_dev, pAp_dev, dot_work, pcg_work, first_iter,
-                                        iters, stream);
+    return pcg_iterations_impl<int64_t>({plan, rowptr, colval_split, nullptr, nullptr, nzval, nrows, nnz, index_base, interior_blocks,
+                                         n_interior, boundary_blocks, n_boundary},
+                                        comm, dinv, x, r, p, Ap, hist_dev, pAp_dev, dot_work, pcg_work, first_iter, iters, stream);
 }
 
 // ---- the same chunk with M = Gt G, a factorised sparse approximate inverse (hp.cg with M = hp.fsai(A)) -----------------
@@ -1193,22 +1231,7 @@ HPCLA_API int hpcla_pcg_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t
 //   6. x += a p, p = z + b p    hpcla_pcg_direction_f64 with z in place of r and dinv == NULL, gated
 // Behind the deciding iteration r is frozen, so 3-5 recompute what they computed and write pairs nobody reads.
 template <typename I>
-struct SpmvBlock {                                                  // the plan and CSR arguments of one matrix
-    hpcla_halo_plan_t *plan;
-    const I *rowptr, *colval;
-    const int16_t *cols16;
-    const hpcla_block_patterns *patterns;
-    const double *nzval;
-    int64_t nrows, nnz;
-    int index_base;
-    const int32_t *interior;
-    int64_t n_interior;
-    const int32_t *boundary;
-    int64_t n_boundary;
-};
-
-template <typename I, typename F, typename G>
-static int pcg_fsai_iterations_impl(F split_fn, G fused_fn, hpcla_comm_t *comm, const SpmvBlock<I> &a, const SpmvBlock<I> &g,
+static int pcg_fsai_iterations_impl(hpcla_comm_t *comm, const SpmvBlock<I> &a, const SpmvBlock<I> &g,
                                     const SpmvBlock<I> &gt, double *x, double *r, double *p, double *Ap, double *u, double *z,
                                     double *hist_dev, double *pAp_dev, void *dot_work, void *pcg_work, int64_t first_iter,
                                     int iters, void *stream)
@@ -1220,20 +1243,16 @@ static int pcg_fsai_iterations_impl(F split_fn, G fused_fn, hpcla_comm_t *comm, 
     const int64_t n = a.nrows;
     if (g.nrows != n || gt.nrows != n) return set_error(HPCLA_ERR_INVALID, "pcg_fsai_iterations: G and Gt must have A's rows");
     if (n > 0 && (!x || !r || !p || !Ap || !u || !z)) return set_error(HPCLA_ERR_INVALID, "pcg_fsai_iterations: null vector");
-    int64_t *state = reinterpret_cast<int64_t *>(static_cast<char *>(pcg_work) + hpcla_pcg_work_bytes()) - 4;
+    int64_t *state = solver_state(pcg_work, hpcla_pcg_work_bytes());
     for (int64_t j = first_iter; j < first_iter + iters; ++j) {
         double *prev = hist_dev + 2 * (j - 1), *cur = hist_dev + 2 * j;
-        int rc = spmv_dist_dot_impl<I>(split_fn, fused_fn, a.plan, comm, a.rowptr, a.colval, a.nzval, p, n, Ap, n, a.nnz,
-                                       a.index_base, a.interior, a.n_interior, a.boundary, a.n_boundary, pAp_dev, dot_work,
-                                       stream, a.cols16, a.patterns);
+        int rc = spmv_dist_dot_impl<I>(a, comm, p, n, Ap, pAp_dev, dot_work, stream);
         if (rc) return rc;
         rc = hpcla_pcg_residual_f64(comm, prev + 1, pAp_dev, Ap, nullptr, r, n, j, state, cur, pcg_work, stream);
         if (rc) return rc;
-        rc = spmv_dist_impl<I>(split_fn, fused_fn, g.plan, g.rowptr, g.colval, g.nzval, r, n, u, n, g.nnz, g.index_base,
-                               g.interior, g.n_interior, g.boundary, g.n_boundary, stream, nullptr, g.cols16, g.patterns);
+        rc = spmv_dist_impl<I>(g, r, n, u, stream);
         if (rc) return rc;
-        rc = spmv_dist_impl<I>(split_fn, fused_fn, gt.plan, gt.rowptr, gt.colval, gt.nzval, u, n, z, n, gt.nnz, gt.index_base,
-                               gt.interior, gt.n_interior, gt.boundary, gt.n_boundary, stream, nullptr, gt.cols16, gt.patterns);
+        rc = spmv_dist_impl<I>(gt, u, n, z, stream);
         if (rc) return rc;
         rc = hpcla_nrm2sq_f64(comm, u, n, cur + 1, pcg_work, stream);
         if (rc) return rc;
@@ -1262,8 +1281,8 @@ HPCLA_API int hpcla_pcg_fsai_iterations_f64_i32(
                                interior_blocks_g, n_interior_g, boundary_blocks_g, n_boundary_g};
     const SpmvBlock<int32_t> gt{plan_t, rowptr_t, colval_split_t, cols16_t, patterns_t, nzval_t, nrows_t, nnz_t, index_base_t,
                                 interior_blocks_t, n_interior_t, boundary_blocks_t, n_boundary_t};
-    return pcg_fsai_iterations_impl<int32_t>(spmv_split_i32, spmv_fused_i32, comm, a, g, gt, x, r, p, Ap, u, z, hist_dev, pAp_dev,
-                                             dot_work, pcg_work, first_iter, iters, stream);
+    return pcg_fsai_iterations_impl<int32_t>(comm, a, g, gt, x, r, p, Ap, u, z, hist_dev, pAp_dev, dot_work, pcg_work, first_iter,
+                                             iters, stream);
 }
 
 HPCLA_API int hpcla_pcg_fsai_iterations_f64_i64(
@@ -1283,8 +1302,8 @@ HPCLA_API int hpcla_pcg_fsai_iterations_f64_i64(
                                interior_blocks_g, n_interior_g, boundary_blocks_g, n_boundary_g};
     const SpmvBlock<int64_t> gt{plan_t, rowptr_t, colval_split_t, nullptr, nullptr, nzval_t, nrows_t, nnz_t, index_base_t,
                                 interior_blocks_t, n_interior_t, boundary_blocks_t, n_boundary_t};
-    return pcg_fsai_iterations_impl<int64_t>(spmv_split_i64, spmv_fused_i64, comm, a, g, gt, x, r, p, Ap, u, z, hist_dev, pAp_dev,
-                                             dot_work, pcg_work, first_iter, iters, stream);
+    return pcg_fsai_iterations_impl<int64_t>(comm, a, g, gt, x, r, p, Ap, u, z, hist_dev, pAp_dev, dot_work, pcg_work, first_iter,
+                                             iters, stream);
 }
 
 // ---- a chunk of gated BiCGStab iterations in ONE host call (the solver, hp.bicgstab) ------------------------------
@@ -1301,18 +1320,15 @@ HPCLA_API int hpcla_pcg_fsai_iterations_f64_i64(
 // One rank: 2 SpMV + 8 launches (every gate is folded into a second stage).  N ranks: + 3 window all-reduces and 3 64-lane
 // gate launches.  hist_dev[2 j], hist_dev[2 j + 1] = sum r_j^2 (sum s_j^2 for a half-step stop), rhat.r_j: the pair is
 // all-reduced in place and its second entry is the rho of iteration j + 1.  scal_dev: rv, ts, tt, ss.
-template <typename I, typename F, typename G>
-static int bicgstab_iterations_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const I *rowptr,
-                                    const I *colval, const int16_t *cols16, const hpcla_block_patterns *patterns,
-                                    const double *nzval, int64_t nrows, int64_t nnz, int index_base, const int32_t *interior,
-                                    int64_t n_interior, const int32_t *boundary, int64_t n_boundary, const double *dinv,
-                                    double *x, double *r, const double *rhat, double *p, double *ph, double *v, double *s,
-                                    double *sh, double *t, double *hist_dev, double *scal_dev, void *work, int64_t first_iter,
-                                    int iters, void *stream)
+template <typename I>
+static int bicgstab_iterations_impl(const SpmvBlock<I> &a, hpcla_comm_t *comm, const double *dinv, double *x, double *r,
+                                    const double *rhat, double *p, double *ph, double *v, double *s, double *sh, double *t,
+                                    double *hist_dev, double *scal_dev, void *work, int64_t first_iter, int iters, void *stream)
 {
+    const int64_t nrows = a.nrows;
     if (iters < 0 || first_iter < 1)
         return set_error(HPCLA_ERR_INVALID, "bicgstab_iterations: negative count or first_iter < 1");
-    if (nrows < 0 || nnz < 0) return set_error(HPCLA_ERR_INVALID, "bicgstab_iterations: negative size");
+    if (nrows < 0 || a.nnz < 0) return set_error(HPCLA_ERR_INVALID, "bicgstab_iterations: negative size");
     if (!hist_dev || !scal_dev || !work) return set_error(HPCLA_ERR_INVALID, "bicgstab_iterations: null scalar / work buffer");
     if (nrows > 0 && (!x || !r || !rhat || !p || !v || !s || !t || (dinv && (!ph || !sh))))
         return set_error(HPCLA_ERR_INVALID, "bicgstab_iterations: null vector");
@@ -1321,20 +1337,18 @@ static int bicgstab_iterations_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *p
          reinterpret_cast<uintptr_t>(t) | reinterpret_cast<uintptr_t>(dinv) |
          (dinv ? reinterpret_cast<uintptr_t>(ph) | reinterpret_cast<uintptr_t>(sh) : 0)) & 15)
         return set_error(HPCLA_ERR_INVALID, "bicgstab_iterations: vectors must be 16-byte aligned");
-    int64_t *state = reinterpret_cast<int64_t *>(static_cast<char *>(work) + hpcla_bicgstab_work_bytes()) - 4;
+    int64_t *state = solver_state(work, hpcla_bicgstab_work_bytes());
     double *in1 = dinv ? ph : p, *in2 = dinv ? sh : s;
     double *rv = scal_dev, *triple = scal_dev + 1;
     for (int64_t j = first_iter; j < first_iter + iters; ++j) {
         double *prev = hist_dev + 2 * (j - 1), *cur = hist_dev + 2 * j;
-        int rc = spmv_dist_impl<I>(split_fn, fused_fn, plan, rowptr, colval, nzval, in1, nrows, v, nrows, nnz, index_base,
-                                   interior, n_interior, boundary, n_boundary, stream, nullptr, cols16, patterns);
+        int rc = spmv_dist_impl<I>(a, in1, nrows, v, stream);
         if (rc) return rc;
         rc = hpcla_bicg_dot_f64(comm, rhat, v, nrows, j, prev + 1, state, rv, work, stream);
         if (rc) return rc;
         rc = hpcla_bicg_s_f64(prev + 1, rv, r, v, dinv, s, dinv ? sh : nullptr, nrows, j, state, stream);
         if (rc) return rc;
-        rc = spmv_dist_impl<I>(split_fn, fused_fn, plan, rowptr, colval, nzval, in2, nrows, t, nrows, nnz, index_base,
-                               interior, n_interior, boundary, n_boundary, stream, nullptr, cols16, patterns);
+        rc = spmv_dist_impl<I>(a, in2, nrows, t, stream);
         if (rc) return rc;
         rc = hpcla_bicg_tts_f64(comm, t, s, nrows, j, state, triple, work, stream);
         if (rc) return rc;
@@ -1356,10 +1370,10 @@ HPCLA_API int hpcla_bicgstab_iterations_f64_i32(hpcla_halo_plan_t *plan, hpcla_c
                                                 double *ph, double *v, double *s, double *sh, double *t, double *hist_dev,
                                                 double *scal_dev, void *work, int64_t first_iter, int iters, void *stream)
 {
-    return bicgstab_iterations_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, comm, rowptr, colval_split, cols16,
-                                             patterns, nzval, nrows, nnz, index_base, interior_blocks, n_interior,
-                                             boundary_blocks, n_boundary, dinv, x, r, rhat, p, ph, v, s, sh, t, hist_dev,
-                                             scal_dev, work, first_iter, iters, stream);
+    return bicgstab_iterations_impl<int32_t>({plan, rowptr, colval_split, cols16, patterns, nzval, nrows, nnz, index_base,
+                                              interior_blocks, n_interior, boundary_blocks, n_boundary},
+                                             comm, dinv, x, r, rhat, p, ph, v, s, sh, t, hist_dev, scal_dev, work, first_iter, iters,
+                                             stream);
 }
 
 HPCLA_API int hpcla_bicgstab_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int64_t *rowptr,
@@ -1370,10 +1384,10 @@ HPCLA_API int hpcla_bicgstab_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_c
                                                 double *s, double *sh, double *t, double *hist_dev, double *scal_dev,
                                                 void *work, int64_t first_iter, int iters, void *stream)
 {
-    return bicgstab_iterations_impl<int64_t>(spmv_split_i64, spmv_fused_i64, plan, comm, rowptr, colval_split, nullptr,
-                                             nullptr, nzval, nrows, nnz, index_base, interior_blocks, n_interior,
-                                             boundary_blocks, n_boundary, dinv, x, r, rhat, p, ph, v, s, sh, t, hist_dev,
-                                             scal_dev, work, first_iter, iters, stream);
+    return bicgstab_iterations_impl<int64_t>({plan, rowptr, colval_split, nullptr, nullptr, nzval, nrows, nnz, index_base,
+                                              interior_blocks, n_interior, boundary_blocks, n_boundary},
+                                             comm, dinv, x, r, rhat, p, ph, v, s, sh, t, hist_dev, scal_dev, work, first_iter, iters,
+                                             stream);
 }
 
 // ---- a chunk of gated LSQR iterations in ONE host call (the solver, hp.lsqr) ---------------------------------------
@@ -1388,35 +1402,27 @@ HPCLA_API int hpcla_bicgstab_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_c
 // One rank: 2 SpMV + 5 launches (the step is folded into vv's second stage).  N ranks: + 2 window all-reduces and one 64-lane
 // step launch.  hist_dev[2 j], hist_dev[2 j + 1] = |rbar_j|^2, |Abar' rbar_j|^2 of the recurrences: formed from global
 // scalars on every rank, never all-reduced.
-template <typename I, typename F, typename G>
-static int lsqr_iterations_impl(F split_fn, G fused_fn, hpcla_comm_t *comm, hpcla_halo_plan_t *plan, const I *rowptr,
-                                const I *colval, const int16_t *cols16, const hpcla_block_patterns *patterns,
-                                const double *nzval, int64_t nrows, int64_t nnz, int index_base, const int32_t *interior,
-                                int64_t n_interior, const int32_t *boundary, int64_t n_boundary, hpcla_halo_plan_t *plan_t,
-                                const I *rowptr_t, const I *colval_t, const int16_t *cols16_t,
-                                const hpcla_block_patterns *patterns_t, const double *nzval_t, int64_t nrows_t, int64_t nnz_t,
-                                int index_base_t, const int32_t *interior_t, int64_t n_interior_t, const int32_t *boundary_t,
-                                int64_t n_boundary_t, double *x, double *uh, double *vh, double *w, double *tu, double *tv,
-                                double *hist_dev, double *scal_dev, void *work, int64_t first_iter, int iters, void *stream)
+template <typename I>
+static int lsqr_iterations_impl(hpcla_comm_t *comm, const SpmvBlock<I> &a, const SpmvBlock<I> &at, double *x, double *uh,
+                                double *vh, double *w, double *tu, double *tv, double *hist_dev, double *scal_dev, void *work,
+                                int64_t first_iter, int iters, void *stream)
 {
+    const int64_t nrows = a.nrows, nrows_t = at.nrows;
     if (iters < 0 || first_iter < 1) return set_error(HPCLA_ERR_INVALID, "lsqr_iterations: negative count or first_iter < 1");
-    if (nrows < 0 || nnz < 0 || nrows_t < 0 || nnz_t < 0) return set_error(HPCLA_ERR_INVALID, "lsqr_iterations: negative size");
+    if (nrows < 0 || a.nnz < 0 || nrows_t < 0 || at.nnz < 0) return set_error(HPCLA_ERR_INVALID, "lsqr_iterations: negative size");
     if (!hist_dev || !scal_dev || !work) return set_error(HPCLA_ERR_INVALID, "lsqr_iterations: null scalar / work buffer");
     if ((nrows > 0 && (!uh || !tu)) || (nrows_t > 0 && (!x || !vh || !w || !tv)))
         return set_error(HPCLA_ERR_INVALID, "lsqr_iterations: null vector");
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(uh) | reinterpret_cast<uintptr_t>(vh) |
          reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(tu) | reinterpret_cast<uintptr_t>(tv)) & 15)
         return set_error(HPCLA_ERR_INVALID, "lsqr_iterations: vectors must be 16-byte aligned");
-    int64_t *state = reinterpret_cast<int64_t *>(static_cast<char *>(work) + hpcla_lsqr_work_bytes()) - 4;
+    int64_t *state = solver_state(work, hpcla_lsqr_work_bytes());
     for (int64_t j = first_iter; j < first_iter + iters; ++j) {
-        int rc = spmv_dist_impl<I>(split_fn, fused_fn, plan, rowptr, colval, nzval, vh, nrows_t, tu, nrows, nnz, index_base,
-                                   interior, n_interior, boundary, n_boundary, stream, nullptr, cols16, patterns);
+        int rc = spmv_dist_impl<I>(a, vh, nrows_t, tu, stream);
         if (rc) return rc;
         rc = hpcla_lsqr_u_f64(comm, scal_dev, tu, uh, nrows, j, state, work, stream);
         if (rc) return rc;
-        rc = spmv_dist_impl<I>(split_fn, fused_fn, plan_t, rowptr_t, colval_t, nzval_t, uh, nrows, tv, nrows_t, nnz_t,
-                               index_base_t, interior_t, n_interior_t, boundary_t, n_boundary_t, stream, nullptr, cols16_t,
-                               patterns_t);
+        rc = spmv_dist_impl<I>(at, uh, nrows, tv, stream);
         if (rc) return rc;
         rc = hpcla_lsqr_v_f64(comm, scal_dev, tv, vh, nrows_t, j, state, hist_dev + 2 * j, work, stream);
         if (rc) return rc;
@@ -1439,10 +1445,11 @@ HPCLA_API int hpcla_lsqr_iterations_f64_i32(hpcla_comm_t *comm, hpcla_halo_plan_
                                             double *hist_dev, double *scal_dev, void *work, int64_t first_iter, int iters,
                                             void *stream)
 {
-    return lsqr_iterations_impl<int32_t>(spmv_split_i32, spmv_fused_i32, comm, plan, rowptr, colval_split, cols16, patterns,
-                                         nzval, nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks,
-                                         n_boundary, plan_t, rowptr_t, colval_split_t, cols16_t, patterns_t, nzval_t, nrows_t,
-                                         nnz_t, index_base_t, interior_blocks_t, n_interior_t, boundary_blocks_t, n_boundary_t,
+    return lsqr_iterations_impl<int32_t>(comm,
+                                         {plan, rowptr, colval_split, cols16, patterns, nzval, nrows, nnz, index_base,
+                                          interior_blocks, n_interior, boundary_blocks, n_boundary},
+                                         {plan_t, rowptr_t, colval_split_t, cols16_t, patterns_t, nzval_t, nrows_t, nnz_t,
+                                          index_base_t, interior_blocks_t, n_interior_t, boundary_blocks_t, n_boundary_t},
                                          x, uh, vh, w, tu, tv, hist_dev, scal_dev, work, first_iter, iters, stream);
 }
 
@@ -1457,10 +1464,11 @@ HPCLA_API int hpcla_lsqr_iterations_f64_i64(hpcla_comm_t *comm, hpcla_halo_plan_
                                             double *vh, double *w, double *tu, double *tv, double *hist_dev, double *scal_dev,
                                             void *work, int64_t first_iter, int iters, void *stream)
 {
-    return lsqr_iterations_impl<int64_t>(spmv_split_i64, spmv_fused_i64, comm, plan, rowptr, colval_split, nullptr, nullptr,
-                                         nzval, nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks,
-                                         n_boundary, plan_t, rowptr_t, colval_split_t, nullptr, nullptr, nzval_t, nrows_t,
-                                         nnz_t, index_base_t, interior_blocks_t, n_interior_t, boundary_blocks_t, n_boundary_t,
+    return lsqr_iterations_impl<int64_t>(comm,
+                                         {plan, rowptr, colval_split, nullptr, nullptr, nzval, nrows, nnz, index_base,
+                                          interior_blocks, n_interior, boundary_blocks, n_boundary},
+                                         {plan_t, rowptr_t, colval_split_t, nullptr, nullptr, nzval_t, nrows_t, nnz_t,
+                                          index_base_t, interior_blocks_t, n_interior_t, boundary_blocks_t, n_boundary_t},
                                          x, uh, vh, w, tu, tv, hist_dev, scal_dev, work, first_iter, iters, stream);
 }
 
@@ -1475,17 +1483,14 @@ HPCLA_API int hpcla_lsqr_iterations_f64_i64(hpcla_comm_t *comm, hpcla_halo_plan_
 // One rank: SpMV + dot stage + 3 launches (the step is folded into bb's second stage).  N ranks: + 2 window all-reduces and
 // one 64-lane step launch.  hist_dev[2 j], hist_dev[2 j + 1] = phibar_j^2, beta_{j+1}^2: formed from global scalars on every
 // rank, never all-reduced.
-template <typename I, typename F, typename G>
-static int minres_iterations_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const I *rowptr,
-                                  const I *colval, const int16_t *cols16, const hpcla_block_patterns *patterns,
-                                  const double *nzval, int64_t nrows, int64_t nnz, int index_base, const int32_t *interior,
-                                  int64_t n_interior, const int32_t *boundary, int64_t n_boundary, const double *dinv, double *x,
-                                  double *r_a, double *r_b, double *y_a, double *y_b, double *w_a, double *w_b, double *t,
-                                  double *hist_dev, double *scal_dev, void *dot_work, void *work, int64_t first_iter, int iters,
-                                  void *stream)
+template <typename I>
+static int minres_iterations_impl(const SpmvBlock<I> &a, hpcla_comm_t *comm, const double *dinv, double *x, double *r_a,
+                                  double *r_b, double *y_a, double *y_b, double *w_a, double *w_b, double *t, double *hist_dev,
+                                  double *scal_dev, void *dot_work, void *work, int64_t first_iter, int iters, void *stream)
 {
+    const int64_t nrows = a.nrows;
     if (iters < 0 || first_iter < 1) return set_error(HPCLA_ERR_INVALID, "minres_iterations: negative count or first_iter < 1");
-    if (nrows < 0 || nnz < 0) return set_error(HPCLA_ERR_INVALID, "minres_iterations: negative size");
+    if (nrows < 0 || a.nnz < 0) return set_error(HPCLA_ERR_INVALID, "minres_iterations: negative size");
     if (!hist_dev || !scal_dev || !dot_work || !work)
         return set_error(HPCLA_ERR_INVALID, "minres_iterations: null scalar / work buffer");
     if (nrows > 0 && (!x || !r_a || !r_b || !w_a || !w_b || !t || (dinv && (!y_a || !y_b))))
@@ -1495,14 +1500,12 @@ static int minres_iterations_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *pla
          reinterpret_cast<uintptr_t>(dinv) |
          (dinv ? reinterpret_cast<uintptr_t>(y_a) | reinterpret_cast<uintptr_t>(y_b) : 0)) & 15)
         return set_error(HPCLA_ERR_INVALID, "minres_iterations: vectors must be 16-byte aligned");
-    int64_t *state = reinterpret_cast<int64_t *>(static_cast<char *>(work) + hpcla_minres_work_bytes()) - 4;
+    int64_t *state = solver_state(work, hpcla_minres_work_bytes());
     double *rbuf[2] = {r_a, r_b}, *wbuf[2] = {w_a, w_b};
     double *ybuf[2] = {dinv ? y_a : r_a, dinv ? y_b : r_b};
     for (int64_t j = first_iter; j < first_iter + iters; ++j) {
         const int cur = (int)((j - 1) & 1), nxt = (int)(j & 1);
-        int rc = spmv_dist_dot_impl<I>(split_fn, fused_fn, plan, comm, rowptr, colval, nzval, ybuf[cur], nrows, t, nrows, nnz,
-                                       index_base, interior, n_interior, boundary, n_boundary, scal_dev + MINRES_YT, dot_work,
-                                       stream, cols16, patterns);
+        int rc = spmv_dist_dot_impl<I>(a, comm, ybuf[cur], nrows, t, scal_dev + MINRES_YT, dot_work, stream);
         if (rc) return rc;
         rc = hpcla_minres_r_f64(comm, scal_dev, t, rbuf[cur], dinv, rbuf[nxt], dinv ? ybuf[nxt] : nullptr, nrows, j, state,
                                 hist_dev + 2 * j, work, stream);
@@ -1522,10 +1525,10 @@ HPCLA_API int hpcla_minres_iterations_f64_i32(hpcla_halo_plan_t *plan, hpcla_com
                                               double *t, double *hist_dev, double *scal_dev, void *dot_work, void *work,
                                               int64_t first_iter, int iters, void *stream)
 {
-    return minres_iterations_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, comm, rowptr, colval_split, cols16, patterns,
-                                           nzval, nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks,
-                                           n_boundary, dinv, x, r_a, r_b, y_a, y_b, w_a, w_b, t, hist_dev, scal_dev, dot_work,
-                                           work, first_iter, iters, stream);
+    return minres_iterations_impl<int32_t>({plan, rowptr, colval_split, cols16, patterns, nzval, nrows, nnz, index_base,
+                                            interior_blocks, n_interior, boundary_blocks, n_boundary},
+                                           comm, dinv, x, r_a, r_b, y_a, y_b, w_a, w_b, t, hist_dev, scal_dev, dot_work, work,
+                                           first_iter, iters, stream);
 }
 
 HPCLA_API int hpcla_minres_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int64_t *rowptr,
@@ -1536,10 +1539,10 @@ HPCLA_API int hpcla_minres_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_com
                                               double *t, double *hist_dev, double *scal_dev, void *dot_work, void *work,
                                               int64_t first_iter, int iters, void *stream)
 {
-    return minres_iterations_impl<int64_t>(spmv_split_i64, spmv_fused_i64, plan, comm, rowptr, colval_split, nullptr, nullptr,
-                                           nzval, nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks,
-                                           n_boundary, dinv, x, r_a, r_b, y_a, y_b, w_a, w_b, t, hist_dev, scal_dev, dot_work,
-                                           work, first_iter, iters, stream);
+    return minres_iterations_impl<int64_t>({plan, rowptr, colval_split, nullptr, nullptr, nzval, nrows, nnz, index_base,
+                                            interior_blocks, n_interior, boundary_blocks, n_boundary},
+                                           comm, dinv, x, r_a, r_b, y_a, y_b, w_a, w_b, t, hist_dev, scal_dev, dot_work, work,
+                                           first_iter, iters, stream);
 }
 
 // ---- a chunk of gated GMRES(m) inner steps in ONE host call (the solver, hp.gmres) -----------------------------------
@@ -1557,16 +1560,13 @@ HPCLA_API int hpcla_minres_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_com
 // One rank: SpMV + 6 + 2 ceil(c / 8) launches per step.  N ranks: + 2 ceil(c / 8) + 1 window all-reduces and one 64-lane
 // small-step launch.  hist_dev[2 k] = g[j+1]^2, the Givens estimate of sum r_k^2 (the true one at a gate R stop and at k = 0);
 // hist_dev[2 k + 1] is not used (the layout is the other solvers' history of pairs).
-template <typename I, typename F, typename G>
-static int gmres_restart_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const I *rowptr,
-                              const I *colval, const int16_t *cols16, const hpcla_block_patterns *patterns, const double *nzval,
-                              int64_t nrows, int64_t nnz, int index_base, const int32_t *interior, int64_t n_interior,
-                              const int32_t *boundary, int64_t n_boundary, const double *dinv, const double *b, const double *x,
+template <typename I>
+static int gmres_restart_impl(const SpmvBlock<I> &a, hpcla_comm_t *comm, const double *dinv, const double *b, const double *x,
                               double *V, double *w, double *z, double *small_dev, double *hist_dev, int64_t *state, void *work,
                               int restart, int64_t iter, void *stream)
 {
-    int rc = spmv_dist_impl<I>(split_fn, fused_fn, plan, rowptr, colval, nzval, x, nrows, w, nrows, nnz, index_base, interior,
-                               n_interior, boundary, n_boundary, stream, nullptr, cols16, patterns);
+    const int64_t nrows = a.nrows;
+    int rc = spmv_dist_impl<I>(a, x, nrows, w, stream);
     if (rc) return rc;
     rc = hpcla_gmres_residual_f64(comm, b, w, nrows, iter, restart, small_dev, hist_dev + 2 * iter, state, work, stream);
     if (rc) return rc;
@@ -1589,24 +1589,21 @@ static int gmres_check(const char *who, int64_t nrows, int64_t nnz, int64_t ldv,
     return HPCLA_OK;
 }
 
-template <typename I, typename F, typename G>
-static int gmres_iterations_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const I *rowptr,
-                                 const I *colval, const int16_t *cols16, const hpcla_block_patterns *patterns,
-                                 const double *nzval, int64_t nrows, int64_t nnz, int index_base, const int32_t *interior,
-                                 int64_t n_interior, const int32_t *boundary, int64_t n_boundary, const double *dinv,
-                                 const double *b, double *x, double *V, int64_t ldv, double *w, double *z, double *small_dev,
-                                 double *hist_dev, void *work, int restart, int64_t first_iter, int iters, void *stream)
+template <typename I>
+static int gmres_iterations_impl(const SpmvBlock<I> &a, hpcla_comm_t *comm, const double *dinv, const double *b, double *x,
+                                 double *V, int64_t ldv, double *w, double *z, double *small_dev, double *hist_dev, void *work,
+                                 int restart, int64_t first_iter, int iters, void *stream)
 {
+    const int64_t nrows = a.nrows;
     if (iters < 0 || first_iter < 1) return set_error(HPCLA_ERR_INVALID, "gmres_iterations: negative count or first_iter < 1");
-    if (int rc = gmres_check("gmres_iterations", nrows, nnz, ldv, restart, dinv, b, x, V, w, z, small_dev, hist_dev, work)) return rc;
-    int64_t *state = reinterpret_cast<int64_t *>(static_cast<char *>(work) + hpcla_gmres_work_bytes(restart)) - 4;
+    if (int rc = gmres_check("gmres_iterations", nrows, a.nnz, ldv, restart, dinv, b, x, V, w, z, small_dev, hist_dev, work)) return rc;
+    int64_t *state = solver_state(work, hpcla_gmres_work_bytes(restart));
     double *h1 = small_dev + hpcla_gmres_small_offset(restart, 4), *h2 = small_dev + hpcla_gmres_small_offset(restart, 5);
     double *y = small_dev + hpcla_gmres_small_offset(restart, 7), *hn = small_dev + hpcla_gmres_small_offset(restart, 9);
     for (int64_t k = first_iter; k < first_iter + iters; ++k) {
         const int j = (int)((k - 1) % restart), c = j + 1;
         const double *in = dinv ? z : V + (int64_t)j * ldv;
-        int rc = spmv_dist_impl<I>(split_fn, fused_fn, plan, rowptr, colval, nzval, in, nrows, w, nrows, nnz, index_base, interior,
-                                   n_interior, boundary, n_boundary, stream, nullptr, cols16, patterns);
+        int rc = spmv_dist_impl<I>(a, in, nrows, w, stream);
         if (rc) return rc;
         rc = hpcla_gmres_dots_f64(comm, V, ldv, c, w, nrows, state, h1, work, stream);
         if (rc) return rc;
@@ -1625,9 +1622,7 @@ static int gmres_iterations_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan
         if (rc) return rc;
         rc = hpcla_gmres_xupdate_f64(V, ldv, c, y, dinv, x, nrows, state, stream);
         if (rc) return rc;
-        rc = gmres_restart_impl<I>(split_fn, fused_fn, plan, comm, rowptr, colval, cols16, patterns, nzval, nrows, nnz, index_base,
-                                   interior, n_interior, boundary, n_boundary, dinv, b, x, V, w, z, small_dev, hist_dev, state,
-                                   work, restart, k, stream);
+        rc = gmres_restart_impl<I>(a, comm, dinv, b, x, V, w, z, small_dev, hist_dev, state, work, restart, k, stream);
         if (rc) return rc;
     }
     return HPCLA_OK;
@@ -1642,10 +1637,10 @@ HPCLA_API int hpcla_gmres_iterations_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm
                                              double *small_dev, double *hist_dev, void *work, int restart, int64_t first_iter,
                                              int iters, void *stream)
 {
-    return gmres_iterations_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, comm, rowptr, colval_split, cols16, patterns,
-                                          nzval, nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks,
-                                          n_boundary, dinv, b, x, V, ldv, w, z, small_dev, hist_dev, work, restart, first_iter,
-                                          iters, stream);
+    return gmres_iterations_impl<int32_t>({plan, rowptr, colval_split, cols16, patterns, nzval, nrows, nnz, index_base,
+                                           interior_blocks, n_interior, boundary_blocks, n_boundary},
+                                          comm, dinv, b, x, V, ldv, w, z, small_dev, hist_dev, work, restart, first_iter, iters,
+                                          stream);
 }
 
 HPCLA_API int hpcla_gmres_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int64_t *rowptr,
@@ -1656,14 +1651,25 @@ HPCLA_API int hpcla_gmres_iterations_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm
                                              double *small_dev, double *hist_dev, void *work, int restart, int64_t first_iter,
                                              int iters, void *stream)
 {
-    return gmres_iterations_impl<int64_t>(spmv_split_i64, spmv_fused_i64, plan, comm, rowptr, colval_split, nullptr, nullptr,
-                                          nzval, nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks,
-                                          n_boundary, dinv, b, x, V, ldv, w, z, small_dev, hist_dev, work, restart, first_iter,
-                                          iters, stream);
+    return gmres_iterations_impl<int64_t>({plan, rowptr, colval_split, nullptr, nullptr, nzval, nrows, nnz, index_base,
+                                           interior_blocks, n_interior, boundary_blocks, n_boundary},
+                                          comm, dinv, b, x, V, ldv, w, z, small_dev, hist_dev, work, restart, first_iter, iters,
+                                          stream);
 }
 
 // The start of a cycle at iteration iter >= 0 on its own (the solver's setup from a given x0): w = A x, w = b - w, gate R,
 // g = (beta, 0, ...), V_0 = w / beta [z = dinv .* V_0].  hist_dev[2 iter] receives w.w at iter = 0 and at a gate R stop.
+template <typename I>
+static int gmres_restart_checked(const SpmvBlock<I> &a, hpcla_comm_t *comm, const double *dinv, const double *b, const double *x,
+                                 double *V, int64_t ldv, double *w, double *z, double *small_dev, double *hist_dev, void *work,
+                                 int restart, int64_t iter, void *stream)
+{
+    if (iter < 0) return set_error(HPCLA_ERR_INVALID, "gmres_restart: negative iteration");
+    if (int rc = gmres_check("gmres_restart", a.nrows, a.nnz, ldv, restart, dinv, b, x, V, w, z, small_dev, hist_dev, work)) return rc;
+    int64_t *state = solver_state(work, hpcla_gmres_work_bytes(restart));
+    return gmres_restart_impl<I>(a, comm, dinv, b, x, V, w, z, small_dev, hist_dev, state, work, restart, iter, stream);
+}
+
 HPCLA_API int hpcla_gmres_restart_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int32_t *rowptr,
                                           const int32_t *colval_split, const int16_t *cols16,
                                           const hpcla_block_patterns_t *patterns, const double *nzval, int64_t nrows, int64_t nnz,
@@ -1673,12 +1679,9 @@ HPCLA_API int hpcla_gmres_restart_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t 
                                           double *small_dev, double *hist_dev, void *work, int restart, int64_t iter,
                                           void *stream)
 {
-    if (iter < 0) return set_error(HPCLA_ERR_INVALID, "gmres_restart: negative iteration");
-    if (int rc = gmres_check("gmres_restart", nrows, nnz, ldv, restart, dinv, b, x, V, w, z, small_dev, hist_dev, work)) return rc;
-    int64_t *state = reinterpret_cast<int64_t *>(static_cast<char *>(work) + hpcla_gmres_work_bytes(restart)) - 4;
-    return gmres_restart_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, comm, rowptr, colval_split, cols16, patterns, nzval,
-                                       nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks, n_boundary, dinv, b,
-                                       x, V, w, z, small_dev, hist_dev, state, work, restart, iter, stream);
+    return gmres_restart_checked<int32_t>({plan, rowptr, colval_split, cols16, patterns, nzval, nrows, nnz, index_base,
+                                           interior_blocks, n_interior, boundary_blocks, n_boundary},
+                                          comm, dinv, b, x, V, ldv, w, z, small_dev, hist_dev, work, restart, iter, stream);
 }
 
 HPCLA_API int hpcla_gmres_restart_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int64_t *rowptr,
@@ -1689,12 +1692,9 @@ HPCLA_API int hpcla_gmres_restart_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t 
                                           double *small_dev, double *hist_dev, void *work, int restart, int64_t iter,
                                           void *stream)
 {
-    if (iter < 0) return set_error(HPCLA_ERR_INVALID, "gmres_restart: negative iteration");
-    if (int rc = gmres_check("gmres_restart", nrows, nnz, ldv, restart, dinv, b, x, V, w, z, small_dev, hist_dev, work)) return rc;
-    int64_t *state = reinterpret_cast<int64_t *>(static_cast<char *>(work) + hpcla_gmres_work_bytes(restart)) - 4;
-    return gmres_restart_impl<int64_t>(spmv_split_i64, spmv_fused_i64, plan, comm, rowptr, colval_split, nullptr, nullptr, nzval,
-                                       nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks, n_boundary, dinv, b,
-                                       x, V, w, z, small_dev, hist_dev, state, work, restart, iter, stream);
+    return gmres_restart_checked<int64_t>({plan, rowptr, colval_split, nullptr, nullptr, nzval, nrows, nnz, index_base,
+                                           interior_blocks, n_interior, boundary_blocks, n_boundary},
+                                          comm, dinv, b, x, V, ldv, w, z, small_dev, hist_dev, work, restart, iter, stream);
 }
 
 // ---- columns of a thick-restart Lanczos cycle in ONE host call (the eigensolver, hp.eigsh) ---------------------------------
@@ -1707,14 +1707,12 @@ HPCLA_API int hpcla_gmres_restart_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t 
 //   5. w = w - V h2, nn = w.w       hpcla_eigsh_update_f64: one all-reduce [nn], the Lanczos small step, gates N and I
 //   6. V_{j+1} = w / hn             hpcla_gmres_next_f64, also at c == ncv: the basis has ncv + 1 columns
 // One rank: SpMV + 6 + 2 ceil(c / 8) launches per step, no read-back.  The host reads the small buffer once per cycle.
-template <typename I, typename F, typename G>
-static int eigsh_steps_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const I *rowptr, const I *colval,
-                            const int16_t *cols16, const hpcla_block_patterns *patterns, const double *nzval, int64_t nrows,
-                            int64_t nnz, int index_base, const int32_t *interior, int64_t n_interior, const int32_t *boundary,
-                            int64_t n_boundary, double *V, int64_t ldv, double *w, double *small_dev, void *work, int ncv,
-                            int first_col, int count, int64_t first_iter, void *stream)
+template <typename I>
+static int eigsh_steps_impl(const SpmvBlock<I> &a, hpcla_comm_t *comm, double *V, int64_t ldv, double *w, double *small_dev,
+                            void *work, int ncv, int first_col, int count, int64_t first_iter, void *stream)
 {
-    if (nrows < 0 || nnz < 0) return set_error(HPCLA_ERR_INVALID, "eigsh_steps: negative size");
+    const int64_t nrows = a.nrows;
+    if (nrows < 0 || a.nnz < 0) return set_error(HPCLA_ERR_INVALID, "eigsh_steps: negative size");
     if (ncv < 1 || ncv > 64) return set_error(HPCLA_ERR_INVALID, "eigsh_steps: ncv must be in 1..64");
     if (first_col < 0 || count < 0 || first_col + count > ncv || first_iter < 1)
         return set_error(HPCLA_ERR_INVALID, "eigsh_steps: columns outside 0..ncv-1 or first_iter < 1");
@@ -1723,14 +1721,13 @@ static int eigsh_steps_impl(F split_fn, G fused_fn, hpcla_halo_plan_t *plan, hpc
     if (nrows > 0 && (!V || !w)) return set_error(HPCLA_ERR_INVALID, "eigsh_steps: null vector");
     if ((reinterpret_cast<uintptr_t>(V) | reinterpret_cast<uintptr_t>(w)) & 15)
         return set_error(HPCLA_ERR_INVALID, "eigsh_steps: vectors must be 16-byte aligned");
-    int64_t *state = reinterpret_cast<int64_t *>(static_cast<char *>(work) + hpcla_gmres_work_bytes(ncv)) - 4;
+    int64_t *state = solver_state(work, hpcla_gmres_work_bytes(ncv));
     double *h1 = small_dev + hpcla_eigsh_small_offset(ncv, 2), *h2 = small_dev + hpcla_eigsh_small_offset(ncv, 3);
     double *hn = small_dev + hpcla_eigsh_small_offset(ncv, 5);
     for (int j = first_col; j < first_col + count; ++j) {
         const int c = j + 1;
         const int64_t k = first_iter + (j - first_col);
-        int rc = spmv_dist_impl<I>(split_fn, fused_fn, plan, rowptr, colval, nzval, V + (int64_t)j * ldv, nrows, w, nrows, nnz,
-                                   index_base, interior, n_interior, boundary, n_boundary, stream, nullptr, cols16, patterns);
+        int rc = spmv_dist_impl<I>(a, V + (int64_t)j * ldv, nrows, w, stream);
         if (rc) return rc;
         rc = hpcla_gmres_dots_f64(comm, V, ldv, c, w, nrows, state, h1, work, stream);
         if (rc) return rc;
@@ -1753,9 +1750,9 @@ HPCLA_API int hpcla_eigsh_steps_f64_i32(hpcla_halo_plan_t *plan, hpcla_comm_t *c
                                         int64_t n_boundary, double *V, int64_t ldv, double *w, double *small_dev, void *work,
                                         int ncv, int first_col, int count, int64_t first_iter, void *stream)
 {
-    return eigsh_steps_impl<int32_t>(spmv_split_i32, spmv_fused_i32, plan, comm, rowptr, colval_split, cols16, patterns, nzval,
-                                     nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks, n_boundary, V, ldv, w,
-                                     small_dev, work, ncv, first_col, count, first_iter, stream);
+    return eigsh_steps_impl<int32_t>({plan, rowptr, colval_split, cols16, patterns, nzval, nrows, nnz, index_base, interior_blocks,
+                                      n_interior, boundary_blocks, n_boundary},
+                                     comm, V, ldv, w, small_dev, work, ncv, first_col, count, first_iter, stream);
 }
 
 HPCLA_API int hpcla_eigsh_steps_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *comm, const int64_t *rowptr,
@@ -1765,9 +1762,9 @@ HPCLA_API int hpcla_eigsh_steps_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *c
                                         double *small_dev, void *work, int ncv, int first_col, int count, int64_t first_iter,
                                         void *stream)
 {
-    return eigsh_steps_impl<int64_t>(spmv_split_i64, spmv_fused_i64, plan, comm, rowptr, colval_split, nullptr, nullptr, nzval,
-                                     nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks, n_boundary, V, ldv, w,
-                                     small_dev, work, ncv, first_col, count, first_iter, stream);
+    return eigsh_steps_impl<int64_t>({plan, rowptr, colval_split, nullptr, nullptr, nzval, nrows, nnz, index_base, interior_blocks,
+                                      n_interior, boundary_blocks, n_boundary},
+                                     comm, V, ldv, w, small_dev, work, ncv, first_col, count, first_iter, stream);
 }
 
 // ---- columns of a thick-restart Golub-Kahan cycle in ONE host call (the truncated SVD, hp.svds) ------------------------------
@@ -1785,18 +1782,13 @@ HPCLA_API int hpcla_eigsh_steps_f64_i64(hpcla_halo_plan_t *plan, hpcla_comm_t *c
 //   8. V_{j+1} = v / beta_j         hpcla_gmres_next_f64, also at j + 1 == ncv: the right basis has ncv + 1 columns
 // One rank: 2 SpMV + 12 + 2 ceil(j / 8) + 2 ceil((j + 1) / 8) launches per step (11 at j = 0), no read-back.  The host reads the small buffer
 // once per cycle.
-template <typename I, typename F, typename G>
-static int svds_steps_impl(F split_fn, G fused_fn, hpcla_comm_t *comm, hpcla_halo_plan_t *plan, const I *rowptr, const I *colval,
-                           const int16_t *cols16, const hpcla_block_patterns *patterns, const double *nzval, int64_t nrows,
-                           int64_t nnz, int index_base, const int32_t *interior, int64_t n_interior, const int32_t *boundary,
-                           int64_t n_boundary, hpcla_halo_plan_t *plan_t, const I *rowptr_t, const I *colval_t,
-                           const int16_t *cols16_t, const hpcla_block_patterns *patterns_t, const double *nzval_t,
-                           int64_t nrows_t, int64_t nnz_t, int index_base_t, const int32_t *interior_t, int64_t n_interior_t,
-                           const int32_t *boundary_t, int64_t n_boundary_t, double *U, int64_t ldu, double *V, int64_t ldv,
-                           double *u, double *v, double *small_dev, void *work, int ncv, int first_col, int count,
+template <typename I>
+static int svds_steps_impl(hpcla_comm_t *comm, const SpmvBlock<I> &a, const SpmvBlock<I> &at, double *U, int64_t ldu, double *V,
+                           int64_t ldv, double *u, double *v, double *small_dev, void *work, int ncv, int first_col, int count,
                            int64_t first_iter, void *stream)
 {
-    if (nrows < 0 || nnz < 0 || nrows_t < 0 || nnz_t < 0) return set_error(HPCLA_ERR_INVALID, "svds_steps: negative size");
+    const int64_t nrows = a.nrows, nrows_t = at.nrows;
+    if (nrows < 0 || a.nnz < 0 || nrows_t < 0 || at.nnz < 0) return set_error(HPCLA_ERR_INVALID, "svds_steps: negative size");
     if (ncv < 1 || ncv > 64) return set_error(HPCLA_ERR_INVALID, "svds_steps: ncv must be in 1..64");
     if (first_col < 0 || count < 0 || first_col + count > ncv || first_iter < 1)
         return set_error(HPCLA_ERR_INVALID, "svds_steps: columns outside 0..ncv-1 or first_iter < 1");
@@ -1807,15 +1799,14 @@ static int svds_steps_impl(F split_fn, G fused_fn, hpcla_comm_t *comm, hpcla_hal
     if ((reinterpret_cast<uintptr_t>(U) | reinterpret_cast<uintptr_t>(V) | reinterpret_cast<uintptr_t>(u) |
          reinterpret_cast<uintptr_t>(v)) & 15)
         return set_error(HPCLA_ERR_INVALID, "svds_steps: vectors must be 16-byte aligned");
-    int64_t *state = reinterpret_cast<int64_t *>(static_cast<char *>(work) + hpcla_gmres_work_bytes(ncv)) - 4;
-    double *g1 = small_dev + hpcla_svds_small_offset(ncv, 2), *g2 = small_dev + hpcla_svds_small_offset(ncv, 3);
+    int64_t *state = solver_state(work, hpcla_gmres_work_bytes(ncv));
+    double *g1 =small_dev + hpcla_svds_small_offset(ncv, 2), *g2 = small_dev + hpcla_svds_small_offset(ncv, 3);
     double *h1 = small_dev + hpcla_svds_small_offset(ncv, 4), *h2 = small_dev + hpcla_svds_small_offset(ncv, 5);
     double *dv = small_dev + hpcla_svds_small_offset(ncv, 8);
     for (int j = first_col; j < first_col + count; ++j) {
         const int64_t k = first_iter + (j - first_col);
         double *Uj = U + (int64_t)j * ldu;
-        int rc = spmv_dist_impl<I>(split_fn, fused_fn, plan, rowptr, colval, nzval, V + (int64_t)j * ldv, nrows_t, u, nrows, nnz,
-                                   index_base, interior, n_interior, boundary, n_boundary, stream, nullptr, cols16, patterns);
+        int rc = spmv_dist_impl<I>(a, V + (int64_t)j * ldv, nrows_t, u, stream);
         if (rc) return rc;
         if (j > 0) {
             rc = hpcla_gmres_dots_f64(comm, U, ldu, j, u, nrows, state, g1, work, stream);
@@ -1829,9 +1820,7 @@ static int svds_steps_impl(F split_fn, G fused_fn, hpcla_comm_t *comm, hpcla_hal
         if (rc) return rc;
         rc = hpcla_gmres_next_f64(u, dv, nullptr, Uj, nullptr, nrows, state, stream);
         if (rc) return rc;
-        rc = spmv_dist_impl<I>(split_fn, fused_fn, plan_t, rowptr_t, colval_t, nzval_t, Uj, nrows, v, nrows_t, nnz_t,
-                               index_base_t, interior_t, n_interior_t, boundary_t, n_boundary_t, stream, nullptr, cols16_t,
-                               patterns_t);
+        rc = spmv_dist_impl<I>(at, Uj, nrows, v, stream);
         if (rc) return rc;
         rc = hpcla_gmres_dots_f64(comm, V, ldv, j + 1, v, nrows_t, state, h1, work, stream);
         if (rc) return rc;
@@ -1859,11 +1848,12 @@ HPCLA_API int hpcla_svds_steps_f64_i32(hpcla_comm_t *comm, hpcla_halo_plan_t *pl
                                        int64_t ldv, double *u, double *v, double *small_dev, void *work, int ncv, int first_col,
                                        int count, int64_t first_iter, void *stream)
 {
-    return svds_steps_impl<int32_t>(spmv_split_i32, spmv_fused_i32, comm, plan, rowptr, colval_split, cols16, patterns, nzval,
-                                    nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks, n_boundary, plan_t,
-                                    rowptr_t, colval_split_t, cols16_t, patterns_t, nzval_t, nrows_t, nnz_t, index_base_t,
-                                    interior_blocks_t, n_interior_t, boundary_blocks_t, n_boundary_t, U, ldu, V, ldv, u, v,
-                                    small_dev, work, ncv, first_col, count, first_iter, stream);
+    return svds_steps_impl<int32_t>(comm,
+                                    {plan, rowptr, colval_split, cols16, patterns, nzval, nrows, nnz, index_base, interior_blocks,
+                                     n_interior, boundary_blocks, n_boundary},
+                                    {plan_t, rowptr_t, colval_split_t, cols16_t, patterns_t, nzval_t, nrows_t, nnz_t, index_base_t,
+                                     interior_blocks_t, n_interior_t, boundary_blocks_t, n_boundary_t},
+                                    U, ldu, V, ldv, u, v, small_dev, work, ncv, first_col, count, first_iter, stream);
 }
 
 HPCLA_API int hpcla_svds_steps_f64_i64(hpcla_comm_t *comm, hpcla_halo_plan_t *plan, const int64_t *rowptr,
@@ -1876,9 +1866,10 @@ HPCLA_API int hpcla_svds_steps_f64_i64(hpcla_comm_t *comm, hpcla_halo_plan_t *pl
                                        int64_t ldu, double *V, int64_t ldv, double *u, double *v, double *small_dev, void *work,
                                        int ncv, int first_col, int count, int64_t first_iter, void *stream)
 {
-    return svds_steps_impl<int64_t>(spmv_split_i64, spmv_fused_i64, comm, plan, rowptr, colval_split, nullptr, nullptr, nzval,
-                                    nrows, nnz, index_base, interior_blocks, n_interior, boundary_blocks, n_boundary, plan_t,
-                                    rowptr_t, colval_split_t, nullptr, nullptr, nzval_t, nrows_t, nnz_t, index_base_t,
-                                    interior_blocks_t, n_interior_t, boundary_blocks_t, n_boundary_t, U, ldu, V, ldv, u, v,
-                                    small_dev, work, ncv, first_col, count, first_iter, stream);
+    return svds_steps_impl<int64_t>(comm,
+                                    {plan, rowptr, colval_split, nullptr, nullptr, nzval, nrows, nnz, index_base, interior_blocks,
+                                     n_interior, boundary_blocks, n_boundary},
+                                    {plan_t, rowptr_t, colval_split_t, nullptr, nullptr, nzval_t, nrows_t, nnz_t, index_base_t,
+                                     interior_blocks_t, n_interior_t, boundary_blocks_t, n_boundary_t},
+                                    U, ldu, V, ldv, u, v, small_dev, work, ncv, first_col, count, first_iter, stream);
 }

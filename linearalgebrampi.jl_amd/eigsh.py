@@ -239,9 +239,8 @@ def eigsh(A, k: int = 6, which: str = "LA", ncv: Optional[int] = None, tol: floa
     comm, rank0 = A.backend.rccl, comm_rank(A.backend.comm) == 0
     n_loc = ws.w.local_length
     sfx = "i64" if plan.is_i64 else "i32"
-    narrow = () if plan.is_i64 else (dptr(plan.cols16), plan.patterns)
-    spmv = (plan.halo if plan.has_halo else None, comm, dptr(plan.rowptr_of(A)), dptr(plan.colval_split), *narrow,
-            dptr(A.nzval), A.nrows_local, A.nnz, 0, dptr(plan.interior), plan.n_interior, dptr(plan.boundary), plan.n_boundary)
+    blk = plan.matrix_block(A)
+    spmv = (blk[0], comm, *blk[1:])
 
     # -- start: V_0 = v0 / sqrt(v0.v0) ---------------------------------------------------------------------------------------------
     ws.small.zero_()

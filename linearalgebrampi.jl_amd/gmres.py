@@ -133,9 +133,8 @@ def gmres(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, a
         ws.with_preconditioner()
     n, stream = ws.x.local_length, current_stream_ptr()
     sfx = "i64" if plan.is_i64 else "i32"
-    narrow = () if plan.is_i64 else (dptr(plan.cols16), plan.patterns)
-    spmv = (plan.halo if plan.has_halo else None, A.backend.rccl, dptr(plan.rowptr_of(A)), dptr(plan.colval_split), *narrow,
-            dptr(A.nzval), A.nrows_local, A.nnz, 0, dptr(plan.interior), plan.n_interior, dptr(plan.boundary), plan.n_boundary)
+    blk = plan.matrix_block(A)
+    spmv = (blk[0], A.backend.rccl, *blk[1:])
     dv, zv = (dptr(dinv.v), dptr(ws.z.v)) if dinv is not None else (None, None)
 
     def solve():                                                 # the history may have grown since the last call

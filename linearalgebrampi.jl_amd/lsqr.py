@@ -86,13 +86,6 @@ class LSQRWorkspace(_PairHistory):
                 and self.x.v.device == b.v.device)
 
 
-def _matrix_block(A, plan):
-    """The plan and CSR arguments of one matrix, as the iterations entries take them (twice)."""
-    narrow = () if plan.is_i64 else (dptr(plan.cols16), plan.patterns)
-    return (plan.halo if plan.has_halo else None, dptr(plan.rowptr_of(A)), dptr(plan.colval_split), *narrow, dptr(A.nzval),
-            A.nrows_local, A.nnz, 0, dptr(plan.interior), plan.n_interior, dptr(plan.boundary), plan.n_boundary)
-
-
 def lsqr(A, b: HPCVector, x0: Optional[HPCVector] = None, damp: float = 0.0, rtol: float = 1e-8, atol: float = 0.0,
          ntol: float = 1e-8, maxiter: Optional[int] = None, check_every: int = 8,
          workspace: Optional[LSQRWorkspace] = None) -> Tuple[HPCVector, LSQRInfo]:
@@ -194,7 +187,7 @@ def lsqr(A, b: HPCVector, x0: Optional[HPCVector] = None, damp: float = 0.0, rto
 
     # -- chunks of check_every iterations; one 16-byte read-back each -------------------------------------------------------
     sfx = "i64" if plan.is_i64 else "i32"
-    blocks = _matrix_block(A, plan) + _matrix_block(At, plan_t)
+    blocks = plan.matrix_block(A) + plan_t.matrix_block(At)
 
     def enqueue(first_iter, count):
         _capi.call(f"hpcla_lsqr_iterations_f64_{sfx}", comm, *blocks, dptr(ws.x.v), dptr(ws.uh.v), dptr(ws.vh.v), dptr(ws.w.v),

@@ -120,9 +120,7 @@ def minres(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, 
     dinv = _minres_dinv(A, b, M)
     if dinv is not None and ws.y is None:
         ws.y = (b.similar(), b.similar())
-    if getattr(plan, "_dot_work", None) is None:
-        nbytes = _capi.load().hpcla_spmv_dot_work_bytes(A.nrows_local)
-        plan._dot_work = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=ws.x.v.device)
+    dot_work = plan.dot_work(A)
     comm, n_loc = A.backend.rccl, ws.x.local_length
     P = lambda v: dptr(v.v) if v is not None else None
 
@@ -169,16 +167,13 @@ def minres(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, 
 
     # -- chunks of check_every iterations; one 16-byte read-back each ---------------------------------------------------------
     sfx = "i64" if plan.is_i64 else "i32"
-    narrow = () if plan.is_i64 else (dptr(plan.cols16), plan.patterns)
+    blk = plan.matrix_block(A)
     ys = ws.y if dinv is not None else (None, None)
 
     def enqueue(first_iter, count):
-        _capi.call(f"hpcla_minres_iterations_f64_{sfx}", plan.halo if plan.has_halo else None, comm,
-                   dptr(plan.rowptr_of(A)), dptr(plan.colval_split), *narrow, dptr(A.nzval), A.nrows_local, A.nnz, 0,
-                   dptr(plan.interior), plan.n_interior, dptr(plan.boundary), plan.n_boundary, P(dinv), dptr(ws.x.v),
+        _capi.call(f"hpcla_minres_iterations_f64_{sfx}", blk[0], comm, *blk[1:], P(dinv), dptr(ws.x.v),
                    dptr(ws.r[0].v), dptr(ws.r[1].v), P(ys[0]), P(ys[1]), dptr(ws.w[0].v), dptr(ws.w[1].v), dptr(ws.t.v),
-                   dptr(ws.hist), dptr(ws.scal), dptr(plan._dot_work), dptr(ws.work), first_iter, count,
-                   current_stream_ptr())
+                   dptr(ws.hist), dptr(ws.scal), dptr(dot_work), dptr(ws.work), first_iter, count, current_stream_ptr())
 
     iterations, status = _run_chunks(ws, A.backend, maxiter, check_every, enqueue)
     h = _residual_norms(ws, b.backend, iterations)

@@ -323,6 +323,7 @@ class VectorPlan:
         # ghost buffer, so that the pointer is a constant of the plan
         self.is_f32 = A.T == np.dtype(np.float32)
         self._stage32 = None
+        self._dot_work = None
         if self.has_halo:
             self.halo = create_halo_plan(backend, h.send_rank_ids, h.send_indices, Tk, h.recv_rank_ids,
                                          [len(p) for p in h.recv_perm], 1, double_buffer=not self.is_f32)
@@ -422,6 +423,22 @@ class VectorPlan:
         """The ``rowptr`` the kernels of this plan read for matrix A: A's own device array, or -- narrowed plan -- the
         plan's Int32 copy (equal contents for every matrix that shares the plan: the structural hash covers rowptr)."""
         return self._rowptr32 if self.narrowed else A.rowptr_target
+
+    def matrix_block(self, A: "HPCSparseMatrix", narrow: bool = True) -> tuple:
+        """Matrix A as this plan multiplies it: the argument run of the ``*_iterations_*`` / ``*_steps_*`` entry points
+        (csrc/comm.hip builds one SpmvBlock from it).  The halo plan comes first -- an entry that takes ``comm`` second is
+        passed ``blk[0], comm, *blk[1:]``; the 16-bit columns and the pattern table are present on Int32 plans only, and not
+        at all with ``narrow=False`` (entries without the pair: hpcla_cg_iterations_*)."""
+        pair = (dptr(self.cols16), self.patterns) if narrow and not self.is_i64 else ()
+        return (self.halo if self.has_halo else None, dptr(self.rowptr_of(A)), dptr(self.colval_split), *pair, dptr(A.nzval),
+                A.nrows_local, A.nnz, 0, dptr(self.interior), self.n_interior, dptr(self.boundary), self.n_boundary)
+
+    def dot_work(self, A: "HPCSparseMatrix"):
+        """Scratch of the fused SpMV + dot over this plan (hpcla_spmv_dot_work_bytes), allocated at first use."""
+        if self._dot_work is None:
+            nbytes = _capi.load().hpcla_spmv_dot_work_bytes(A.nrows_local)
+            self._dot_work = _torch().empty(nbytes // 8 + 1, dtype=_torch().float64, device=self.backend.torch_device)
+        return self._dot_work
 
     def stage_f32(self, n: int):
         """Staging vector of a Float32 exchange (hpcla_halo_begin_f32): n doubles, written at the send positions only."""
@@ -916,11 +933,7 @@ def mul_dot_(y: HPCVector, A: HPCSparseMatrix, x: HPCVector, out) -> HPCVector:
     plan = get_vector_plan(A, x)
     if y.structural_hash != plan.result_partition_hash or x.structural_hash != plan.result_partition_hash:
         raise ValueError("mul_dot_: x and y must have A's row partition")
-    torch = _torch()
-    work = getattr(plan, "_dot_work", None)
-    if work is None:
-        nbytes = _capi.load().hpcla_spmv_dot_work_bytes(A.nrows_local)
-        work = plan._dot_work = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=x.v.device)
+    work = plan.dot_work(A)
     pk = A._packed_for(plan)
     if pk is not None:
         _capi.call("hpcla_spmv_dist_packed_f64_i32", plan.halo if plan.has_halo else None, A.backend.rccl,

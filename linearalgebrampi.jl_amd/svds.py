@@ -55,7 +55,6 @@ import numpy as np
 from . import _capi
 from .backends import comm_bcast_bytes, comm_rank, comm_size
 from .eigsh import kept_count
-from .lsqr import _matrix_block
 from .partition import compute_partition_hash, uniform_partition
 from .sparse import get_vector_plan
 from .transpose import TransposedHPCSparseMatrix
@@ -252,7 +251,7 @@ def svds(A, k: int = 6, which: str = "LM", ncv: Optional[int] = None, tol: float
     comm, rank0 = backend.rccl, comm_rank(backend.comm) == 0
     m_loc, n_loc = ws.u.local_length, ws.v.local_length
     sfx = "i64" if plan.is_i64 else "i32"
-    blocks = _matrix_block(A, plan) + _matrix_block(At, plan_t)
+    blocks = plan.matrix_block(A) + plan_t.matrix_block(At)
 
     # -- start: V_0 = v0 / sqrt(v0.v0) ---------------------------------------------------------------------------------------------
     ws.small.zero_()
