@@ -1031,6 +1031,64 @@ int hpcla_pcg_fsai_iterations_f64_i64(
     int64_t nnz_t, int index_base_t, const int32_t *interior_blocks_t, int64_t n_interior_t, const int32_t *boundary_blocks_t,
     int64_t n_boundary_t, double *x, double *r, double *p, double *Ap, double *u, double *z, double *hist_dev, double *pAp_dev,
     void *dot_work, void *pcg_work, int64_t first_iter, int iters, void *stream);
+/* ---- smoothed-aggregation multigrid (hp.amg, csrc/amg.hip): the setup kernels of a level and the two fused smoother updates
+ * of the cycle (no reference counterpart).  The setup's products, its transpose and the cycle's SpMVs are the entries above.
+ * Rows and columns of A are partitioned alike (n_own == nrows < 2^31): a split column < n_own is the local row it names, columns
+ * >= n_own are ghosts, which the weights read and the strength graph leaves out (aggregates never cross ranks).
+ *   amg_work_bytes     device bytes of `work` for the scans.   amg_round_blocks  entries of block_undecided_dev.
+ *   amg_weights        diag_dev[i] = a_ii (+0.0 where none is stored), ratio_dev[i] = sum_j |a_ij| / a_ii over the whole row;
+ *                      info_dev[0] = all ones, or the smallest local row with !(a_ii > 0) (NaN included).
+ *   amg_smoother       s = w ./ diag.
+ *   amg_strength_count / _fill   the graph of entries c != i, c < n_own, a_ic != 0, |a_ic| >= theta sqrt(a_ii a_cc), theta in
+ *                      [0, 1): s_rowptr_dev (nrows + 1, 0-based), info_dev[0] = its entries; then local columns, row order kept.
+ *   amg_mis_init       key = (h(row_start + i) << 31) | i with h the 31-bit mix of csrc/amg.hip; state = key.
+ *   amg_mis_round      one round of the distance-2 independent set, three launches: m1, m2 (neighbour maxima of the state: key
+ *                      undecided, 2^62 root, -1 out), state_out, and per workgroup the rows still undecided.  No atomics.
+ *   amg_join           owner_b_dev[i] = the local row of i's root (pass 1 into owner_a_dev: roots and their neighbours; pass 2:
+ *                      the rest), rootid_dev = the exclusive scan of the root flags; info_dev[0] = all ones or a row left
+ *                      without a root (cannot happen for a maximal set), info_dev[1] = the number of roots.
+ *   amg_aggregate_ids  agg_dev[i] = offset + rootid[owner[i]]: global aggregate ids.
+ *   amg_prolongator    p_ic = [c == agg(i)] - s_i * (A T)_ic on the CSR of A T (compressed local columns, their global ids).
+ *   amg_presmooth      x = s .* b.      amg_postsmooth  x += s .* (b - t).  16-byte aligned vectors.
+ * All only enqueue. */
+int64_t hpcla_amg_work_bytes(int64_t nrows);
+int64_t hpcla_amg_round_blocks(int64_t nrows);
+int hpcla_amg_weights_f64_i32(const int32_t *rowptr, const int32_t *colval_split, const double *nzval, int64_t nrows,
+                              int64_t n_own, int index_base, double *diag_dev, double *ratio_dev, int64_t *info_dev,
+                              void *stream);
+int hpcla_amg_weights_f64_i64(const int64_t *rowptr, const int64_t *colval_split, const double *nzval, int64_t nrows,
+                              int64_t n_own, int index_base, double *diag_dev, double *ratio_dev, int64_t *info_dev,
+                              void *stream);
+int hpcla_amg_smoother_f64(double w, const double *diag_dev, double *s_dev, int64_t n, void *stream);
+int hpcla_amg_strength_count_f64_i32(const int32_t *rowptr, const int32_t *colval_split, const double *nzval,
+                                     const double *diag_dev, int64_t nrows, int64_t n_own, int index_base, double theta,
+                                     int64_t *s_rowptr_dev, int64_t *info_dev, void *work, void *stream);
+int hpcla_amg_strength_count_f64_i64(const int64_t *rowptr, const int64_t *colval_split, const double *nzval,
+                                     const double *diag_dev, int64_t nrows, int64_t n_own, int index_base, double theta,
+                                     int64_t *s_rowptr_dev, int64_t *info_dev, void *work, void *stream);
+int hpcla_amg_strength_fill_f64_i32(const int32_t *rowptr, const int32_t *colval_split, const double *nzval,
+                                    const double *diag_dev, int64_t nrows, int64_t n_own, int index_base, double theta,
+                                    const int64_t *s_rowptr_dev, int32_t *s_cols_dev, void *stream);
+int hpcla_amg_strength_fill_f64_i64(const int64_t *rowptr, const int64_t *colval_split, const double *nzval,
+                                    const double *diag_dev, int64_t nrows, int64_t n_own, int index_base, double theta,
+                                    const int64_t *s_rowptr_dev, int32_t *s_cols_dev, void *stream);
+int hpcla_amg_mis_init(int64_t nrows, int64_t row_start, int64_t *key_dev, int64_t *state_dev, void *stream);
+int hpcla_amg_mis_round(const int64_t *s_rowptr_dev, const int32_t *s_cols_dev, int64_t nrows, const int64_t *key_dev,
+                        const int64_t *state_in_dev, int64_t *m1_dev, int64_t *m2_dev, int64_t *state_out_dev,
+                        int64_t *block_undecided_dev, void *stream);
+int hpcla_amg_join(const int64_t *s_rowptr_dev, const int32_t *s_cols_dev, int64_t nrows, const int64_t *key_dev,
+                   const int64_t *state_dev, int32_t *owner_a_dev, int32_t *owner_b_dev, int64_t *rootid_dev, int64_t *info_dev,
+                   void *work, void *stream);
+int hpcla_amg_aggregate_ids(const int32_t *owner_dev, const int64_t *rootid_dev, int64_t nrows, int64_t offset, int64_t *agg_dev,
+                            void *stream);
+int hpcla_amg_prolongator_f64_i32(const int32_t *at_rowptr, const int32_t *at_colval, const int64_t *at_col_indices_dev,
+                                  const double *at_nzval, const int64_t *agg_dev, const double *s_dev, int64_t nrows,
+                                  int index_base, double *p_nzval, void *stream);
+int hpcla_amg_prolongator_f64_i64(const int64_t *at_rowptr, const int64_t *at_colval, const int64_t *at_col_indices_dev,
+                                  const double *at_nzval, const int64_t *agg_dev, const double *s_dev, int64_t nrows,
+                                  int index_base, double *p_nzval, void *stream);
+int hpcla_amg_presmooth_f64(const double *s_dev, const double *b, double *x, int64_t n, void *stream);
+int hpcla_amg_postsmooth_f64(const double *s_dev, const double *b, const double *t, double *x, int64_t n, void *stream);
 /* ---- BiCGStab for nonsymmetric A: gated steps of right-preconditioned BiCGStab, K = identity or dinv .* (no reference
  * counterpart: the reference solves a general A \ b through MUMPS on the host; a caller of its operators composes the
  * method from A*p, src/sparse.jl:2096-2128, dot, src/vectors.jl:798-812, and the broadcasts, src/vectors.jl:1203-1226).

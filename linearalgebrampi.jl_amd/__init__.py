@@ -13,6 +13,9 @@ Layout
   cg.py              fixed-iteration CG harness; cg(): the converging solver (Jacobi or FSAI preconditioner, device-side stop)
   fsai.py            fsai(): the factorised sparse approximate inverse preconditioner G' G of an SPD A for cg(M=...): one small dense
                      Cholesky per row on the device (csrc/fsai.hip), applied as two SpMVs; rank-local couplings, <= 32 entries per row
+  amg.py             amg(): the smoothed-aggregation multigrid preconditioner of an SPD A for cg(M=...): aggregation by a distance-2
+                     independent set on the device (csrc/amg.hip), the hierarchy through spgemm and transpose, a symmetric
+                     V(1,1) cycle on ordinary SpMVs; aggregates never cross ranks
   bicgstab.py        bicgstab(): BiCGStab for nonsymmetric A, the same device-side stop (csrc/vecops.hip, bicg_* kernels)
   gmres.py           gmres(): restarted GMRES(m), fused twice-applied Gram-Schmidt, the same device-side stop (gmres_* kernels)
   lsqr.py            lsqr(): least squares for rectangular A on A and its materialised transpose, damped form, two stop rules
@@ -54,6 +57,7 @@ from .spmm_plans import clear_spmm_cache, spmm, spmm_block_order_of, spmm_exchan
 from .matmat import clear_matrix_plan_cache, get_matrix_plan, spgemm
 from .cg import CGGraphPair, CGInfo, CGWorkspace, PCGWorkspace, cg, cg_fixed_iterations, cg_iterate, cg_setup
 from .fsai import FSAI, fsai
+from .amg import AMG, AMGLevel, AMGWorkspace, amg
 from .bicgstab import BiCGStabWorkspace, bicgstab
 from .gmres import GMRESWorkspace, gmres
 from .lsqr import LSQRInfo, LSQRWorkspace, lsqr

@@ -173,6 +173,25 @@ _SIGNATURES = {
                                           _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
                                           _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
+    # smoothed-aggregation multigrid (hp.amg, csrc/amg.hip): a level's weights, strength graph, aggregation and prolongator
+    # values; the cycle's two fused smoother updates
+    "hpcla_amg_work_bytes": [_i64],
+    "hpcla_amg_round_blocks": [_i64],
+    "hpcla_amg_weights_f64_i32": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp],
+    "hpcla_amg_weights_f64_i64": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp],
+    "hpcla_amg_smoother_f64": [_f64, _vp, _vp, _i64, _vp],
+    "hpcla_amg_strength_count_f64_i32": [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _f64, _vp, _vp, _vp, _vp],
+    "hpcla_amg_strength_count_f64_i64": [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _f64, _vp, _vp, _vp, _vp],
+    "hpcla_amg_strength_fill_f64_i32": [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _f64, _vp, _vp, _vp],
+    "hpcla_amg_strength_fill_f64_i64": [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _f64, _vp, _vp, _vp],
+    "hpcla_amg_mis_init": [_i64, _i64, _vp, _vp, _vp],
+    "hpcla_amg_mis_round": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "hpcla_amg_join": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "hpcla_amg_aggregate_ids": [_vp, _vp, _i64, _i64, _vp, _vp],
+    "hpcla_amg_prolongator_f64_i32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp],
+    "hpcla_amg_prolongator_f64_i64": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp],
+    "hpcla_amg_presmooth_f64": [_vp, _vp, _vp, _i64, _vp],
+    "hpcla_amg_postsmooth_f64": [_vp, _vp, _vp, _vp, _i64, _vp],
     # BiCGStab for nonsymmetric A (hp.bicgstab): the gated steps and the chunk of iterations
     "hpcla_bicgstab_work_bytes": [],
     "hpcla_bicg_dot_f64": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
@@ -364,6 +383,8 @@ _RESTYPES = {
     "hpcla_cols16_padded_len": _i64,
     "hpcla_pcg_work_bytes": _i64,
     "hpcla_fsai_work_bytes": _i64,
+    "hpcla_amg_work_bytes": _i64,
+    "hpcla_amg_round_blocks": _i64,
     "hpcla_bicgstab_work_bytes": _i64,
     "hpcla_lsqr_work_bytes": _i64,
     "hpcla_minres_work_bytes": _i64,

@@ -1,0 +1,370 @@
+"""amg(): the smoothed-aggregation algebraic multigrid preconditioner of a symmetric positive definite ``A`` for ``hp.cg``.
+
+Level setup (csrc/amg.hip for what the library's products do not cover), repeated on the current level's ``A``:
+  weight      rho = max_i sum_j |a_ij| / a_ii over whole rows (a max across ranks), w = 4 / (3 rho), s = w ./ diag(A)
+  strength    (i, j) kept when j != i, j owned by this rank, a_ij != 0 and |a_ij| >= theta sqrt(a_ii a_jj): device CSR
+  roots       a distance-2 maximal independent set over keyed rows, three launches a round, the host reads the rows left
+  join        non-roots take the neighbouring root (then the neighbour's) with the largest key; ids by a scan of the root flags,
+              plus the rank's offset: aggregates never cross ranks and a level's setup exchanges nothing but sizes
+  stall       the level is the last one when the aggregates number >= 0.8 n
+  P           T (one 1.0 per row at its aggregate), A T by ``spgemm``, p_ij = [j == agg(i)] - s_i (A T)_ij,
+              Pt = transpose(P), A_c = Pt (A P) (the rows of Pt split into runs where the product is over spgemm's bound)
+  last level  n <= coarse_size: the inverse of the symmetrised matrix, formed once on the host, an HPCMatrix applied by the
+              dense mat-vec; else ``coarse_sweeps`` damped Jacobi sweeps from zero
+
+The cycle is a symmetric V(1,1): x = s .* b, r = b - A x, x += P cycle(Pt r), x += s .* (b - A x); ``M`` is positive definite.
+Its SpMVs are the ordinary ones on ordinary plans; x = s .* b and x += s .* (b - t) are fused kernels of csrc/amg.hip.
+
+Limits: Float64, ``cg`` only, ``A`` symmetric positive definite with a positive stored diagonal, rows and columns partitioned
+alike, one rank (the aggregation is rank-local and runs on several; the products and transposes of the setup move values between
+ranks through RCCL only, so the hierarchy across ranks waits for a transport that ranks sharing a GPU have too).
+"""
+from __future__ import annotations
+
+from typing import List, Optional
+
+import numpy as np
+
+from . import _capi
+from .sparse import HPCSparseMatrix, HPCSparseMatrix_local_device, get_vector_plan, mul_
+from .vectors import HPCVector, current_stream_ptr, dptr, f64_only, rd16, wr16
+
+STALL = 0.8
+MAX_ROUNDS = 64
+MAX_COARSE_SIZE = 1024
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def check_arguments(T, shape, row_partition, col_partition, theta=0.0, max_levels=12, coarse_size=128, coarse_sweeps=4) -> None:
+    """The argument rules, on host values only: ``T`` the element type, ``shape`` and the partitions A's."""
+    if np.dtype(T) != np.dtype(np.float64):
+        raise TypeError("amg: offered for Float64 backends only")
+    if int(shape[0]) != int(shape[1]):
+        raise ValueError(f"amg: the matrix must be square, got {shape[0]} x {shape[1]}")
+    if not np.array_equal(np.asarray(row_partition), np.asarray(col_partition)):
+        raise ValueError("amg: A's rows and columns must be partitioned alike")
+    if not (0.0 <= float(theta) < 1.0):
+        raise ValueError(f"amg: theta must lie in [0, 1), got {theta}")
+    if int(max_levels) < 1:
+        raise ValueError("amg: max_levels must be at least 1")
+    if not (1 <= int(coarse_size) <= MAX_COARSE_SIZE):
+        raise ValueError(f"amg: coarse_size must lie in 1..{MAX_COARSE_SIZE}")
+    if int(coarse_sweeps) < 1:
+        raise ValueError("amg: coarse_sweeps must be at least 1")
+
+
+class AMGLevel:
+    """One level: ``A``, the smoother ``s`` (an HPCVector) with its weight ``w`` and ``rho``, ``n`` (global rows), and on every
+    level but the last ``P``, ``Pt``, ``aggregates`` (global ids of the local rows, a device tensor), ``n_roots`` (this rank's)
+    and ``coarse_partition``.  A level that stalled keeps its aggregation.  The last level has ``inverse`` (an HPCMatrix: this
+    rank's rows of the dense inverse) or ``sweeps``."""
+
+    def __init__(self, A: HPCSparseMatrix):
+        self.A = A
+        self.n = int(A.shape[0])
+        self.s = self.w = self.rho = None
+        self.P = self.Pt = self.aggregates = self.coarse_partition = self.inverse = None
+        self.n_roots = self.rounds = self.sweeps = self.galerkin = None
+
+
+class AMGWorkspace:
+    """The vectors of a cycle: per level x, b (the coarse ones), t (where the level multiplies by its A) and r / e (where it has a
+    P).  One per user of a hierarchy: a ``PCGWorkspace`` holds its own next to its solve vectors (two solves with one hierarchy
+    do not share any), ``AMG.apply`` uses the hierarchy's."""
+
+    def __init__(self, levels: List[AMGLevel]):
+        mk = lambda lvl: HPCVector.zeros(lvl.A.row_partition, lvl.A.backend)
+        self.x = [mk(l) for l in levels]
+        self.b = [None] + [mk(l) for l in levels[1:]]
+        self.t = [mk(l) if l.inverse is None else None for l in levels]
+        self.r = [mk(l) if l.P is not None else None for l in levels]
+
+
+class AMG:
+    """The hierarchy.  ``levels``: AMGLevel objects, fine to coarse; ``operator_complexity``: the stored entries of every
+    level's A over those of the first (global counts)."""
+
+    def __init__(self, levels: List[AMGLevel], operator_complexity: float):
+        self.levels = levels
+        self.operator_complexity = float(operator_complexity)
+        self._work: Optional[AMGWorkspace] = None
+
+    def workspace(self) -> AMGWorkspace:
+        """The vectors ``apply`` works in: calls of ``apply`` on one hierarchy must follow each other on one stream."""
+        if self._work is None:
+            self._work = AMGWorkspace(self.levels)
+        return self._work
+
+    def apply(self, r: HPCVector, out: Optional[HPCVector] = None) -> HPCVector:
+        """``out = M r``: one V(1,1) cycle from zero; r on A's row partition."""
+        ws = self.workspace()
+        if r.structural_hash != ws.x[0].structural_hash:
+            raise ValueError("amg: r must be partitioned like the rows of A")
+        out = r.similar() if out is None else out
+        rv, (xv, land) = rd16(r.v), wr16(out.v)              # the smoother kernels read and write 16 bytes at a time
+        wrap = lambda v, t: v if t is v.v else HPCVector(v.structural_hash, v.partition, t, v.backend)
+        self._cycle(0, wrap(r, rv), wrap(out, xv), ws)
+        land()
+        return out
+
+    def _cycle(self, k: int, b: HPCVector, x: HPCVector, ws: AMGWorkspace) -> None:
+        lvl = self.levels[k]
+        n, s = b.local_length, current_stream_ptr()
+        if lvl.inverse is not None:
+            from .dense import dense_matvec
+            dense_matvec(lvl.inverse, b, y=x)
+            return
+        t = ws.t[k]
+        _capi.call("hpcla_amg_presmooth_f64", dptr(lvl.s.v), dptr(b.v), dptr(x.v), n, s)                 # x = s .* b
+        if lvl.P is None:
+            for _ in range(lvl.sweeps - 1):
+                mul_(t, lvl.A, x)
+                _capi.call("hpcla_amg_postsmooth_f64", dptr(lvl.s.v), dptr(b.v), dptr(t.v), dptr(x.v), n, s)
+            return
+        r = ws.r[k]
+        mul_(t, lvl.A, x)                                                                                  # t = A x
+        _capi.call("hpcla_axpby_f64", 1.0, dptr(b.v), -1.0, dptr(t.v), dptr(r.v), n, s)                    # r = b - t
+        mul_(ws.b[k + 1], lvl.Pt, r)                                                                       # bc = Pt r
+        self._cycle(k + 1, ws.b[k + 1], ws.x[k + 1], ws)
+        mul_(r, lvl.P, ws.x[k + 1])                                                                        # e = P xc
+        _capi.call("hpcla_axpy_f64", 1.0, None, None, dptr(r.v), dptr(x.v), n, s)                          # x += e
+        mul_(t, lvl.A, x)                                                                                  # t = A x
+        _capi.call("hpcla_amg_postsmooth_f64", dptr(lvl.s.v), dptr(b.v), dptr(t.v), dptr(x.v), n, s)      # x += s .* (b - t)
+
+
+def _raise_together(backend, local_row: int, row_start: int, message) -> None:
+    """``local_row`` < 0: this rank has nothing to report.  Every rank raises ValueError for the smallest global row."""
+    from .backends import comm_allgather
+    mine = -1 if local_row < 0 else row_start + local_row
+    every = comm_allgather(backend.comm, np.array([mine], dtype=np.int64))
+    bad = every[every >= 0]
+    if len(bad):
+        raise ValueError(message(int(bad.min())))
+
+
+def _weights(lvl: AMGLevel, plan, sfx: str, row_start: int):
+    """diag(A) on the device, s = w ./ diag(A); raises on every rank for a diagonal that is not positive."""
+    from .partition import compute_partition_hash
+    from .vectors import maximum
+    torch = _torch()
+    A = lvl.A
+    backend, dev, n = A.backend, A.backend.torch_device, A.nrows_local
+    diag = torch.zeros(max(n, 1), dtype=torch.float64, device=dev)
+    ratio = torch.zeros(n, dtype=torch.float64, device=dev)
+    info = torch.zeros(1, dtype=torch.int64, device=dev)
+    s = current_stream_ptr()
+    _capi.call(f"hpcla_amg_weights_f64_{sfx}", dptr(plan.rowptr_of(A)), dptr(plan.colval_split), dptr(A.nzval), n, plan.n_own, 0,
+               dptr(diag), dptr(ratio), dptr(info), s)
+    _raise_together(backend, int(info.item()), row_start,
+                    lambda row: f"amg: the diagonal of row {row} is not positive (level of {lvl.n} rows)")
+    h = compute_partition_hash(A.row_partition)
+    lvl.rho = maximum(HPCVector(h, A.row_partition, ratio, backend))
+    lvl.w = 4.0 / (3.0 * lvl.rho)
+    sv = torch.zeros(n, dtype=torch.float64, device=dev)
+    _capi.call("hpcla_amg_smoother_f64", lvl.w, dptr(diag), dptr(sv), n, s)
+    lvl.s = HPCVector(h, A.row_partition, sv, backend)
+    return diag
+
+
+def _aggregate(lvl: AMGLevel, plan, sfx: str, diag, theta: float, row_start: int) -> None:
+    """Strength graph, roots, join, numbering: fills lvl.aggregates, lvl.n_roots, lvl.rounds, lvl.coarse_partition."""
+    from .backends import comm_allgather, comm_rank
+    torch = _torch()
+    lib = _capi.load()
+    A = lvl.A
+    backend, dev, n = A.backend, A.backend.torch_device, A.nrows_local
+    s = current_stream_ptr()
+    i64 = lambda k, fill=0: torch.full((max(k, 1),), fill, dtype=torch.int64, device=dev)
+    work = i64(lib.hpcla_amg_work_bytes(n) // 8)
+    info = i64(2)
+    s_rowptr = i64(n + 1)
+    structure = (dptr(plan.rowptr_of(A)), dptr(plan.colval_split), dptr(A.nzval), dptr(diag), n, plan.n_own, 0, float(theta))
+    _capi.call(f"hpcla_amg_strength_count_f64_{sfx}", *structure, dptr(s_rowptr), dptr(info), dptr(work), s)
+    s_cols = torch.empty(max(int(info[0].item()), 1), dtype=torch.int32, device=dev)      # the size the graph is allocated by
+    _capi.call(f"hpcla_amg_strength_fill_f64_{sfx}", *structure, dptr(s_rowptr), dptr(s_cols), s)
+
+    key, m1, m2, state, state_next = (i64(n) for _ in range(5))
+    counts = i64(lib.hpcla_amg_round_blocks(n))
+    _capi.call("hpcla_amg_mis_init", n, row_start, dptr(key), dptr(state), s)
+    rounds = 0
+    while True:                                              # a rank's set is its own: no rank waits for another here
+        if rounds == MAX_ROUNDS:
+            raise RuntimeError("amg: the independent set did not finish in 64 rounds")
+        _capi.call("hpcla_amg_mis_round", dptr(s_rowptr), dptr(s_cols), n, dptr(key), dptr(state), dptr(m1), dptr(m2),
+                   dptr(state_next), dptr(counts), s)
+        state, state_next = state_next, state
+        rounds += 1
+        if n == 0 or int(counts.sum().item()) == 0:          # the one read-back of a round
+            break
+    owner_a = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    owner_b = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    rootid = i64(n)
+    _capi.call("hpcla_amg_join", dptr(s_rowptr), dptr(s_cols), n, dptr(key), dptr(state), dptr(owner_a), dptr(owner_b), dptr(rootid),
+               dptr(info), dptr(work), s)
+    lost, n_roots = (int(v) for v in info.cpu().tolist())
+    if lost != -1:
+        raise RuntimeError(f"amg: local row {lost} was left without an aggregate")
+    every = comm_allgather(backend.comm, np.array([n_roots], dtype=np.int64))
+    lvl.coarse_partition = np.concatenate([[0], np.cumsum(every)]).astype(np.int64)
+    lvl.n_roots, lvl.rounds = n_roots, rounds
+    agg = torch.empty(n, dtype=torch.int64, device=dev)
+    _capi.call("hpcla_amg_aggregate_ids", dptr(owner_b), dptr(rootid), n, int(lvl.coarse_partition[comm_rank(backend.comm)]),
+               dptr(agg), s)
+    lvl.aggregates = agg
+
+
+def _prolongator(lvl: AMGLevel) -> HPCSparseMatrix:
+    """P on the pattern of A T, and Pt; returns the next level's A."""
+    from .backends import comm_rank
+    from .indexing import _col_indices_dev
+    from .matmat import spgemm
+    from .transpose import transpose
+    torch = _torch()
+    A = lvl.A
+    backend, dev, n = A.backend, A.backend.torch_device, A.nrows_local
+    part = lvl.coarse_partition
+    nc = int(part[-1])
+    lo = int(part[comm_rank(backend.comm)])
+    window = (lo, lo + lvl.n_roots - 1) if lvl.n_roots > 0 else (0, 0)
+    T = HPCSparseMatrix_local_device(torch.arange(n + 1, dtype=torch.int64, device=dev), lvl.aggregates,
+                                     torch.ones(n, dtype=torch.float64, device=dev), nc, backend, col_partition=part,
+                                     col_window=window)
+    AT = spgemm(A, T)
+    vals = torch.empty_like(AT.nzval)
+    sfx = "i64" if AT.Ti == np.dtype(np.int64) else "i32"
+    _capi.call(f"hpcla_amg_prolongator_f64_{sfx}", dptr(AT.rowptr_target), dptr(AT.colval_target()), dptr(_col_indices_dev(AT)),
+               dptr(AT.nzval), dptr(lvl.aggregates), dptr(lvl.s.v), n, 0, dptr(vals), current_stream_ptr())
+    lvl.P = AT._with_values(vals)
+    lvl.Pt = transpose(lvl.P).materialize()
+    return galerkin(lvl, A)
+
+
+FORCE_SPLIT = 0                # tests set it to split the rows of Pt below on matrices that do not need it
+MAX_SPLIT = 32
+
+
+def _split_rows(Pt: HPCSparseMatrix, q: int) -> List[HPCSparseMatrix]:
+    """Pt as a sum of q matrices of its shape: part j keeps, of every row, the j-th of q runs of its stored entries (order kept).
+    Index arithmetic on the device; the parts are assembled like any device-built matrix."""
+    from .indexing import _col_indices_dev
+    torch = _torch()
+    dev, n = Pt.backend.torch_device, Pt.nrows_local
+    rowptr = Pt.rowptr_target.to(torch.int64)
+    counts = rowptr[1:] - rowptr[:-1]
+    row_of = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), counts)
+    pos = torch.arange(Pt.nnz, dtype=torch.int64, device=dev) - rowptr[row_of]
+    part_of = (pos * q) // counts[row_of]
+    cols = _col_indices_dev(Pt)[Pt.colval_target().to(torch.int64)]
+    parts = []
+    for j in range(q):
+        keep = part_of == j
+        if not bool(keep.any()):
+            continue
+        rp = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        rp[1:] = torch.cumsum(torch.bincount(row_of[keep], minlength=n), 0)
+        parts.append(HPCSparseMatrix_local_device(rp, cols[keep].contiguous(), Pt.nzval[keep].contiguous(), int(Pt.shape[1]),
+                                                  Pt.backend, col_partition=Pt.col_partition))
+    return parts
+
+
+def galerkin(lvl: AMGLevel, A: HPCSparseMatrix) -> HPCSparseMatrix:
+    """``Pt (A P)``.  ``hp.spgemm`` bounds the candidate products of an output row (the lengths of the rows of ``A P`` that a row
+    of ``Pt`` names, summed); the aggregates of a 3-D stencil's coarse levels are over it.  There the rows of ``Pt`` are split
+    into q runs of their entries, ``Pt = Pt_1 + ... + Pt_q``, and the coarse matrix is ``Pt_1 (A P) + ... + Pt_q (A P)``: the
+    same pattern, the same products, the sums of an entry associated run by run, so the last bits can differ from the unsplit
+    product's.  q doubles until every part fits; ``lvl.galerkin`` records it (1: not split)."""
+    from .addition import sparse_add
+    from .matmat import spgemm
+    AP = spgemm(A, lvl.P)
+    q = max(int(FORCE_SPLIT), 1)
+    while True:
+        try:
+            if q == 1:
+                Ac = spgemm(lvl.Pt, AP)
+            else:
+                parts = _split_rows(lvl.Pt, q)
+                Ac = spgemm(parts[0], AP)
+                for part in parts[1:]:
+                    Ac = sparse_add(Ac, spgemm(part, AP))
+            lvl.galerkin = q
+            return Ac
+        except NotImplementedError as exc:
+            if "candidate entries" not in str(exc) or 2 * q > MAX_SPLIT:
+                raise NotImplementedError(f"amg: the coarse matrix of the level of {lvl.n} rows cannot be formed: {exc}") from None
+            q *= 2
+
+
+def _dense_inverse(lvl: AMGLevel) -> None:
+    """The last level's rows on the host; the inverse of the symmetrised matrix, applied by the dense mat-vec."""
+    from .dense import HPCMatrix
+    torch = _torch()
+    A = lvl.A
+    n = lvl.n
+    D = np.zeros((n, n))
+    if A.nnz:
+        rowptr = A.rowptr.astype(np.int64)
+        cols = A.col_indices[A.colval.astype(np.int64)]
+        D[np.repeat(np.arange(n), np.diff(rowptr)), cols] = A.nzval.cpu().numpy()
+    inv = np.linalg.inv((D + D.T) / 2)
+    mine = torch.from_numpy(np.ascontiguousarray(inv)).to(A.backend.torch_device)
+    lvl.inverse = HPCMatrix(A.row_partition, A.row_partition, mine, A.backend)
+
+
+def aggregate_level(A: HPCSparseMatrix, theta: float = 0.0) -> AMGLevel:
+    """The rank-local part of a level's setup alone, for tests: the weights and the aggregation of ``A`` as an AMGLevel (``s``,
+    ``w``, ``rho``, ``aggregates``, ``n_roots``, ``rounds``, ``coarse_partition``; no P).  It exchanges nothing but sizes, the
+    maximum of rho and the error word, so unlike ``amg`` it runs on several ranks.  Raises like ``amg``."""
+    from .backends import comm_rank
+    f64_only(A.backend, "amg")
+    check_arguments(A.backend.T, A.shape, A.row_partition, A.col_partition, theta)
+    lvl = AMGLevel(A)
+    plan = get_vector_plan(A, HPCVector.zeros(A.col_partition, A.backend))
+    sfx = "i64" if plan.is_i64 else "i32"
+    row_start = int(A.row_partition[comm_rank(A.backend.comm)])
+    _aggregate(lvl, plan, sfx, _weights(lvl, plan, sfx, row_start), theta, row_start)
+    return lvl
+
+
+def amg(A: HPCSparseMatrix, theta: float = 0.0, max_levels: int = 12, coarse_size: int = 128, coarse_sweeps: int = 4) -> AMG:
+    """Build the smoothed-aggregation multigrid preconditioner of a symmetric positive definite ``A`` for
+    ``hp.cg(A, b, M=hp.amg(A))``.
+
+    ``theta``: the strength threshold in [0, 1) (0 keeps every stored coupling; 0.25 suits anisotropic problems).  Setup stops
+    at ``n <= coarse_size`` (1..1024; solved densely), at ``max_levels``, or when a level's aggregates number >= 0.8 n; a last
+    level above ``coarse_size`` gets ``coarse_sweeps`` damped Jacobi sweeps.  Raises ValueError, with the global row, for a
+    diagonal that is not positive (a NaN counts), and NotImplementedError for a communicator of more than one rank and for a
+    level whose coarse matrix is over ``hp.spgemm``'s bound in both orders of the product."""
+    from .backends import comm_allgather, comm_rank, comm_size
+    f64_only(A.backend, "amg")
+    check_arguments(A.backend.T, A.shape, A.row_partition, A.col_partition, theta, max_levels, coarse_size, coarse_sweeps)
+    backend = A.backend
+    if comm_size(backend.comm) > 1:                              # the same on every rank
+        raise NotImplementedError("amg: one rank only in this version.  Across ranks the setup's products and transposes move "
+                                  "their values through RCCL, which ranks that share one GPU do not have, so the hierarchy and "
+                                  "the solve across ranks cannot be tested yet; the aggregation itself is rank-local")
+    rank = comm_rank(backend.comm)
+    levels: List[AMGLevel] = []
+    nnz = []
+    while True:
+        lvl = AMGLevel(A)
+        levels.append(lvl)
+        nnz.append(int(comm_allgather(backend.comm, np.array([A.nnz], dtype=np.int64)).sum()))
+        plan = get_vector_plan(A, HPCVector.zeros(A.col_partition, backend))
+        sfx = "i64" if plan.is_i64 else "i32"
+        row_start = int(A.row_partition[rank])
+        diag = _weights(lvl, plan, sfx, row_start)
+        last = lvl.n <= coarse_size or len(levels) >= max_levels
+        if not last:
+            _aggregate(lvl, plan, sfx, diag, theta, row_start)
+            last = int(lvl.coarse_partition[-1]) >= STALL * lvl.n
+        if last:
+            if lvl.n <= coarse_size:
+                _dense_inverse(lvl)
+            else:
+                lvl.sweeps = int(coarse_sweeps)
+            return AMG(levels, sum(nnz) / max(nnz[0], 1))
+        A = _prolongator(lvl)

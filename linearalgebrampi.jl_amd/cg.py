@@ -29,6 +29,7 @@ state once per ``check_every`` iterations, and the iterations enqueued behind th
 from __future__ import annotations
 
 import math
+import time
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
@@ -289,7 +290,11 @@ def _run_chunks(ws, backend, maxiter: int, check_every: int, enqueue) -> Tuple[i
         k = min(check_every, maxiter - j + 1)
         if j + k - 1 > ws.hist_capacity():
             ws.grow_hist(min(maxiter, 2 * (j + k)))
+        clock = getattr(ws, "enqueue_ms", None)                  # a list: the host's time in each chunk's enqueueing is appended
+        t0 = time.perf_counter() if clock is not None else 0.0
         enqueue(j, int(k))
+        if clock is not None:
+            clock.append((time.perf_counter() - t0) * 1e3)
         j += k
         done_iter, status = (int(v) for v in ws.state[:2].cpu().tolist())
         if multi:                                                # no rank leaves the loop alone, whatever produced its scalars
@@ -315,7 +320,9 @@ class PCGWorkspace(_PairHistory):
     """What a ``cg`` solve allocates: x, r, p, Ap, the history of (sum r_j^2, sum r_j.(dinv r_j)) pairs (it IS the scalar
     storage of the iterations; it grows by doubling between chunks), pAp, and the scratch of the gated kernels whose last
     32 bytes are the solve's device state (done_iter, status, thr).  Reusable: every solve resets all of it.  ``u`` and ``z``
-    (u = G r, z = Gt u) exist once a solve with ``M=<FSAI>`` has used the workspace."""
+    (u = G r, z = Gt u) exist once a solve with ``M=<FSAI>`` has used the workspace, ``z`` and ``amg`` (the cycle's level vectors)
+    once one with ``M=<AMG>`` has.  ``enqueue_ms``: set it to a list and every chunk appends the host's time in its enqueueing
+    (milliseconds, the chunk's read-back outside); benchmarks/bench_amg.py reads it."""
 
     def __init__(self, b: HPCVector, hist_iters: int = 254):
         torch = _torch()
@@ -329,14 +336,37 @@ class PCGWorkspace(_PairHistory):
         self.tmp = torch.ones(2, dtype=torch.float64, device=dev)      # [0]: |b|^2 for a given x0; [1]: the constant 1
         self.work = torch.zeros(_capi.load().hpcla_pcg_work_bytes() // 8, dtype=torch.float64, device=dev)
         self.state = self.work[-4:].view(torch.int64)                  # done_iter, status, thr (a double), reserved
-        self.u = self.z = None
+        self.u = self.z = self.amg = self._amg_of = None
 
     def fsai_vectors(self) -> None:
         if self.u is None:
-            self.u, self.z = self.r.similar(), self.r.similar()
+            self.u = self.r.similar()
+        if self.z is None:
+            self.z = self.r.similar()
+
+    def amg_vectors(self, mg) -> None:
+        """z, and this workspace's own level vectors for the hierarchy ``mg``: allocated once, kept for later solves with it."""
+        from .amg import AMGWorkspace
+        if self.z is None:
+            self.z = self.r.similar()
+        if self.amg is None or self._amg_of is not mg:
+            self.amg, self._amg_of = AMGWorkspace(mg.levels), mg
 
     def fits(self, b: HPCVector) -> bool:
         return self.x.structural_hash == b.structural_hash and self.x.v.device == b.v.device
+
+
+def _cg_amg(A, M):
+    """M when it is the hierarchy of ``hp.amg`` (amg.py is looked at only for an M that is nothing else), checked against A."""
+    if M is None or isinstance(M, (str, HPCVector)):
+        return None
+    from .amg import AMG
+    if not isinstance(M, AMG):
+        return None
+    top = M.levels[0].A
+    if not np.array_equal(top.row_partition, A.row_partition) or top.shape != A.shape:
+        raise ValueError("cg: the AMG preconditioner was built for a matrix of another shape or partition")
+    return M
 
 
 def _cg_dinv(A, b: HPCVector, M) -> Optional[HPCVector]:
@@ -351,7 +381,8 @@ def _cg_dinv(A, b: HPCVector, M) -> Optional[HPCVector]:
             raise ValueError("cg: M='jacobi' needs a positive diagonal (minimum(diag(A)) > 0)")
         return diag(A, reciprocal=True)
     if not isinstance(M, HPCVector):
-        raise ValueError("cg: M must be None, 'jacobi', an HPCVector on A's row partition or an FSAI (hp.fsai(A))")
+        raise ValueError("cg: M must be None, 'jacobi', an HPCVector on A's row partition, an FSAI (hp.fsai(A)) or an AMG "
+                         "(hp.amg(A))")
     b._same_partition(M)
     return rd16_vector(M)                                        # the step kernels read it 16 bytes at a time
 
@@ -365,8 +396,9 @@ def cg(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, atol
     after ``maxiter`` iterations (default ``10 n``), or on a breakdown (``p.Ap <= 0`` or NaN: A is not positive definite
     along p).  ``M``: ``None``, ``"jacobi"`` (``1 ./ diag(A)``, formed on the device; the diagonal must be positive), an
     HPCVector holding the inverse diagonal to apply, or the ``FSAI`` object of ``hp.fsai(A)`` (``z = Gt (G r)``: two more SpMVs
-    per iteration, ``r.M r`` formed as ``sum (G r)^2``).  ``x0`` defaults to zero.  Returns ``(x, CGInfo)``; x is the
-    workspace's vector.
+    per iteration, ``r.M r`` formed as ``sum (G r)^2``), or the ``AMG`` object of ``hp.amg(A)`` (``z`` = one multigrid V-cycle on
+    ``r``, enqueued from here between the gated steps).  ``x0`` defaults to zero.  Returns ``(x, CGInfo)``; x is the workspace's
+    vector.
 
     The stop test and the breakdown test run on the device.  The host enqueues ``check_every`` iterations in one library
     call and then reads the 16-byte state (the only synchronisation); iterations enqueued behind the one that decided are
@@ -378,7 +410,10 @@ def cg(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, atol
     if plan.result_partition_hash != ws.p.structural_hash:
         raise ValueError("cg: b must be partitioned like the rows of A")
     op = M if isinstance(M, FSAI) else None
-    dinv = None if op is not None else _cg_dinv(A, b, M)
+    mg = _cg_amg(A, M) if op is None else None
+    dinv = None if op is not None or mg is not None else _cg_dinv(A, b, M)
+    if mg is not None:
+        ws.amg_vectors(mg)
     if op is not None:
         if not np.array_equal(op.G.row_partition, A.row_partition) or op.G.shape != A.shape:
             raise ValueError("cg: the FSAI preconditioner was built for a matrix of another shape or partition")
@@ -408,6 +443,10 @@ def cg(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, atol
         mul_(ws.z, op.Gt, ws.u)
         ws.p.v.copy_(ws.z.v)
         norm(ws.u, 2, out=ws.hist[1:2])
+    elif mg is not None:                                         # z = M r (one cycle), p = z, pair 0's second slot = r.z
+        mg._cycle(0, ws.r, ws.z, ws.amg)
+        ws.p.v.copy_(ws.z.v)
+        dot(ws.r, ws.z, out=ws.hist[1:2])
     elif dinv is None:
         ws.p.v.copy_(ws.r.v)
         ws.hist[1:2].copy_(ws.hist[0:1])
@@ -434,8 +473,24 @@ def cg(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, atol
                    dptr(ws.Ap.v), dptr(ws.u.v), dptr(ws.z.v), dptr(ws.hist), dptr(ws.pAp), dptr(dot_work), dptr(ws.work),
                    first, count, current_stream_ptr())
 
+    def enqueue_amg(first, count):
+        """The order of hpcla_pcg_fsai_iterations_*, enqueued from here through the exported gated entries: Ap and pAp, the
+        residual step (dinv == NULL), the cycle on r into z (not gated: behind the deciding iteration r is frozen and the cycle
+        rewrites its own vectors with what they held), r.z into the pair's second slot, the direction step with z for r."""
+        n, s, comm = ws.x.local_length, current_stream_ptr(), A.backend.rccl
+        for j in range(first, first + count):
+            prev, cur = ws.hist[2 * j - 1:2 * j], ws.hist[2 * j:2 * j + 2]
+            mul_dot_(ws.Ap, A, ws.p, ws.pAp)
+            _capi.call("hpcla_pcg_residual_f64", comm, dptr(prev), dptr(ws.pAp), dptr(ws.Ap.v), None, dptr(ws.r.v), n, j,
+                       dptr(ws.state), dptr(cur), dptr(ws.work), s)
+            mg._cycle(0, ws.r, ws.z, ws.amg)
+            dot(ws.r, ws.z, out=cur[1:2])
+            _capi.call("hpcla_pcg_direction_f64", dptr(prev), dptr(ws.pAp), dptr(cur[1:2]), dptr(prev), dptr(ws.z.v), None,
+                       dptr(ws.x.v), dptr(ws.p.v), n, j, dptr(ws.state), s)
+
     if op is not None:
         blocks = blk + plan_g.matrix_block(op.G) + plan_t.matrix_block(op.Gt)
-    iterations, status = _run_chunks(ws, A.backend, maxiter, check_every, enqueue_fsai if op is not None else enqueue_diagonal)
+    enqueue = enqueue_fsai if op is not None else (enqueue_amg if mg is not None else enqueue_diagonal)
+    iterations, status = _run_chunks(ws, A.backend, maxiter, check_every, enqueue)
     h = _residual_norms(ws, b.backend, iterations)
     return ws.x, CGInfo(status == 1, iterations, _STATUS[status], h)
