@@ -20,6 +20,12 @@ Level setup, on the current level's A:
 Cases (``cases()``): 5-point grids 16x16, 32x32, 64x64 and 37x53, the 7-point grid 16^3, the anisotropic 40x40 grid (couplings
 1 and 0.01), a diagonal matrix, n = 1 and n = 2, path graphs of 255, 256 and 257 rows, a star whose hub has 300 neighbours, and
 a seeded random symmetric diagonally dominant matrix of 600 rows.
+
+For the tests that call the kernels' C entries on their own (tests/test_gpu_precond_kernels.py): ``split_block`` gives one block
+of a partition in the rank-local split form the entries read, ghosts included; ``weights_stored_order`` the weights with the row
+sum in the order the method defines; ``mis2_states`` the independent set round by round on a block's own graph;
+``compressed_columns`` a column space that is not in ascending order; ``chain_levels`` / ``chain_coverage`` the levels those
+tests walk and the edges they hold.
 """
 import math
 
@@ -320,6 +326,111 @@ def pcg_amg(A, b, levels, **kw):
 def pcg_jacobi(A, b, **kw):
     dinv = 1.0 / A.diagonal()
     return pcg_m(A, b, lambda r: dinv * r, **kw)
+
+
+# ---- one block at a time: the inputs and stages of the kernels' C entries ----------------------------------------------------
+def split_block(A, partition, j, base=0, Ti=np.int32):
+    """The rank-local split form of block j's rows: (rowptr, colval_split, vals, n_own, ghosts).  An owned column c becomes
+    c - lo, a ghost n_own + its position among the block's sorted distinct ghosts (``ghosts``: their global ids); entries stay
+    in stored (global ascending) order, so ghosts below lo come before the owned columns.  ``base`` is added to both index
+    arrays, which have type ``Ti``."""
+    A = A.tocsr()
+    lo, hi = int(partition[j]), int(partition[j + 1])
+    a, b = int(A.indptr[lo]), int(A.indptr[hi])
+    cols = A.indices[a:b].astype(np.int64)
+    own = (cols >= lo) & (cols < hi)
+    ghosts = np.unique(cols[~own])
+    split = np.where(own, cols - lo, (hi - lo) + np.searchsorted(ghosts, cols))
+    rowptr = A.indptr[lo:hi + 1].astype(np.int64) - a
+    return (rowptr + base).astype(Ti), (split + base).astype(Ti), A.data[a:b].copy(), hi - lo, ghosts
+
+
+def weights_stored_order(A):
+    """(d, sum_j |a_ij| / d) with the row sum added one entry at a time in stored order (``weights`` adds pairwise); d = 0
+    where no diagonal is stored."""
+    A = A.tocsr()
+    n = A.shape[0]
+    d = A.diagonal()
+    start, length = A.indptr[:-1].astype(np.int64), np.diff(A.indptr)
+    absval = np.abs(A.data)
+    total = np.zeros(n)
+    for k in range(int(length.max()) if n else 0):              # the k-th stored entry of every row that has one
+        rows = np.flatnonzero(length > k)
+        total[rows] = total[rows] + absval[start[rows] + k]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return d, total / d
+
+
+def mis2_states(indptr, indices, key):
+    """The state array after each round of ``mis2`` on one graph and its keys (a block's own: local columns, the block's keys);
+    the last one has no undecided row."""
+    k = key.copy()
+    while np.any((k >= 0) & (k < ROOT)):
+        m2 = neighbour_max(indptr, indices, neighbour_max(indptr, indices, k))
+        und = (k >= 0) & (k < ROOT)
+        k = np.where(und & (m2 == key), ROOT, np.where(und & (m2 >= ROOT), -1, k))
+        yield k.copy()
+
+
+def compressed_columns(rows_indices, rng):
+    """(colval_local, col_indices): a block's global columns as local ids into ``col_indices``, which lists the distinct columns
+    in a shuffled order, not an ascending one: col_indices[colval_local] gives the columns back."""
+    distinct = np.unique(np.asarray(rows_indices, dtype=np.int64))
+    order = rng.permutation(len(distinct))
+    col_indices = distinct[order]
+    where = np.empty(len(distinct), dtype=np.int64)
+    where[order] = np.arange(len(distinct))
+    return where[np.searchsorted(distinct, rows_indices)], col_indices
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+CHAIN_COARSE = 8               # coarse_size at which every case but n = 1, 2 aggregates at least once
+
+
+def theta_of(name):
+    return 0.25 if name.startswith("aniso") else 0.0
+
+
+def aggregate_product(lvl):
+    """A T of a level that aggregated (T: one 1.0 per row at its aggregate), every structural entry stored."""
+    n, nc = lvl["n"], int(lvl["counts"].sum())
+    T = sp.csr_matrix((np.ones(n), lvl["agg"], np.arange(n + 1)), shape=(n, nc))
+    return structural_product(lvl["A"], T)
+
+
+def chain_levels(matrices, names=None):
+    """(name, blocks) -> the levels that aggregate of ``setup`` at coarse_size = CHAIN_COARSE over ``equal_blocks``, theta 0.25
+    on the anisotropic grid and 0 elsewhere: what the tests of the kernels' C entries walk block by block."""
+    out = {}
+    for name in (matrices if names is None else names):
+        A = matrices[name]
+        for k in BLOCKS:
+            levels = setup(A, equal_blocks(A.shape[0], k), theta_of(name), coarse_size=CHAIN_COARSE)
+            out[name, k] = [lvl for lvl in levels if "agg" in lvl]
+    return out
+
+
+def chain_coverage(levels_by_case):
+    """What those levels hold: their number, the blocks (chains), the blocks of one row, the stored zeros, the levels with a row
+    that has no strong neighbour, the most ghost entries of a level and the longest row of A T."""
+    out = dict(levels=0, chains=0, one_row_blocks=0, stored_zeros=0, isolated=0, ghost_entries=0, longest_row=0)
+    for levels in levels_by_case.values():
+        for lvl in levels:
+            A, part = lvl["A"], np.asarray(lvl["partition"])
+            sizes = np.diff(part)
+            out["levels"] += 1
+            out["chains"] += int(np.sum(sizes > 0))
+            out["one_row_blocks"] += int(np.sum(sizes == 1))
+            out["stored_zeros"] += int(np.sum(A.data == 0))
+            out["isolated"] += int(np.any(np.diff(lvl["graph"][0]) == 0))
+            _, block = keys_of(lvl["partition"])
+            row = np.repeat(np.arange(lvl["n"]), np.diff(A.indptr))
+            out["ghost_entries"] = max(out["ghost_entries"], int(np.sum(block[row] != block[A.indices])))
+            out["longest_row"] = max(out["longest_row"], int(np.diff(aggregate_product(lvl).indptr).max()))
+    return out
 
 
 # ---- the argument rules, restated ---------------------------------------------------------------------------------------------

@@ -21,6 +21,10 @@ Cases
                    1 - 4 < 0 at row 2).
   no diagonal      tridiagonal n = 9 whose row 4 does not store its diagonal.
   pattern          the structure of A^2 for the 16x16 grid (up to 7 entries per row of G).
+  three faults     ``three_faults``: 600 banded rows with a NaN diagonal, a diagonal that is not stored and a pivot that is not
+                   positive, healed one at a time (the order of the error word).
+  pattern is not A ``pattern_is_not_a``: a 40-row block whose pattern rows hold columns above the diagonal, ghosts in front of
+                   the owned columns and entries A does not store, while A stores entries outside the pattern.
 """
 import math
 
@@ -250,6 +254,68 @@ def pcg_op(rowptr, colidx, vals, b, G, rtol=1e-8, atol=0.0, maxiter=None, x0=Non
         if converged:
             return x, j, "converged", hist
     return x, maxiter, "maxiter", hist
+
+
+# ---- inputs of the kernels' C entries, one block at a time ------------------------------------------------------------------
+def to_scipy(rowptr, colidx, vals=None, ncols=None):
+    """scipy CSR with exactly the stored entries given (ones where ``vals`` is None: a pattern)."""
+    import scipy.sparse as sp
+    n = len(rowptr) - 1
+    vals = np.ones(len(colidx)) if vals is None else vals
+    return sp.csr_matrix((np.array(vals, dtype=np.float64), np.array(colidx), np.array(rowptr)), shape=(n, n if ncols is None else ncols))
+
+
+FAULT_ROWS = (40, 300, 520)                                     # NaN diagonal, no stored diagonal, a pivot that is not positive
+
+
+def three_faults(heal=0, n=600, w=3):
+    """``banded(w, n)`` with three faults, the first ``heal`` of them (in row order) taken out again: the diagonal of row 40 is
+    NaN, row 300 does not store its diagonal, and the diagonal of row 520 is 0.01, positive but below the sum of squares of its
+    row of L, so its pivot is negative.  (rowptr, colidx, vals); the pattern is the matrix's own."""
+    rowptr, colidx, vals = banded(w, n)
+    at = lambda r: int(rowptr[r] + np.flatnonzero(colidx[rowptr[r]:rowptr[r + 1]] == r)[0])
+    vals = vals.copy()
+    if heal < 3:
+        vals[at(520)] = 0.01
+    if heal < 1:
+        vals[at(40)] = np.nan
+    if heal < 2:
+        keep = np.ones(len(colidx), dtype=bool)
+        keep[at(300)] = False
+        rowptr = rowptr.copy()
+        rowptr[301:] -= 1
+        colidx, vals = colidx[keep], vals[keep]
+    return rowptr, colidx, vals
+
+
+def pattern_is_not_a(n=60, lo=10, hi=50):
+    """(A, pattern, thinned pattern, partition, block): scipy matrices of n rows whose block [lo, hi) is a 40-row rank-local
+    case.  A is banded, half-bandwidth 3, strictly diagonally dominant.  A pattern row i holds i - 1 and i - 2 (stored by A),
+    i - 5 (A does not store it), i + 1 and i + 4 (above the diagonal), on every third row columns 2 and 7 (ghosts, in front of
+    the owned columns) and on every fourth row column n - 3 (a ghost behind them); the diagonal on odd rows only; never i - 3,
+    which A stores.  The thinned pattern drops what the method ignores: the columns above the diagonal and the ghosts."""
+    rowptr, colidx, vals = banded(3, n)
+    full_ptr, full, thin_ptr, thin = [0], [], [0], []
+    for i in range(n):
+        cols = {i - 1, i - 2, i - 5, i + 1, i + 4}
+        if i % 3 == 0:
+            cols |= {2, 7}
+        if i % 4 == 0:
+            cols.add(n - 3)
+        if i % 2:
+            cols.add(i)
+        cols = sorted(c for c in cols if 0 <= c < n)
+        block_lo = lo if lo <= i < hi else 0
+        block_hi = hi if lo <= i < hi else n
+        kept = [c for c in cols if block_lo <= c < block_hi and c <= i]
+        full += cols
+        thin += kept
+        full_ptr.append(len(full))
+        thin_ptr.append(len(thin))
+    A = to_scipy(rowptr, colidx, vals)
+    P = to_scipy(np.array(full_ptr), np.array(full, dtype=np.int64))
+    Pthin = to_scipy(np.array(thin_ptr), np.array(thin, dtype=np.int64))
+    return A, P, Pthin, [0, lo, hi, n], 1
 
 
 def spd_cases(orc):

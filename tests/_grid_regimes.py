@@ -76,6 +76,14 @@ _dg_m1, DIGEST_T, DIGEST_CAP, _dg_cap, _dg_t = _ints(
     "construct.hip", _pat("int64_t g = ( n + # ) / # ; if ( g > # ) g = # ;") + _WS +
     _pat("digest_kernel < I > <<< ( uint32_t ) g , # , 0 , s >>>"))
 assert _dg_m1 == DIGEST_T - 1 and _dg_cap == DIGEST_CAP and _dg_t == DIGEST_T
+# the two fused smoother kernels (amg.hip): g = (n / 2 + 255) / 256, clamped to [1, 4096], workgroups of 256 lanes
+AMG_SMOOTH_WIDTH, _as_m1, AMG_SMOOTH_T, AMG_SMOOTH_CAP, _as_cap, _as_t = _ints(
+    "amg.hip", _pat("int64_t g = ( n / # + # ) / # ; g = g < 1 ? 1 : ( g > # ? # : g ) ;") + _WS +
+    _pat("amg_smooth_kernel < MODE > <<< ( uint32_t ) g , # , 0 , as_stream ( stream ) >>>"))
+_as_first, _as_stride = _ints(
+    "amg.hip", _pat("int64_t i = ( int64_t ) blockIdx . x * # + threadIdx . x ; const int64_t stride = ( int64_t ) gridDim . x * # ;") +
+    _WS + _pat("for ( ; i < n2 ; i += stride ) {"))
+assert _as_m1 == AMG_SMOOTH_T - 1 and _as_cap == AMG_SMOOTH_CAP and _as_t == AMG_SMOOTH_T == _as_first == _as_stride
 
 
 # ---- the grid functions ----------------------------------------------------------------------------------------------------
@@ -112,6 +120,11 @@ def digest_grid(n):
 
 def digest_trips(n):
     return _ceil_div(n, digest_grid(n) * DIGEST_T) if n else 0
+
+
+def amg_smooth_grid(n):
+    """Workgroups of amg_smooth_kernel over n doubles (n // 2 double2, the odd element by one thread)."""
+    return min(max(_ceil_div(n // AMG_SMOOTH_WIDTH, AMG_SMOOTH_T), 1), AMG_SMOOTH_CAP)
 
 
 def partials_two_stage(np_):
@@ -152,6 +165,16 @@ def elementwise_regime(n):
     return "E3" if n // 2 > g * EW_T else None
 
 
+def amg_smooth_regime(n):
+    """Of the two smoother kernels over n doubles, on their own grid: E3 is the capped grid with a further grid-stride trip."""
+    g = amg_smooth_grid(n)
+    if g == 1:
+        return "E1"
+    if g < AMG_SMOOTH_CAP:
+        return "E2"
+    return "E3" if n // AMG_SMOOTH_WIDTH > g * AMG_SMOOTH_T else None
+
+
 def has_tail(n, width=None):
     """Whether lane 0 of workgroup 0 has a scalar tail to add at this size."""
     return n % (REDUCE_WIDTH if width is None else width) != 0
@@ -182,6 +205,9 @@ PLAIN_F64_NAN = [(1, 0), (64, 63), (513, 0), (513, 512), (100_003, 50_001), (4_0
 F32_ALONE = [0, 1, 3, 4, 1023, 1024, 1025, 1_000_003, 1_228_807, R4_N]
 # cg_update_ / cg_residual_ / cg_direction_ on vectors alone
 CG_TRIO_ALONE = [1, 511, 2051, R3_N, R4_N]
+# hpcla_amg_presmooth_f64 / hpcla_amg_postsmooth_f64 on vectors alone: 1, 2, 3 and 511 one workgroup (the odd element alone, one
+# double2, both), 2051 five workgroups, R3_N 1201, R4_N the grid capped at 4096 with a third trip and the odd element
+AMG_SMOOTH_ALONE = [1, 2, 3, 511, 2051, R3_N, R4_N]
 
 REDUCTION_FAMILIES = {
     "pcg": PCG_ALONE, "bicgstab": BICGSTAB_ALONE, "lsqr": LSQR_ALONE, "minres": MINRES_ALONE,
@@ -190,6 +216,12 @@ REDUCTION_FAMILIES = {
 }
 # families whose step also runs an elementwise kernel on ew_grid(n // 2) (the Lanczos second pass has none)
 ELEMENTWISE_FAMILIES = {k: REDUCTION_FAMILIES[k] for k in ("pcg", "bicgstab", "lsqr", "minres", "gmres", "cg_trio")}
+ELEMENTWISE_FAMILIES["amg_smooth"] = AMG_SMOOTH_ALONE             # no reduction: elementwise only, on a grid of its own
+ELEMENTWISE_REGIME_OF = {"amg_smooth": amg_smooth_regime}         # every other family launches on ew_grid(n // 2)
+
+
+def elementwise_regime_of(family):
+    return ELEMENTWISE_REGIME_OF.get(family, elementwise_regime)
 
 # ---- the scan, the partial sums and the digest -----------------------------------------------------------------------------------
 # windows of hpcla_compress_columns: 256 blocks (one trip of phase 2), 257 (a second trip with one live lane), 601 (a ragged

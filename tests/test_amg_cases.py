@@ -194,3 +194,111 @@ def test_c_entries_refuse_bad_arguments_without_a_gpu(hp):
     assert hp._capi.last_error() == "amg_smooth: negative size"
     assert lib.hpcla_amg_strength_count_f64_i32(None, None, None, None, 4, 4, 0, 1.0, None, None, None, None) != 0
     assert hp._capi.last_error() == "amg_strength_count: theta must lie in [0, 1)"
+
+
+# ---- the helpers that feed the kernels one block at a time -----------------------------------------------------------------------
+def test_split_block_maps_back_to_the_rows_of_A(matrices):
+    """Through (lo, ghosts) the split columns give the block's rows of A exactly, in every (case, blocks) pair, index type and
+    base; ghosts below lo stand in front of the owned columns."""
+    front = 0
+    for name, A in matrices.items():
+        n = A.shape[0]
+        for k in ac.BLOCKS:
+            part = ac.equal_blocks(n, k)
+            for j in range(k):
+                lo, hi = part[j], part[j + 1]
+                for base, Ti in ((0, np.int32), (1, np.int64)):
+                    rowptr, split, vals, n_own, ghosts = ac.split_block(A, part, j, base, Ti)
+                    assert rowptr.dtype == split.dtype == Ti and n_own == hi - lo and len(rowptr) == n_own + 1, (name, k, j)
+                    assert np.array_equal(rowptr - base, A.indptr[lo:hi + 1] - A.indptr[lo]), (name, k, j)
+                    c = split.astype(np.int64) - base
+                    assert np.all(np.diff(ghosts) > 0) and not np.any((ghosts >= lo) & (ghosts < hi)), (name, k, j)
+                    assert c.size == 0 or (c.min() >= 0 and c.max() < n_own + len(ghosts)), (name, k, j)
+                    back = np.where(c < n_own, c + lo, ghosts[np.maximum(c - n_own, 0)] if len(ghosts) else -1)
+                    a, b = A.indptr[lo], A.indptr[hi]
+                    assert np.array_equal(back, A.indices[a:b]) and np.array_equal(ac.bits(vals), ac.bits(A.data[a:b])), (name, k, j)
+                    assert len(ghosts) == 0 or set(ghosts) == set(A.indices[a:b]) - set(range(lo, hi)), (name, k, j)
+                    first = c[(rowptr[:-1] - base)[np.diff(rowptr) > 0]]
+                    front += int(np.sum(first >= n_own))
+    assert front > 1000                                            # rows that open with a ghost
+
+
+def test_weights_in_stored_order_lie_within_the_pairwise_ones(matrices, hierarchies):
+    worst, longest = 0.0, 0
+    for (name, k), levels in hierarchies.items():
+        for lvl in levels:
+            A = lvl["A"]
+            d, ratio = ac.weights_stored_order(A)
+            assert np.array_equal(ac.bits(d), ac.bits(A.diagonal())), (name, k)
+            rho = float(ratio.max())
+            worst = max(worst, abs(rho - lvl["rho"]) / lvl["rho"])
+            pairwise = np.asarray(abs(A).sum(axis=1)).ravel() / d
+            worst = max(worst, float(np.max(np.abs(ratio - pairwise) / pairwise)))
+            longest = max(longest, int(np.diff(A.indptr).max()))
+    print(f"stored order against pairwise: {worst:.2e} over rows of up to {longest} entries")
+    assert worst <= 1e-13
+    hub = matrices["star300"]                                      # a plain loop over the longest row of the fine cases
+    total = 0.0
+    for v in hub.data[hub.indptr[0]:hub.indptr[1]]:
+        total = total + abs(v)
+    assert ac.weights_stored_order(hub)[1][0] == total / hub[0, 0]
+    # what the bit comparison on the device can tell apart: the same rows summed by 8 lanes (lane l takes entries l, l + 8, ...)
+    # and combined pairwise differ from the stored order in a bit on some row of the random case's levels
+    differ = rows = 0
+    for lvl in hierarchies["random600", 8]:
+        A = lvl["A"]
+        d, ratio = ac.weights_stored_order(A)
+        for i in range(A.shape[0]):
+            v = np.abs(A.data[A.indptr[i]:A.indptr[i + 1]])
+            lanes = [float(np.cumsum(v[l::8])[-1]) if len(v) > l else 0.0 for l in range(8)]
+            while len(lanes) > 1:
+                lanes = [a + b for a, b in zip(lanes[::2], lanes[1::2])]
+            differ += int(lanes[0] / d[i] != ratio[i])
+            rows += 1
+    print(f"a lane-parallel sum differs from the stored order on {differ} of {rows} rows")
+    assert differ >= 10
+
+
+def test_mis2_states_end_in_the_roots_of_the_block(hierarchies):
+    seen = 0
+    for (name, k), levels in hierarchies.items():
+        for lvl in levels:
+            if "agg" not in lvl:
+                continue
+            part = lvl["partition"]
+            indptr, indices = lvl["graph"]
+            key, _ = ac.keys_of(part)
+            for j in range(len(part) - 1):
+                lo, hi = part[j], part[j + 1]
+                ptr = indptr[lo:hi + 1] - indptr[lo]
+                cols = indices[indptr[lo]:indptr[hi]] - lo
+                assert cols.size == 0 or (cols.min() >= 0 and cols.max() < hi - lo), (name, k, j)
+                states = list(ac.mis2_states(ptr, cols, key[lo:hi]))
+                assert (1 if hi > lo else 0) <= len(states) <= lvl["rounds"], (name, k, j, len(states))
+                if states:
+                    assert np.array_equal(states[-1] == ac.ROOT, lvl["roots"][lo:hi]), (name, k, j)
+                    assert np.all((states[-1] == ac.ROOT) | (states[-1] == -1)), (name, k, j)
+                    assert all(np.any((s >= 0) & (s < ac.ROOT)) for s in states[:-1]), (name, k, j)
+                seen += 1
+    assert seen >= 300
+
+
+def test_compressed_columns_are_shuffled_and_map_back(hierarchies):
+    rng = np.random.default_rng(3)
+    lvl = hierarchies["grid37x53", 3][0]
+    cols = lvl["P"].indices[lvl["P"].indptr[100]:lvl["P"].indptr[900]]
+    local, col_indices = ac.compressed_columns(cols, rng)
+    assert np.array_equal(col_indices[local], cols) and np.array_equal(np.sort(col_indices), np.unique(cols))
+    assert np.any(np.diff(col_indices) < 0) and local.min() == 0 and local.max() == len(col_indices) - 1
+    one, ids = ac.compressed_columns(np.array([5, 5, 5]), rng)
+    assert np.array_equal(one, [0, 0, 0]) and np.array_equal(ids, [5])
+
+
+def test_the_levels_the_kernel_tests_walk_have_the_edges_they_name(matrices):
+    """tests/test_gpu_precond_kernels.py asserts the same on what it ran; here without a device, so that a changed generator
+    fails in the CPU suite first."""
+    stats = ac.chain_coverage(ac.chain_levels(matrices))
+    print(stats)
+    assert stats["levels"] >= 120 and stats["one_row_blocks"] >= 1 and stats["stored_zeros"] >= 1 and stats["isolated"] >= 1
+    assert stats["chains"] >= 400 and stats["ghost_entries"] >= 75_000
+    assert stats["longest_row"] >= 128                             # of A T: sixteen trips of the prolongator's 8-lane loop

@@ -175,3 +175,50 @@ def test_blocked_G_ignores_the_columns_of_other_blocks(orc):
     # an empty block is legal
     gp0, _, _ = fc.fsai_blocks(rowptr, colidx, vals, [0, 100, 100, 256])
     assert gp0[-1] == len(fc.fsai_blocks(rowptr, colidx, vals, [0, 100, 256])[1])
+
+
+# ---- the hand-built inputs of the kernel tests --------------------------------------------------------------------------------
+def test_three_faults_fail_in_row_order_and_heal_one_at_a_time():
+    """The restatement walks the rows in order, so it names the smallest faulty row, as the device's error word must."""
+    want = [(fc.NotPositiveDefinite, 40), (fc.NoDiagonal, 300), (fc.NotPositiveDefinite, 520)]
+    assert tuple(r for _, r in want) == fc.FAULT_ROWS
+    for heal, (exc, row) in enumerate(want):
+        rowptr, colidx, vals = fc.three_faults(heal)
+        assert len(rowptr) == 601 and rowptr[-1] == len(colidx) == len(vals)
+        with pytest.raises(exc) as e:
+            fc.fsai_cholesky(rowptr, colidx, vals)
+        assert e.value.row == row, (heal, e.value.row)
+    rowptr, colidx, vals = fc.three_faults(3)
+    clean = fc.banded(3, 600)
+    assert all(np.array_equal(a, b) for a, b in zip((rowptr, colidx, vals), clean))
+    fc.fsai_cholesky(rowptr, colidx, vals)
+    r, c, v = fc.three_faults(2)                                   # the last fault is a POSITIVE diagonal: only the pivot fails
+    assert v[r[520] + np.flatnonzero(c[r[520]:r[521]] == 520)[0]] > 0
+
+
+def test_pattern_is_not_a_has_the_three_kinds_of_entry_and_thins_to_the_same_G():
+    import tests._amg_cases as ac
+    A, P, Pthin, part, j = fc.pattern_is_not_a()
+    lo, hi = part[j], part[j + 1]
+    assert hi - lo == 40
+    above = ghosts_in_front = unstored = outside = no_diag = 0
+    for i in range(lo, hi):
+        prow = P.indices[P.indptr[i]:P.indptr[i + 1]]
+        arow = A.indices[A.indptr[i]:A.indptr[i + 1]]
+        above += int(np.sum(prow > i))
+        ghosts_in_front += int(prow[0] < lo)
+        unstored += len(set(prow[(prow >= lo) & (prow < i)]) - set(arow))
+        outside += len(set(arow[(arow >= lo) & (arow < i)]) - set(prow))
+        no_diag += int(i not in prow)
+    assert min(above, ghosts_in_front, unstored, outside, no_diag) >= 10
+    _, split, _, n_own, _ = ac.split_block(P, part, j)
+    rowptr = P.indptr[lo:hi + 1] - P.indptr[lo]
+    assert np.sum(split[rowptr[:-1]] >= n_own) == ghosts_in_front    # in split form too the row opens with the ghost
+    cut = lambda M: (M.indptr[lo:hi + 1] - M.indptr[lo], M.indices[M.indptr[lo]:M.indptr[hi]])
+    rows = (*cut(A), A.data[A.indptr[lo]:A.indptr[hi]])
+    full = fc.fsai_cholesky(*rows, row_start=lo, pattern=cut(P))
+    thin = fc.fsai_cholesky(*rows, row_start=lo, pattern=cut(Pthin))
+    own = fc.fsai_cholesky(*rows, row_start=lo)
+    assert all(np.array_equal(a, b) for a, b in zip(full[:2], thin[:2])) and np.array_equal(pc.bits(full[2]), pc.bits(thin[2]))
+    assert not np.array_equal(full[0], own[0])                      # and it is not the G of A's own pattern
+    assert Pthin.nnz < P.nnz

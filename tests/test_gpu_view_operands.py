@@ -905,3 +905,82 @@ def test_lobpcg_with_a_start_block_view_and_weight_view(hp, orc, backends, combo
     _same_info(info, info_f, "lobpcg")                           # iterations, status, residual_norms, history, anorm
     assert len(info.history) == info.iterations and info.anorm > 0
     hp.clear_plan_cache()
+
+
+# ---- 9. the preconditioner objects: apply and cg with M = hp.fsai(A) / hp.amg(A) -------------------------------------------------------
+PRECONDITIONERS = ("fsai", "amg")
+
+
+def _preconditioner(hp, kind, A):
+    """hp.amg at coarse_size = 8: 256 -> 37 -> 4 rows on the 16 x 16 case, so the cycle runs both smoother kernels on two levels
+    and the dense last level."""
+    return hp.fsai(A) if kind == "fsai" else hp.amg(A, coarse_size=8)
+
+
+@pytest.mark.parametrize("kind", PRECONDITIONERS)
+@pytest.mark.parametrize("combo", vo.combos(vo.VECTOR_F64, vo.VECTOR_F64), ids=_ids)
+def test_preconditioner_apply_on_views(hp, backends, spd, kind, combo):
+    """``M.apply(r, out=out)``, positions (r, out): out holds the bits of the all-fresh call in the caller's buffer, r and the
+    poison around both are untouched, and the call returns ``out`` itself."""
+    B = backends["i32"]
+    A = _csr_matrix(hp, B, *spd["csr"])
+    M = _preconditioner(hp, kind, A)
+    n = len(spd["b"])
+    rg = _values(n, F64, 61)
+    want = M.apply(_hvec(hp, B, Placed(rg, "fresh"))).local_values().copy()
+    assert np.isfinite(want).all() and want.any()
+    pr, po = Placed(rg, combo[0]), Placed(np.full(n, 7.0), combo[1])
+    out = _hvec(hp, B, po)
+    assert M.apply(_hvec(hp, B, pr), out=out) is out
+    pr.unchanged()
+    po.holds(want)
+    hp.clear_plan_cache()
+
+
+@pytest.mark.parametrize("kind", PRECONDITIONERS)
+@pytest.mark.parametrize("combo", vo.combos(vo.VECTOR_F64, vo.VECTOR_F64), ids=_ids)
+def test_cg_with_a_preconditioner_object_and_view_operands(hp, backends, spd, kind, combo):
+    """hp.cg(A, b, x0=..., M=hp.fsai(A) or hp.amg(A)), positions (b, x0)."""
+    B = backends["i32"]
+    A = _csr_matrix(hp, B, *spd["csr"])
+    M = _preconditioner(hp, kind, A)
+    x0g = np.full(len(spd["b"]), 1e-3)
+    _linear_solve(hp, B, hp.cg, A, spd["dense"], spd["b"], x0g, None, combo + ("fresh",), _rel_to(spd["b"]), rtol=1e-8, M=M)
+    hp.clear_plan_cache()
+
+
+def test_preconditioners_of_a_matrix_built_on_a_value_view(hp, backends, spd):
+    """``HPCSparseMatrix_local_device`` keeps the caller's value tensor as it is: A on an ``nzval`` 8 bytes off a 16-byte boundary.
+    Every level of hp.amg(A) and the G of hp.fsai(A) have the bits of the build on fresh storage; the values and the poison
+    around them are untouched."""
+    import torch
+    B = backends["i32"]
+    rowptr, colidx, vals = spd["csr"]
+    n = len(rowptr) - 1
+    built = {}
+    for variant in ("off8", "fresh"):
+        pv = Placed(np.asarray(vals, dtype=np.float64), variant)
+        A = hp.HPCSparseMatrix_local_device(torch.from_numpy(np.array(rowptr, dtype=np.int64)).cuda(),
+                                            torch.from_numpy(np.array(colidx, dtype=np.int64)).cuda(), pv.t, n, B)
+        assert A.nzval.data_ptr() == pv.t.data_ptr() and A.nzval.data_ptr() % 16 == pv.promise[0], variant
+        M, F = hp.amg(A, coarse_size=8), hp.fsai(A)
+        pv.unchanged()
+        built[variant] = (M, F)
+    (M, F), (Mf, Ff) = built["off8"], built["fresh"]
+    assert [l.n for l in M.levels] == [l.n for l in Mf.levels] and len(M.levels) >= 3
+    host = lambda t: t.cpu().numpy()
+    for k, (a, b) in enumerate(zip(M.levels, Mf.levels)):
+        _same_bits(host(a.A.nzval), host(b.A.nzval), f"level {k} A")
+        _same_bits(a.s.local_values(), b.s.local_values(), f"level {k} s")
+        assert (a.w, a.rho, a.n_roots, a.rounds) == (b.w, b.rho, b.n_roots, b.rounds), k
+        assert (a.P is None) == (b.P is None) and (a.inverse is None) == (b.inverse is None), k
+        if a.P is not None:
+            assert np.array_equal(host(a.aggregates), host(b.aggregates)), k
+            _same_bits(host(a.P.nzval), host(b.P.nzval), f"level {k} P")
+            _same_bits(host(a.Pt.nzval), host(b.Pt.nzval), f"level {k} Pt")
+        if a.inverse is not None:
+            _same_bits(a.inverse.local_values(), b.inverse.local_values(), f"level {k} inverse")
+    assert np.array_equal(host(F.G.rowptr_target), host(Ff.G.rowptr_target)) and F.max_row == Ff.max_row
+    _same_bits(host(F.G.nzval), host(Ff.G.nzval), "G")
+    _same_bits(host(F.Gt.nzval), host(Ff.Gt.nzval), "Gt")
+    hp.clear_plan_cache()

@@ -39,8 +39,21 @@ def test_every_reduction_family_reaches_every_regime_with_a_tail(family):
 @pytest.mark.parametrize("family", sorted(gr.ELEMENTWISE_FAMILIES))
 def test_every_elementwise_family_reaches_every_regime(family):
     sizes = gr.ELEMENTWISE_FAMILIES[family]
-    seen = {gr.elementwise_regime(n) for n in sizes}
+    regime = gr.elementwise_regime_of(family)
+    seen = {regime(n) for n in sizes}
     assert set(gr.ELEMENTWISE_REGIMES) <= seen, (family, sorted(set(gr.ELEMENTWISE_REGIMES) - seen))
+    assert any(regime(n) == "E3" and n & 1 for n in sizes), f"{family}: no odd size (scalar tail) on the capped grid"
+
+
+def test_the_smoother_kernels_grid_at_the_documented_sizes():
+    """amg_smooth_kernel's own grid, read from csrc/amg.hip: the figures tests/test_gpu_precond_kernels.py quotes."""
+    assert (gr.AMG_SMOOTH_WIDTH, gr.AMG_SMOOTH_T, gr.AMG_SMOOTH_CAP) == (2, 256, 4096)
+    assert [gr.amg_smooth_grid(n) for n in gr.AMG_SMOOTH_ALONE] == [1, 1, 1, 1, 5, 1201, 4096]
+    assert [gr.amg_smooth_regime(n) for n in gr.AMG_SMOOTH_ALONE] == ["E1"] * 4 + ["E2"] * 2 + ["E3"]
+    assert gr.elementwise_regime_of("amg_smooth") is gr.amg_smooth_regime and gr.elementwise_regime_of("pcg") is gr.elementwise_regime
+    n2 = gr.R4_N // 2                                                       # 2 097 153 double2: two full trips and lane 0's third
+    assert n2 == 2 * gr.AMG_SMOOTH_CAP * gr.AMG_SMOOTH_T + 1 and gr.R4_N & 1
+    assert gr.amg_smooth_regime(2 * gr.AMG_SMOOTH_CAP * gr.AMG_SMOOTH_T) is None      # the cap reached, no further trip
 
 
 def test_float32_reductions_reach_every_regime_with_a_tail():
