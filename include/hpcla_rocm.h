@@ -1089,6 +1089,61 @@ int hpcla_amg_prolongator_f64_i64(const int64_t *at_rowptr, const int64_t *at_co
                                   int index_base, double *p_nzval, void *stream);
 int hpcla_amg_presmooth_f64(const double *s_dev, const double *b, double *x, int64_t n, void *stream);
 int hpcla_amg_postsmooth_f64(const double *s_dev, const double *b, const double *t, double *x, int64_t n, void *stream);
+/* ---- fine-grained ILU(0) (hp.ilu0, csrc/ilu.hip): Chow-Patel sweeps for the factors, truncated Jacobi sweeps in place of the
+ * two triangular solves, as the preconditioner of the GMRES and BiCGStab solvers below (no reference counterpart: the
+ * reference's only solver is MUMPS on the host, and it has no preconditioner).  Rows and columns of A are partitioned alike
+ * (n_own == nrows < 2^31 - 1), so a split column < n_own is the local row it names; columns >= n_own are ghosts and are dropped:
+ * the factors couple a rank's own rows only.  The owned block is a CSR of its own with Int32 indices (fewer than 2^31 entries):
+ * b_rowptr_dev (nrows + 1, 0-based), b_cols_dev (local columns, ascending within a row whatever A's order), b_rows_dev (the row
+ * of every entry), b_diag_dev (the position of a row's diagonal, -1 when none is stored), b_map_dev (the entry's 0-based
+ * position in A's nzval).  c_ptr_dev (nrows + 1) / c_pos_dev: the entries of column j as positions into the block, ascending
+ * row -- a stable sort of the positions by column, left to the caller.  f: one value per block entry, l_ij for i > j (unit
+ * diagonal not stored), u_ij for i <= j.
+ *   ilu_work_bytes  device bytes of `work` for the count.
+ *   ilu_count       b_rowptr_dev.  info_dev[0] = the block's entries, info_dev[1] = the error word, reset here: all ones, or
+ *                   (local row << 2) | code of the smallest failing row -- 1: the row stores no diagonal, 2: its diagonal is zero
+ *                   or NaN, 3: its pivot u_ii is zero, NaN or infinite.
+ *   ilu_fill        the other index arrays (an entry's place in its row: the number of owned entries with a smaller column;
+ *                   quadratic in the row's length, no scratch); lowers the error word with codes 1 and 2.
+ *   ilu_gather      a_vals_dev[p] = a_nzval[b_map_dev[p]]: the block's values, also new values for an unchanged structure.
+ *   ilu_init        f = the initial guess: l_ij = a_ij / a_jj, u_ij = a_ij.
+ *   ilu_sweep       one lane per entry: s = a_ij - sum_{k < min(i, j), (i, k) and (k, j) stored} l_ik * u_kj from f_old_dev in
+ *                   ascending k, multiply and subtract separately rounded; f_new_dev = s / u_jj (f_old_dev's) for i > j, s
+ *                   otherwise.  Two buffers; rows of any length; no atomics.  A row without a diagonal yields NaN.
+ *   ilu_pivots      dinv_dev[i] = 1 / u_ii; lowers the error word with code 3.
+ *   ilu_trisweep    out_i = (rhs_i - sum_p f_p * in[col_p]) [* dinv_i] over the part of row i below (upper == 0) or above
+ *                   (upper != 0) its diagonal, in one kernel.  lanes = 1: one lane per row, a running subtraction in stored
+ *                   order; 2, 4, 8: a lane group per row, partial sums joined by shuffles, subtracted once.  in == NULL: the
+ *                   sum is empty; dinv_dev == NULL: no scaling.  in and out are two buffers.  No alignment is asked for.
+ *   ilu_apply       out = N_U(N_L(r)) in 2 solve_sweeps + 1 trisweep launches: y_0 = r, y_{m+1} = r - L y_m;  z_0 = dinv .* y,
+ *                   z_{m+1} = dinv .* (y - U z_m), solve_sweeps (1..16) times each.  t0, t1: scratch of nrows doubles; r, t0,
+ *                   t1 and out are distinct.
+ * All only enqueue (vector atomic min on info_dev, no waiting); every result is fixed by the inputs. */
+int64_t hpcla_ilu_work_bytes(int64_t nrows);
+int hpcla_ilu_count_f64_i32(const int32_t *a_rowptr, const int32_t *a_colval_split, int64_t nrows, int64_t n_own,
+                            int index_base, int32_t *b_rowptr_dev, int64_t *info_dev, void *work, void *stream);
+int hpcla_ilu_count_f64_i64(const int64_t *a_rowptr, const int64_t *a_colval_split, int64_t nrows, int64_t n_own,
+                            int index_base, int32_t *b_rowptr_dev, int64_t *info_dev, void *work, void *stream);
+int hpcla_ilu_fill_f64_i32(const int32_t *a_rowptr, const int32_t *a_colval_split, const double *a_nzval, int64_t nrows,
+                           int64_t n_own, int index_base, const int32_t *b_rowptr_dev, int32_t *b_cols_dev,
+                           int32_t *b_rows_dev, int32_t *b_diag_dev, int64_t *b_map_dev, int64_t *info_dev, void *stream);
+int hpcla_ilu_fill_f64_i64(const int64_t *a_rowptr, const int64_t *a_colval_split, const double *a_nzval, int64_t nrows,
+                           int64_t n_own, int index_base, const int32_t *b_rowptr_dev, int32_t *b_cols_dev,
+                           int32_t *b_rows_dev, int32_t *b_diag_dev, int64_t *b_map_dev, int64_t *info_dev, void *stream);
+int hpcla_ilu_gather_f64(const double *a_nzval, const int64_t *b_map_dev, int64_t nnz, double *a_vals_dev, void *stream);
+int hpcla_ilu_init_f64(const int32_t *b_cols_dev, const int32_t *b_rows_dev, const int32_t *b_diag_dev,
+                       const double *a_vals_dev, int64_t nnz, double *f_dev, void *stream);
+int hpcla_ilu_sweep_f64(const int32_t *b_rowptr_dev, const int32_t *b_cols_dev, const int32_t *b_rows_dev,
+                        const int32_t *b_diag_dev, const int32_t *c_ptr_dev, const int32_t *c_pos_dev,
+                        const double *a_vals_dev, const double *f_old_dev, double *f_new_dev, int64_t nnz, void *stream);
+int hpcla_ilu_pivots_f64(const int32_t *b_diag_dev, const double *f_dev, int64_t nrows, double *dinv_dev, int64_t *info_dev,
+                         void *stream);
+int hpcla_ilu_trisweep_f64(const int32_t *b_rowptr_dev, const int32_t *b_cols_dev, const int32_t *b_diag_dev,
+                           const double *f_dev, const double *rhs, const double *in, const double *dinv_dev, double *out,
+                           int64_t nrows, int upper, int lanes, void *stream);
+int hpcla_ilu_apply_f64(const int32_t *b_rowptr_dev, const int32_t *b_cols_dev, const int32_t *b_diag_dev, const double *f_dev,
+                        const double *dinv_dev, const double *r, double *t0, double *t1, double *out, int64_t nrows,
+                        int solve_sweeps, int lanes, void *stream);
 /* ---- BiCGStab for nonsymmetric A: gated steps of right-preconditioned BiCGStab, K = identity or dinv .* (no reference
  * counterpart: the reference solves a general A \ b through MUMPS on the host; a caller of its operators composes the
  * method from A*p, src/sparse.jl:2096-2128, dot, src/vectors.jl:798-812, and the broadcasts, src/vectors.jl:1203-1226).

@@ -16,6 +16,9 @@ Layout
   amg.py             amg(): the smoothed-aggregation multigrid preconditioner of an SPD A for cg(M=...): aggregation by a distance-2
                      independent set on the device (csrc/amg.hip), the hierarchy through spgemm and transpose, a symmetric
                      V(1,1) cycle on ordinary SpMVs; aggregates never cross ranks
+  ilu.py             ilu0(): the fine-grained ILU(0) preconditioner of a nonsymmetric A for gmres(M=...) and bicgstab(M=...):
+                     Chow-Patel sweeps build the factors, truncated Jacobi sweeps stand for the triangular solves (csrc/ilu.hip);
+                     rank-local couplings, no fill, no kernel that waits
   bicgstab.py        bicgstab(): BiCGStab for nonsymmetric A, the same device-side stop (csrc/vecops.hip, bicg_* kernels)
   gmres.py           gmres(): restarted GMRES(m), fused twice-applied Gram-Schmidt, the same device-side stop (gmres_* kernels)
   lsqr.py            lsqr(): least squares for rectangular A on A and its materialised transpose, damped form, two stop rules
@@ -58,6 +61,7 @@ from .matmat import clear_matrix_plan_cache, get_matrix_plan, spgemm
 from .cg import CGGraphPair, CGInfo, CGWorkspace, PCGWorkspace, cg, cg_fixed_iterations, cg_iterate, cg_setup
 from .fsai import FSAI, fsai
 from .amg import AMG, AMGLevel, AMGWorkspace, amg
+from .ilu import ILU0, ilu0
 from .bicgstab import BiCGStabWorkspace, bicgstab
 from .gmres import GMRESWorkspace, gmres
 from .lsqr import LSQRInfo, LSQRWorkspace, lsqr

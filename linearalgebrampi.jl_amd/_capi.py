@@ -163,6 +163,18 @@ _SIGNATURES = {
     "hpcla_fsai_count_f64_i64": [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp],
     "hpcla_fsai_factor_f64_i32": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp],
     "hpcla_fsai_factor_f64_i64": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp],
+    # fine-grained ILU(0) (hp.ilu0, csrc/ilu.hip): the owned block's CSR, the factor sweeps, the triangular sweeps of an application
+    "hpcla_ilu_work_bytes": [_i64],
+    "hpcla_ilu_count_f64_i32": [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp],
+    "hpcla_ilu_count_f64_i64": [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp],
+    "hpcla_ilu_fill_f64_i32": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "hpcla_ilu_fill_f64_i64": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "hpcla_ilu_gather_f64": [_vp, _vp, _i64, _vp, _vp],
+    "hpcla_ilu_init_f64": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
+    "hpcla_ilu_sweep_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    "hpcla_ilu_pivots_f64": [_vp, _vp, _i64, _vp, _vp, _vp],
+    "hpcla_ilu_trisweep_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
+    "hpcla_ilu_apply_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
     "hpcla_pcg_fsai_iterations_f64_i32": [_vp,
                                           _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
                                           _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
@@ -383,6 +395,7 @@ _RESTYPES = {
     "hpcla_cols16_padded_len": _i64,
     "hpcla_pcg_work_bytes": _i64,
     "hpcla_fsai_work_bytes": _i64,
+    "hpcla_ilu_work_bytes": _i64,
     "hpcla_amg_work_bytes": _i64,
     "hpcla_amg_round_blocks": _i64,
     "hpcla_bicgstab_work_bytes": _i64,

@@ -6,7 +6,8 @@ host read-backs and about 13 launches per BiCGStab iteration.  Here an iteration
 (csrc/vecops.hip, ``hpcla_bicgstab_iterations_f64_*``) whose scalars, stop rule and breakdown tests stay on the device; the
 host enqueues ``check_every`` iterations per library call and reads 16 bytes of state per chunk, exactly as ``hp.cg`` does.
 
-Right-preconditioned, ``K`` = identity or ``dinv .*``; gate order and rounding order (tests/_bicgstab_cases.py restates them):
+Right-preconditioned, ``K`` = identity, ``dinv .*`` or the operator of ``hp.ilu0`` (ilu.py; the same steps with ``dinv == NULL``,
+enqueued one by one from here with ``K`` applied between them); gate order and rounding order (tests/_bicgstab_cases.py restates them):
 
     setup  x = x0 or 0;  r = b - A x;  rhat = r;  p = r;  rho = rhat.r;  hist[0] = r.r;  thr = max(rtol |b|, atol)^2
     j      ph = K p;  v = A ph;  rv = rhat.v                      gate A  !(rho != 0 and rv != 0): breakdown at j - 1
@@ -22,6 +23,8 @@ from __future__ import annotations
 
 import math
 from typing import Optional, Tuple
+
+import numpy as np
 
 from . import _capi
 from .cg import CGInfo, _PairHistory, _residual_norms, _run_chunks, _solver_arguments, _stop_rule_or_done
@@ -77,9 +80,21 @@ def _bicgstab_dinv(A, b: HPCVector, M, name: str = "bicgstab") -> Optional[HPCVe
             raise ValueError(f"{name}: M='jacobi' needs a diagonal without zeros (minimum(abs(diag(A))) > 0)")
         return dinv
     if not isinstance(M, HPCVector):
-        raise ValueError(f"{name}: M must be None, 'jacobi' or an HPCVector on A's row partition")
+        raise ValueError(f"{name}: M must be None, 'jacobi', an HPCVector on A's row partition or an ILU0 (hp.ilu0(A))")
     b._same_partition(M)
     return rd16_vector(M)                                        # the step kernels read it 16 bytes at a time
+
+
+def _ilu_operator(A, M, name: str):
+    """M when it is the operator of ``hp.ilu0`` (ilu.py is looked at only for an M that is nothing else), checked against A."""
+    if M is None or isinstance(M, (str, HPCVector)):
+        return None
+    from .ilu import ILU0
+    if not isinstance(M, ILU0):
+        return None
+    if not np.array_equal(M.row_partition, A.row_partition) or M.shape != tuple(int(v) for v in A.shape):
+        raise ValueError(f"{name}: the ILU0 preconditioner was built for a matrix of another shape or partition")
+    return M
 
 
 def bicgstab(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, atol: float = 0.0,
@@ -90,8 +105,10 @@ def bicgstab(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8
     Stops at the first iteration with ``||r_k|| <= max(rtol * ||b||, atol)`` (``hp.cg``'s rule; also tested on the half-step
     residual ``s_k``), after ``maxiter`` iterations (default ``10 n``), or on a breakdown (``rhat.v``, ``rho``, ``t.t`` or
     ``t.s`` zero or NaN).  ``M``: ``None``, ``"jacobi"`` (``1 ./ diag(A)``, formed on the device; no diagonal entry may be
-    zero) or an HPCVector holding the inverse diagonal to apply.  ``x0`` defaults to zero.  Returns ``(x, CGInfo)``; x is the
-    workspace's vector, ``residual_norms[j]`` is ``||r_j||`` (``||s_j||`` for a half-step stop) of the recurrence.
+    zero), an HPCVector holding the inverse diagonal to apply, or the ``ILU0`` object of ``hp.ilu0(A)`` (``ph = M p``,
+    ``sh = M s``: its triangular sweeps, enqueued from here between the gated steps).  ``x0`` defaults to zero.  Returns
+    ``(x, CGInfo)``; x is the workspace's vector, ``residual_norms[j]`` is ``||r_j||`` (``||s_j||`` for a half-step stop) of the
+    recurrence.
 
     Every test runs on the device.  The host enqueues ``check_every`` iterations in one library call and then reads the
     16-byte state (the only synchronisation); iterations enqueued behind the one that decided are no-ops, so the answer does
@@ -101,7 +118,8 @@ def bicgstab(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8
     plan = get_vector_plan(A, ws.p)
     if plan.result_partition_hash != ws.p.structural_hash:
         raise ValueError("bicgstab: b must be partitioned like the rows of A")
-    dinv = _bicgstab_dinv(A, b, M)
+    op = _ilu_operator(A, M, "bicgstab")
+    dinv = None if op is not None else _bicgstab_dinv(A, b, M)
 
     # -- setup: r0 = b - A x0, rhat = p0 = r0, ph0 = dinv p0, pair 0, the state ------------------------------------------
     ws.hist.zero_()
@@ -121,7 +139,11 @@ def bicgstab(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8
     norm(ws.r, 2, out=ws.hist[0:1])
     ws.hist[1:2].copy_(ws.hist[0:1])                             # rho_0 = rhat.r = r.r
     one = ws.tmp[1:2]
-    if dinv is None:
+    if op is not None:                                           # p = r, ph = M p
+        ws.with_preconditioner()
+        ws.p.v.copy_(ws.r.v)
+        op.apply(ws.p, out=ws.ph)
+    elif dinv is None:
         ws.p.v.copy_(ws.r.v)
     else:                                                        # p = r + 1 * (0 - 1 * 0), ph = dinv p through the step-7 kernel
         ws.with_preconditioner()
@@ -144,6 +166,27 @@ def bicgstab(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8
                    pre[0], dptr(ws.v.v), dptr(ws.s.v), pre[1], dptr(ws.t.v), dptr(ws.hist), dptr(ws.scal), dptr(ws.work),
                    first, count, current_stream_ptr())
 
-    iterations, status = _run_chunks(ws, A.backend, maxiter, check_every, enqueue)
+    def enqueue_operator(first, count):
+        """The order of hpcla_bicgstab_iterations_*, enqueued from here through the exported gated entries with dinv == NULL;
+        each ``dinv .*`` is ``op.apply`` (not gated: behind the deciding iteration s and p are frozen and the sweeps rewrite
+        sh, ph and their own scratch with what they held)."""
+        n, s, comm = ws.x.local_length, current_stream_ptr(), A.backend.rccl
+        rv, triple = dptr(ws.scal), dptr(ws.scal[1:])
+        state = dptr(ws.state)
+        for j in range(first, first + count):
+            rho, cur = dptr(ws.hist[2 * j - 1:]), dptr(ws.hist[2 * j:])
+            mul_(ws.v, A, ws.ph)
+            _capi.call("hpcla_bicg_dot_f64", comm, dptr(ws.rhat.v), dptr(ws.v.v), n, j, rho, state, rv, dptr(ws.work), s)
+            _capi.call("hpcla_bicg_s_f64", rho, rv, dptr(ws.r.v), dptr(ws.v.v), None, dptr(ws.s.v), None, n, j, state, s)
+            op.apply(ws.s, out=ws.sh)
+            mul_(ws.t, A, ws.sh)
+            _capi.call("hpcla_bicg_tts_f64", comm, dptr(ws.t.v), dptr(ws.s.v), n, j, state, triple, dptr(ws.work), s)
+            _capi.call("hpcla_bicg_xr_f64", comm, rho, rv, triple, dptr(ws.ph.v), dptr(ws.sh.v), dptr(ws.s.v), dptr(ws.t.v),
+                       dptr(ws.rhat.v), dptr(ws.x.v), dptr(ws.r.v), n, j, state, cur, dptr(ws.work), s)
+            _capi.call("hpcla_bicg_p_f64", dptr(ws.hist[2 * j + 1:]), rho, rv, triple, dptr(ws.r.v), dptr(ws.v.v), None,
+                       dptr(ws.p.v), None, n, j, state, s)
+            op.apply(ws.p, out=ws.ph)
+
+    iterations, status = _run_chunks(ws, A.backend, maxiter, check_every, enqueue_operator if op is not None else enqueue)
     h = _residual_norms(ws, b.backend, iterations)
     return ws.x, CGInfo(status in (1, 3), iterations, _STATUS[status], h)

@@ -9,7 +9,8 @@ with one read of the basis; ``gmres_update``: the whole running subtraction in o
 stop rule and breakdown test stay on the device; the host enqueues ``check_every`` inner steps per library call
 (``hpcla_gmres_iterations_f64_*``) and reads 16 bytes of state per chunk, exactly as the other two solvers do.
 
-Right-preconditioned, ``K`` = identity or ``dinv .*``; gate order and rounding order (tests/_gmres_cases.py restates them):
+Right-preconditioned, ``K`` = identity, ``dinv .*`` or the operator of ``hp.ilu0`` (ilu.py; ``_gmres_operator`` enqueues the same
+steps with ``dinv == NULL`` one by one and applies ``K`` between them); gate order and rounding order (tests/_gmres_cases.py restates them):
 
     start / restart   w = b - A x (w = b when x is zero);  rr = w.w
                       gate R  rr <= thr: converged at a restart, hist[k] = rr
@@ -28,9 +29,9 @@ from __future__ import annotations
 from typing import Optional, Tuple
 
 from . import _capi
-from .bicgstab import _bicgstab_dinv
+from .bicgstab import _bicgstab_dinv, _ilu_operator
 from .cg import CGInfo, _PairHistory, _residual_norms, _run_chunks, _solver_arguments, _stop_rule_or_done
-from .sparse import get_vector_plan
+from .sparse import get_vector_plan, mul_
 from .vectors import HPCVector, current_stream_ptr, dptr, norm, rd16_vector
 
 _STATUS = {0: "maxiter", 1: "converged", 2: "breakdown", 3: "converged"}     # 3: converged at a restart
@@ -81,6 +82,13 @@ class GMRESWorkspace(_PairHistory):
         if self.z is None:
             self.z = self.x.similar()
 
+    def with_operator(self) -> None:
+        """z, and what ``x = x + K (V y)`` needs when K is an operator (``hp.ilu0``): u = V y, ku = K u, the constant 1."""
+        self.with_preconditioner()
+        if getattr(self, "u", None) is None:
+            self.u, self.ku = self.x.similar(), self.x.similar()
+            self.one = _torch().ones(1, dtype=self.V.dtype, device=self.V.device)
+
     def small_array(self, name: str):
         """A view of one of the small arrays (R, c, s, g, h1, h2, col, y, nn, hn)."""
         lib = _capi.load()
@@ -99,6 +107,82 @@ def _open_columns(status: int, iterations: int, maxiter: int, m: int) -> int:
     return 0                                                     # gate R: x is already updated
 
 
+def _gmres_operator(A, b: HPCVector, x0, rtol: float, atol: float, m: int, maxiter: int, op, check_every: int,
+                    ws: GMRESWorkspace) -> Tuple[HPCVector, CGInfo]:
+    """``gmres`` with ``K = op.apply`` (the ILU0 of ilu.py): the order of hpcla_gmres_iterations_*, enqueued from here through
+    the exported gated entries with dinv == NULL; each ``dinv .*`` is ``op.apply``.  The application is not gated: behind the
+    deciding step its input is frozen and it rewrites z and its own scratch with what they held.  ``x = x + K (V y)`` goes
+    through a scratch vector: u = 0, the gated update adds V y into u, ku = K u, and a gated update of one column adds
+    1 * ku into x -- behind a stop u stays zero and nothing is added."""
+    ws.with_operator()
+    n, ldv, comm = ws.x.local_length, ws.ldv, A.backend.rccl
+    state, small, work = dptr(ws.state), dptr(ws.small), dptr(ws.work)
+    hn, y, h1, h2 = (dptr(ws.small_array(k)) for k in ("hn", "y", "h1", "h2"))
+    one = dptr(ws.one)
+    column = lambda c: ws.V.data_ptr() + 8 * c * ldv
+
+    def apply_to_column(c):
+        if n:
+            op._enqueue(column(c), dptr(ws.z.v))
+
+    def start_cycle(k):                                          # the residual (w holds A x, or 0), gate R, V_0, z = K V_0
+        s = current_stream_ptr()
+        _capi.call("hpcla_gmres_residual_f64", comm, dptr(b.v), dptr(ws.w.v), n, k, m, small, dptr(ws.hist[2 * k:]), state, work, s)
+        _capi.call("hpcla_gmres_next_f64", dptr(ws.w.v), hn, None, column(0), None, n, state, s)
+        apply_to_column(0)
+
+    def add_cycle(ncols, gate):                                  # x = x + K (V y) over ncols columns
+        s = current_stream_ptr()
+        ws.u.v.zero_()
+        _capi.call("hpcla_gmres_xupdate_f64", dptr(ws.V), ldv, ncols, y, None, dptr(ws.u.v), n, gate, s)
+        op.apply(ws.u, out=ws.ku)
+        _capi.call("hpcla_gmres_xupdate_f64", dptr(ws.ku.v), ldv, 1, one, None, dptr(ws.x.v), n, gate, s)
+
+    ws.hist.zero_()
+    ws.small.zero_()
+    ws.work.zero_()                                              # done_iter = 0, status = running, thr = 0
+    ws.V.zero_()
+    if x0 is None:                                               # w = b - 0, not b - A 0
+        ws.x.v.zero_()
+        ws.w.v.zero_()
+    else:
+        b._same_partition(x0)
+        ws.x.v.copy_(x0.v)
+        norm(b, 2, out=ws.tmp[0:1])
+        mul_(ws.w, A, ws.x)
+    start_cycle(0)
+    done = _stop_rule_or_done(ws, b, x0 is not None, rtol, atol, maxiter)
+    if done is not None:
+        return ws.x, done
+
+    def enqueue(first, count):
+        for k in range(first, first + count):
+            s = current_stream_ptr()
+            c = (k - 1) % m + 1
+            mul_(ws.w, A, ws.z)
+            _capi.call("hpcla_gmres_dots_f64", comm, dptr(ws.V), ldv, c, dptr(ws.w.v), n, state, h1, work, s)
+            _capi.call("hpcla_gmres_update_f64", comm, dptr(ws.V), ldv, c, h1, dptr(ws.w.v), n, k, m, None, None, state, work, s)
+            _capi.call("hpcla_gmres_dots_f64", comm, dptr(ws.V), ldv, c, dptr(ws.w.v), n, state, h2, work, s)
+            _capi.call("hpcla_gmres_update_f64", comm, dptr(ws.V), ldv, c, h2, dptr(ws.w.v), n, k, m, small, dptr(ws.hist[2 * k:]),
+                       state, work, s)
+            if c < m:
+                _capi.call("hpcla_gmres_next_f64", dptr(ws.w.v), hn, None, column(c), None, n, state, s)
+                apply_to_column(c)
+                continue
+            _capi.call("hpcla_gmres_solve_f64", c, m, small, state, s)
+            add_cycle(c, state)
+            mul_(ws.w, A, ws.x)
+            start_cycle(k)
+
+    iterations, status = _run_chunks(ws, A.backend, maxiter, check_every, enqueue)
+    open_columns = _open_columns(status, iterations, maxiter, m)
+    if open_columns:
+        _capi.call("hpcla_gmres_solve_f64", open_columns, m, small, None, current_stream_ptr())
+        add_cycle(open_columns, None)
+    h = _residual_norms(ws, b.backend, iterations)
+    return ws.x, CGInfo(status in (1, 3), iterations, _STATUS[status], h)
+
+
 def gmres(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, atol: float = 0.0, restart: int = 30,
           maxiter: Optional[int] = None, M=None, check_every: int = 8,
           workspace: Optional[GMRESWorkspace] = None) -> Tuple[HPCVector, CGInfo]:
@@ -108,7 +192,8 @@ def gmres(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, a
     tested on the true residual at every restart), after ``maxiter`` inner steps (default ``10 n``), or on a breakdown (a
     new Hessenberg column that is zero or NaN: ``A`` is singular on the Krylov space).  ``restart`` is the cycle length, 1..64;
     a cycle keeps ``restart + 1`` basis vectors.  ``M``: ``None``, ``"jacobi"`` (``1 ./ diag(A)``, formed on the device; no
-    diagonal entry may be zero) or an HPCVector holding the inverse diagonal to apply.  ``x0`` defaults to zero.  Returns
+    diagonal entry may be zero), an HPCVector holding the inverse diagonal to apply, or the ``ILU0`` object of ``hp.ilu0(A)``
+    (its triangular sweeps, enqueued from here between the gated steps).  ``x0`` defaults to zero.  Returns
     ``(x, CGInfo)``; x is the workspace's vector.  ``iterations`` counts inner steps: one SpMV each, plus one per restart.
     ``residual_norms[k]`` is the Givens estimate ``|g_{j+1}|`` of ``||r_k||`` after step k -- with the preconditioner on the
     right that is the norm of the true residual ``b - A x_k`` -- and entry 0 is the true ``||b - A x0||``; it never rises.
@@ -128,6 +213,9 @@ def gmres(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, a
     plan = get_vector_plan(A, ws.x)
     if plan.result_partition_hash != ws.x.structural_hash:
         raise ValueError("gmres: b must be partitioned like the rows of A")
+    op = _ilu_operator(A, M, "gmres")
+    if op is not None:
+        return _gmres_operator(A, b, x0, rtol, atol, m, maxiter, op, check_every, ws)
     dinv = _bicgstab_dinv(A, b, M, "gmres")
     if dinv is not None:
         ws.with_preconditioner()
