@@ -1050,6 +1050,14 @@ int hpcla_pcg_fsai_iterations_f64_i64(
  *   amg_aggregate_ids  agg_dev[i] = offset + rootid[owner[i]]: global aggregate ids.
  *   amg_prolongator    p_ic = [c == agg(i)] - s_i * (A T)_ic on the CSR of A T (compressed local columns, their global ids).
  *   amg_presmooth      x = s .* b.      amg_postsmooth  x += s .* (b - t).  16-byte aligned vectors.
+ * For a nonsymmetric A (hp.amg(A, symmetric=False)):
+ *   amg_symmetrise_count / _fill   the graph E u E^T of the strength graph E (s_rowptr_dev, s_cols_dev): indeg_dev (nrows words)
+ *                      = the in-degrees by integer atomics, u_rowptr_dev (nrows + 1) = the scan of out- plus in-degrees,
+ *                      info_dev[0] = its entries; then each row's out-list followed by its in-list (cursor_dev: nrows words of
+ *                      scratch).  The in-list's order is not defined and an edge stored both ways appears twice; the rounds and
+ *                      the join depend on the set of a row's neighbours only.  One index form: the graph's own.
+ *   amg_restrictor     r_cj = [agg(j) == row_offset + c] - (T^t A)_cj * s_j on the CSR of T^t A (compressed local columns, their
+ *                      global ids, each in 0..ncols and owned): the Petrov-Galerkin restriction T^t (I - A S).
  * All only enqueue. */
 int64_t hpcla_amg_work_bytes(int64_t nrows);
 int64_t hpcla_amg_round_blocks(int64_t nrows);
@@ -1087,6 +1095,16 @@ int hpcla_amg_prolongator_f64_i32(const int32_t *at_rowptr, const int32_t *at_co
 int hpcla_amg_prolongator_f64_i64(const int64_t *at_rowptr, const int64_t *at_colval, const int64_t *at_col_indices_dev,
                                   const double *at_nzval, const int64_t *agg_dev, const double *s_dev, int64_t nrows,
                                   int index_base, double *p_nzval, void *stream);
+int hpcla_amg_symmetrise_count(const int64_t *s_rowptr_dev, const int32_t *s_cols_dev, int64_t nrows, int64_t *indeg_dev,
+                               int64_t *u_rowptr_dev, int64_t *info_dev, void *work, void *stream);
+int hpcla_amg_symmetrise_fill(const int64_t *s_rowptr_dev, const int32_t *s_cols_dev, int64_t nrows, const int64_t *u_rowptr_dev,
+                              int64_t *cursor_dev, int32_t *u_cols_dev, void *stream);
+int hpcla_amg_restrictor_f64_i32(const int32_t *ta_rowptr, const int32_t *ta_colval, const int64_t *ta_col_indices_dev,
+                                 const double *ta_nzval, const int64_t *agg_dev, const double *s_dev, int64_t nrows, int64_t ncols,
+                                 int64_t row_offset, int index_base, double *r_nzval, void *stream);
+int hpcla_amg_restrictor_f64_i64(const int64_t *ta_rowptr, const int64_t *ta_colval, const int64_t *ta_col_indices_dev,
+                                 const double *ta_nzval, const int64_t *agg_dev, const double *s_dev, int64_t nrows, int64_t ncols,
+                                 int64_t row_offset, int index_base, double *r_nzval, void *stream);
 int hpcla_amg_presmooth_f64(const double *s_dev, const double *b, double *x, int64_t n, void *stream);
 int hpcla_amg_postsmooth_f64(const double *s_dev, const double *b, const double *t, double *x, int64_t n, void *stream);
 /* ---- fine-grained ILU(0) (hp.ilu0, csrc/ilu.hip): Chow-Patel sweeps for the factors, truncated Jacobi sweeps in place of the

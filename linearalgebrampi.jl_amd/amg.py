@@ -1,4 +1,5 @@
-"""amg(): the smoothed-aggregation algebraic multigrid preconditioner of a symmetric positive definite ``A`` for ``hp.cg``.
+"""amg(): the smoothed-aggregation algebraic multigrid preconditioner: of a symmetric positive definite ``A`` for ``hp.cg``, and
+with ``symmetric=False`` of a nonsymmetric ``A`` with a positive diagonal for ``hp.gmres`` and ``hp.bicgstab``.
 
 Level setup (csrc/amg.hip for what the library's products do not cover), repeated on the current level's ``A``:
   weight      rho = max_i sum_j |a_ij| / a_ii over whole rows (a max across ranks), w = 4 / (3 rho), s = w ./ diag(A)
@@ -12,12 +13,27 @@ Level setup (csrc/amg.hip for what the library's products do not cover), repeate
   last level  n <= coarse_size: the inverse of the symmetrised matrix, formed once on the host, an HPCMatrix applied by the
               dense mat-vec; else ``coarse_sweeps`` damped Jacobi sweeps from zero
 
-The cycle is a symmetric V(1,1): x = s .* b, r = b - A x, x += P cycle(Pt r), x += s .* (b - A x); ``M`` is positive definite.
-Its SpMVs are the ordinary ones on ordinary plans; x = s .* b and x += s .* (b - t) are fused kernels of csrc/amg.hip.
+The cycle is a symmetric V(1,1): x = s .* b, r = b - A x, x += P cycle(R r), x += s .* (b - A x) with R = Pt; ``M`` is positive
+definite.  Its SpMVs are the ordinary ones on ordinary plans; x = s .* b and x += s .* (b - t) are fused kernels of csrc/amg.hip.
 
-Limits: Float64, ``cg`` only, ``A`` symmetric positive definite with a positive stored diagonal, rows and columns partitioned
-alike, one rank (the aggregation is rank-local and runs on several; the products and transposes of the setup move values between
-ranks through RCCL only, so the hierarchy across ranks waits for a transport that ranks sharing a GPU have too).
+``symmetric=False`` changes three steps of a level and nothing else (rho bounds the spectral radius of D^-1 A for any A with a
+positive diagonal, so the weights and the smoother stay):
+  strength    the graph becomes E u E^T (E: the graph above), built on the device from E's own CSR: the independent set and the
+              join assume an undirected graph (on a directed one rows that do not see each other all become roots: on an
+              out-star every leaf, two edges from every other leaf, so the set is not independent and aggregates degenerate).  The
+              threshold is symmetric in i and j, so this is max(|a_ij|, |a_ji|) >= theta sqrt(a_ii a_jj) with an entry that is
+              not stored counting as 0.  Ghost columns stay out both ways.
+  R           the Petrov-Galerkin restriction Tt (I - A S), S = diag(s): Tt A by ``spgemm`` (its rows split like those of Pt
+              below where the product is over the bound), r_cj = [agg(j) == c] - (Tt A)_cj s_j; A_c = R (A P).  ``Pt`` is not
+              formed.  On a symmetric A the first level's R has the bits of Pt.
+  last level  the inverse of the coarse matrix itself.
+The cycle is then a fixed linear operator that is not symmetric: right-preconditioned GMRES and BiCGStab take it, ``cg`` refuses it.
+
+Limits: Float64; ``cg`` for ``A`` symmetric positive definite, ``gmres`` / ``bicgstab`` for either mode; a positive stored diagonal
+on every level (a strongly convective or non-M-matrix ``A`` can give a coarse diagonal that is not: the setup raises), the
+constant as the only near-nullspace candidate, rows and columns partitioned alike, one rank (the aggregation is rank-local and
+runs on several; the products and transposes of the setup move values between ranks through RCCL only, so the hierarchy across
+ranks waits for a transport that ranks sharing a GPU have too).
 """
 from __future__ import annotations
 
@@ -39,8 +55,11 @@ def _torch():
     return torch
 
 
-def check_arguments(T, shape, row_partition, col_partition, theta=0.0, max_levels=12, coarse_size=128, coarse_sweeps=4) -> None:
+def check_arguments(T, shape, row_partition, col_partition, theta=0.0, max_levels=12, coarse_size=128, coarse_sweeps=4,
+                    symmetric=True) -> None:
     """The argument rules, on host values only: ``T`` the element type, ``shape`` and the partitions A's."""
+    if not isinstance(symmetric, (bool, np.bool_)):
+        raise TypeError(f"amg: symmetric must be a bool, got {symmetric!r}")
     if np.dtype(T) != np.dtype(np.float64):
         raise TypeError("amg: offered for Float64 backends only")
     if int(shape[0]) != int(shape[1]):
@@ -59,22 +78,25 @@ def check_arguments(T, shape, row_partition, col_partition, theta=0.0, max_level
 
 class AMGLevel:
     """One level: ``A``, the smoother ``s`` (an HPCVector) with its weight ``w`` and ``rho``, ``n`` (global rows), and on every
-    level but the last ``P``, ``Pt``, ``aggregates`` (global ids of the local rows, a device tensor), ``n_roots`` (this rank's)
-    and ``coarse_partition``.  A level that stalled keeps its aggregation.  The last level has ``inverse`` (an HPCMatrix: this
-    rank's rows of the dense inverse) or ``sweeps``."""
+    level but the last ``P``, ``R`` (the restriction: ``Pt`` itself in the symmetric mode; in the other ``Pt`` stays None),
+    ``aggregates`` (global ids of the local rows, a device tensor), ``n_roots`` (this rank's), ``coarse_partition``, and the
+    runs the two products were split into (``galerkin``; ``restriction_split`` for ``Tt A``, nonsymmetric mode only).  A level
+    that stalled keeps its aggregation.  The last level has ``inverse`` (an HPCMatrix: this rank's rows of the dense inverse)
+    or ``sweeps``."""
 
     def __init__(self, A: HPCSparseMatrix):
         self.A = A
         self.n = int(A.shape[0])
         self.s = self.w = self.rho = None
-        self.P = self.Pt = self.aggregates = self.coarse_partition = self.inverse = None
-        self.n_roots = self.rounds = self.sweeps = self.galerkin = None
+        self.P = self.Pt = self.R = self.aggregates = self.coarse_partition = self.inverse = None
+        self.n_roots = self.rounds = self.sweeps = self.galerkin = self.restriction_split = None
 
 
 class AMGWorkspace:
     """The vectors of a cycle: per level x, b (the coarse ones), t (where the level multiplies by its A) and r / e (where it has a
     P).  One per user of a hierarchy: a ``PCGWorkspace`` holds its own next to its solve vectors (two solves with one hierarchy
-    do not share any), ``AMG.apply`` uses the hierarchy's."""
+    do not share any), a ``GMRESWorkspace`` and a ``BiCGStabWorkspace`` likewise; ``AMG.apply`` uses the hierarchy's unless it is
+    given one."""
 
     def __init__(self, levels: List[AMGLevel]):
         mk = lambda lvl: HPCVector.zeros(lvl.A.row_partition, lvl.A.backend)
@@ -86,11 +108,12 @@ class AMGWorkspace:
 
 class AMG:
     """The hierarchy.  ``levels``: AMGLevel objects, fine to coarse; ``operator_complexity``: the stored entries of every
-    level's A over those of the first (global counts)."""
+    level's A over those of the first (global counts); ``symmetric``: the mode it was built in."""
 
-    def __init__(self, levels: List[AMGLevel], operator_complexity: float):
+    def __init__(self, levels: List[AMGLevel], operator_complexity: float, symmetric: bool = True):
         self.levels = levels
         self.operator_complexity = float(operator_complexity)
+        self.symmetric = bool(symmetric)
         self._work: Optional[AMGWorkspace] = None
 
     def workspace(self) -> AMGWorkspace:
@@ -99,9 +122,10 @@ class AMG:
             self._work = AMGWorkspace(self.levels)
         return self._work
 
-    def apply(self, r: HPCVector, out: Optional[HPCVector] = None) -> HPCVector:
-        """``out = M r``: one V(1,1) cycle from zero; r on A's row partition."""
-        ws = self.workspace()
+    def apply(self, r: HPCVector, out: Optional[HPCVector] = None, workspace: Optional[AMGWorkspace] = None) -> HPCVector:
+        """``out = M r``: one V(1,1) cycle from zero; r on A's row partition.  ``workspace``: the level vectors to work in (the
+        solvers pass their own); the hierarchy's by default."""
+        ws = self.workspace() if workspace is None else workspace
         if r.structural_hash != ws.x[0].structural_hash:
             raise ValueError("amg: r must be partitioned like the rows of A")
         out = r.similar() if out is None else out
@@ -128,7 +152,7 @@ class AMG:
         r = ws.r[k]
         mul_(t, lvl.A, x)                                                                                  # t = A x
         _capi.call("hpcla_axpby_f64", 1.0, dptr(b.v), -1.0, dptr(t.v), dptr(r.v), n, s)                    # r = b - t
-        mul_(ws.b[k + 1], lvl.Pt, r)                                                                       # bc = Pt r
+        mul_(ws.b[k + 1], lvl.R, r)                                                                        # bc = R r
         self._cycle(k + 1, ws.b[k + 1], ws.x[k + 1], ws)
         mul_(r, lvl.P, ws.x[k + 1])                                                                        # e = P xc
         _capi.call("hpcla_axpy_f64", 1.0, None, None, dptr(r.v), dptr(x.v), n, s)                          # x += e
@@ -170,8 +194,9 @@ def _weights(lvl: AMGLevel, plan, sfx: str, row_start: int):
     return diag
 
 
-def _aggregate(lvl: AMGLevel, plan, sfx: str, diag, theta: float, row_start: int) -> None:
-    """Strength graph, roots, join, numbering: fills lvl.aggregates, lvl.n_roots, lvl.rounds, lvl.coarse_partition."""
+def _aggregate(lvl: AMGLevel, plan, sfx: str, diag, theta: float, row_start: int, symmetric: bool = True) -> None:
+    """Strength graph (E u E^T unless ``symmetric``), roots, join, numbering: fills lvl.aggregates, lvl.n_roots, lvl.rounds,
+    lvl.coarse_partition."""
     from .backends import comm_allgather, comm_rank
     torch = _torch()
     lib = _capi.load()
@@ -186,6 +211,12 @@ def _aggregate(lvl: AMGLevel, plan, sfx: str, diag, theta: float, row_start: int
     _capi.call(f"hpcla_amg_strength_count_f64_{sfx}", *structure, dptr(s_rowptr), dptr(info), dptr(work), s)
     s_cols = torch.empty(max(int(info[0].item()), 1), dtype=torch.int32, device=dev)      # the size the graph is allocated by
     _capi.call(f"hpcla_amg_strength_fill_f64_{sfx}", *structure, dptr(s_rowptr), dptr(s_cols), s)
+    if not symmetric:                                        # E u E^T: in-degrees, the combined row pointer, out-lists then in-lists
+        indeg, u_rowptr = i64(n), i64(n + 1)
+        _capi.call("hpcla_amg_symmetrise_count", dptr(s_rowptr), dptr(s_cols), n, dptr(indeg), dptr(u_rowptr), dptr(info), dptr(work), s)
+        u_cols = torch.empty(max(int(info[0].item()), 1), dtype=torch.int32, device=dev)
+        _capi.call("hpcla_amg_symmetrise_fill", dptr(s_rowptr), dptr(s_cols), n, dptr(u_rowptr), dptr(indeg), dptr(u_cols), s)
+        s_rowptr, s_cols = u_rowptr, u_cols
 
     key, m1, m2, state, state_next = (i64(n) for _ in range(5))
     counts = i64(lib.hpcla_amg_round_blocks(n))
@@ -217,8 +248,23 @@ def _aggregate(lvl: AMGLevel, plan, sfx: str, diag, theta: float, row_start: int
     lvl.aggregates = agg
 
 
-def _prolongator(lvl: AMGLevel) -> HPCSparseMatrix:
-    """P on the pattern of A T, and Pt; returns the next level's A."""
+def _restrictor(lvl: AMGLevel, T: HPCSparseMatrix, lo: int) -> HPCSparseMatrix:
+    """R = Tt (I - A S) on the pattern of Tt A (one rank: every column of Tt A is a local row of the level)."""
+    from .indexing import _col_indices_dev
+    from .transpose import transpose
+    A = lvl.A
+    Tt = transpose(T).materialize()
+    TA, lvl.restriction_split = _split_product(Tt, A, 1, lvl, "restriction")
+    vals = _torch().zeros_like(TA.nzval)
+    sfx = "i64" if TA.Ti == np.dtype(np.int64) else "i32"
+    _capi.call(f"hpcla_amg_restrictor_f64_{sfx}", dptr(TA.rowptr_target), dptr(TA.colval_target()), dptr(_col_indices_dev(TA)),
+               dptr(TA.nzval), dptr(lvl.aggregates), dptr(lvl.s.v), TA.nrows_local, A.nrows_local, lo, 0, dptr(vals),
+               current_stream_ptr())
+    return TA._with_values(vals)
+
+
+def _prolongator(lvl: AMGLevel, symmetric: bool = True) -> HPCSparseMatrix:
+    """P on the pattern of A T, and R (Pt, or the Petrov-Galerkin restriction); returns the next level's A."""
     from .backends import comm_rank
     from .indexing import _col_indices_dev
     from .matmat import spgemm
@@ -239,7 +285,10 @@ def _prolongator(lvl: AMGLevel) -> HPCSparseMatrix:
     _capi.call(f"hpcla_amg_prolongator_f64_{sfx}", dptr(AT.rowptr_target), dptr(AT.colval_target()), dptr(_col_indices_dev(AT)),
                dptr(AT.nzval), dptr(lvl.aggregates), dptr(lvl.s.v), n, 0, dptr(vals), current_stream_ptr())
     lvl.P = AT._with_values(vals)
-    lvl.Pt = transpose(lvl.P).materialize()
+    if symmetric:
+        lvl.R = lvl.Pt = transpose(lvl.P).materialize()
+    else:
+        lvl.R = _restrictor(lvl, T, lo)
     return galerkin(lvl, A)
 
 
@@ -276,30 +325,37 @@ def galerkin(lvl: AMGLevel, A: HPCSparseMatrix) -> HPCSparseMatrix:
     of ``Pt`` names, summed); the aggregates of a 3-D stencil's coarse levels are over it.  There the rows of ``Pt`` are split
     into q runs of their entries, ``Pt = Pt_1 + ... + Pt_q``, and the coarse matrix is ``Pt_1 (A P) + ... + Pt_q (A P)``: the
     same pattern, the same products, the sums of an entry associated run by run, so the last bits can differ from the unsplit
-    product's.  q doubles until every part fits; ``lvl.galerkin`` records it (1: not split)."""
-    from .addition import sparse_add
+    product's.  q doubles until every part fits; ``lvl.galerkin`` records it (1: not split).  With ``symmetric=False`` the left
+    factor is ``lvl.R``, and ``Tt A`` inside it is formed the same way (``lvl.restriction_split``)."""
     from .matmat import spgemm
     AP = spgemm(A, lvl.P)
-    q = max(int(FORCE_SPLIT), 1)
+    Ac, lvl.galerkin = _split_product(lvl.R, AP, max(int(FORCE_SPLIT), 1), lvl, "coarse matrix")
+    return Ac
+
+
+def _split_product(L: HPCSparseMatrix, B: HPCSparseMatrix, q: int, lvl: AMGLevel, what: str):
+    """``(L B, q)``: the product with the rows of L in q runs, q doubling from the given one while a part is over the bound."""
+    from .addition import sparse_add
+    from .matmat import spgemm
     while True:
         try:
             if q == 1:
-                Ac = spgemm(lvl.Pt, AP)
+                C = spgemm(L, B)
             else:
-                parts = _split_rows(lvl.Pt, q)
-                Ac = spgemm(parts[0], AP)
+                parts = _split_rows(L, q)
+                C = spgemm(parts[0], B)
                 for part in parts[1:]:
-                    Ac = sparse_add(Ac, spgemm(part, AP))
-            lvl.galerkin = q
-            return Ac
+                    C = sparse_add(C, spgemm(part, B))
+            return C, q
         except NotImplementedError as exc:
             if "candidate entries" not in str(exc) or 2 * q > MAX_SPLIT:
-                raise NotImplementedError(f"amg: the coarse matrix of the level of {lvl.n} rows cannot be formed: {exc}") from None
+                raise NotImplementedError(f"amg: the {what} of the level of {lvl.n} rows cannot be formed: {exc}") from None
             q *= 2
 
 
-def _dense_inverse(lvl: AMGLevel) -> None:
-    """The last level's rows on the host; the inverse of the symmetrised matrix, applied by the dense mat-vec."""
+def _dense_inverse(lvl: AMGLevel, symmetric: bool = True) -> None:
+    """The last level's rows on the host; the inverse of the symmetrised matrix (of the matrix itself unless ``symmetric``),
+    applied by the dense mat-vec."""
     from .dense import HPCMatrix
     torch = _torch()
     A = lvl.A
@@ -309,38 +365,47 @@ def _dense_inverse(lvl: AMGLevel) -> None:
         rowptr = A.rowptr.astype(np.int64)
         cols = A.col_indices[A.colval.astype(np.int64)]
         D[np.repeat(np.arange(n), np.diff(rowptr)), cols] = A.nzval.cpu().numpy()
-    inv = np.linalg.inv((D + D.T) / 2)
+    inv = np.linalg.inv((D + D.T) / 2 if symmetric else D)
     mine = torch.from_numpy(np.ascontiguousarray(inv)).to(A.backend.torch_device)
     lvl.inverse = HPCMatrix(A.row_partition, A.row_partition, mine, A.backend)
 
 
-def aggregate_level(A: HPCSparseMatrix, theta: float = 0.0) -> AMGLevel:
+def aggregate_level(A: HPCSparseMatrix, theta: float = 0.0, symmetric: bool = True) -> AMGLevel:
     """The rank-local part of a level's setup alone, for tests: the weights and the aggregation of ``A`` as an AMGLevel (``s``,
     ``w``, ``rho``, ``aggregates``, ``n_roots``, ``rounds``, ``coarse_partition``; no P).  It exchanges nothing but sizes, the
-    maximum of rho and the error word, so unlike ``amg`` it runs on several ranks.  Raises like ``amg``."""
+    maximum of rho and the error word, in either mode (``symmetric=False``: the graph E u E^T, ghost columns out both ways),
+    so unlike ``amg`` it runs on several ranks.  Raises like ``amg``."""
     from .backends import comm_rank
     f64_only(A.backend, "amg")
-    check_arguments(A.backend.T, A.shape, A.row_partition, A.col_partition, theta)
+    check_arguments(A.backend.T, A.shape, A.row_partition, A.col_partition, theta, symmetric=symmetric)
     lvl = AMGLevel(A)
     plan = get_vector_plan(A, HPCVector.zeros(A.col_partition, A.backend))
     sfx = "i64" if plan.is_i64 else "i32"
     row_start = int(A.row_partition[comm_rank(A.backend.comm)])
-    _aggregate(lvl, plan, sfx, _weights(lvl, plan, sfx, row_start), theta, row_start)
+    _aggregate(lvl, plan, sfx, _weights(lvl, plan, sfx, row_start), theta, row_start, bool(symmetric))
     return lvl
 
 
-def amg(A: HPCSparseMatrix, theta: float = 0.0, max_levels: int = 12, coarse_size: int = 128, coarse_sweeps: int = 4) -> AMG:
+def amg(A: HPCSparseMatrix, theta: float = 0.0, max_levels: int = 12, coarse_size: int = 128, coarse_sweeps: int = 4,
+        symmetric: bool = True) -> AMG:
     """Build the smoothed-aggregation multigrid preconditioner of a symmetric positive definite ``A`` for
-    ``hp.cg(A, b, M=hp.amg(A))``.
+    ``hp.cg(A, b, M=hp.amg(A))``, or with ``symmetric=False`` that of a nonsymmetric ``A`` with a positive diagonal for
+    ``hp.gmres`` and ``hp.bicgstab`` (which take a hierarchy of either mode; ``hp.cg`` refuses one built with ``symmetric=False``).
 
     ``theta``: the strength threshold in [0, 1) (0 keeps every stored coupling; 0.25 suits anisotropic problems).  Setup stops
     at ``n <= coarse_size`` (1..1024; solved densely), at ``max_levels``, or when a level's aggregates number >= 0.8 n; a last
     level above ``coarse_size`` gets ``coarse_sweeps`` damped Jacobi sweeps.  Raises ValueError, with the global row, for a
     diagonal that is not positive (a NaN counts), and NotImplementedError for a communicator of more than one rank and for a
-    level whose coarse matrix is over ``hp.spgemm``'s bound in both orders of the product."""
+    level whose coarse matrix is over ``hp.spgemm``'s bound in both orders of the product.
+
+    ``symmetric=False`` (a bool) aggregates on the symmetrised strength graph E u E^T, restricts with the Petrov-Galerkin
+    ``R = Tt (I - A S)`` in place of ``Pt`` (``AMGLevel.R``; ``Pt`` stays None) and inverts the last level's matrix as it is.  The
+    tentative prolongator is the constant vector, so a two-sided scaling of ``A`` takes most of the gain away; a strongly
+    convective or non-M-matrix ``A`` can give a coarse diagonal that is not positive, which raises as above."""
     from .backends import comm_allgather, comm_rank, comm_size
     f64_only(A.backend, "amg")
-    check_arguments(A.backend.T, A.shape, A.row_partition, A.col_partition, theta, max_levels, coarse_size, coarse_sweeps)
+    check_arguments(A.backend.T, A.shape, A.row_partition, A.col_partition, theta, max_levels, coarse_size, coarse_sweeps, symmetric)
+    symmetric = bool(symmetric)
     backend = A.backend
     if comm_size(backend.comm) > 1:                              # the same on every rank
         raise NotImplementedError("amg: one rank only in this version.  Across ranks the setup's products and transposes move "
@@ -359,12 +424,12 @@ def amg(A: HPCSparseMatrix, theta: float = 0.0, max_levels: int = 12, coarse_siz
         diag = _weights(lvl, plan, sfx, row_start)
         last = lvl.n <= coarse_size or len(levels) >= max_levels
         if not last:
-            _aggregate(lvl, plan, sfx, diag, theta, row_start)
+            _aggregate(lvl, plan, sfx, diag, theta, row_start, symmetric)
             last = int(lvl.coarse_partition[-1]) >= STALL * lvl.n
         if last:
             if lvl.n <= coarse_size:
-                _dense_inverse(lvl)
+                _dense_inverse(lvl, symmetric)
             else:
                 lvl.sweeps = int(coarse_sweeps)
-            return AMG(levels, sum(nnz) / max(nnz[0], 1))
-        A = _prolongator(lvl)
+            return AMG(levels, sum(nnz) / max(nnz[0], 1), symmetric)
+        A = _prolongator(lvl, symmetric)

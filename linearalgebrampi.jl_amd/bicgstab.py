@@ -6,7 +6,7 @@ host read-backs and about 13 launches per BiCGStab iteration.  Here an iteration
 (csrc/vecops.hip, ``hpcla_bicgstab_iterations_f64_*``) whose scalars, stop rule and breakdown tests stay on the device; the
 host enqueues ``check_every`` iterations per library call and reads 16 bytes of state per chunk, exactly as ``hp.cg`` does.
 
-Right-preconditioned, ``K`` = identity, ``dinv .*`` or the operator of ``hp.ilu0`` (ilu.py; the same steps with ``dinv == NULL``,
+Right-preconditioned, ``K`` = identity, ``dinv .*`` or the operator of ``hp.ilu0`` / ``hp.amg`` (ilu.py, amg.py; the same steps with ``dinv == NULL``,
 enqueued one by one from here with ``K`` applied between them); gate order and rounding order (tests/_bicgstab_cases.py restates them):
 
     setup  x = x0 or 0;  r = b - A x;  rhat = r;  p = r;  rho = rhat.r;  hist[0] = r.r;  thr = max(rtol |b|, atol)^2
@@ -80,15 +80,38 @@ def _bicgstab_dinv(A, b: HPCVector, M, name: str = "bicgstab") -> Optional[HPCVe
             raise ValueError(f"{name}: M='jacobi' needs a diagonal without zeros (minimum(abs(diag(A))) > 0)")
         return dinv
     if not isinstance(M, HPCVector):
-        raise ValueError(f"{name}: M must be None, 'jacobi', an HPCVector on A's row partition or an ILU0 (hp.ilu0(A))")
+        raise ValueError(f"{name}: M must be None, 'jacobi', an HPCVector on A's row partition, an ILU0 (hp.ilu0(A)) or an AMG "
+                         f"(hp.amg(A, symmetric=False))")
     b._same_partition(M)
     return rd16_vector(M)                                        # the step kernels read it 16 bytes at a time
 
 
-def _ilu_operator(A, M, name: str):
-    """M when it is the operator of ``hp.ilu0`` (ilu.py is looked at only for an M that is nothing else), checked against A."""
+class _AMGOperator:
+    """The hierarchy of ``hp.amg`` (either mode) as the operator of one solver workspace: ``apply`` is one cycle in level vectors
+    that belong to that workspace (allocated once, kept for later solves with the same hierarchy), so two solves with one
+    hierarchy share none."""
+
+    def __init__(self, mg, ws):
+        from .amg import AMGWorkspace
+        if getattr(ws, "amg", None) is None or ws._amg_of is not mg:
+            ws.amg, ws._amg_of = AMGWorkspace(mg.levels), mg
+        self.mg, self.work = mg, ws.amg
+
+    def apply(self, r: HPCVector, out: HPCVector) -> HPCVector:
+        return self.mg.apply(r, out=out, workspace=self.work)
+
+
+def _ilu_operator(A, M, name: str, ws=None):
+    """M when it is the operator of ``hp.ilu0``, or the hierarchy of ``hp.amg`` wrapped for the workspace ``ws`` (ilu.py and
+    amg.py are looked at only for an M that is nothing else), checked against A."""
     if M is None or isinstance(M, (str, HPCVector)):
         return None
+    from .amg import AMG
+    if isinstance(M, AMG):
+        top = M.levels[0].A
+        if not np.array_equal(top.row_partition, A.row_partition) or top.shape != A.shape:
+            raise ValueError(f"{name}: the AMG preconditioner was built for a matrix of another shape or partition")
+        return _AMGOperator(M, ws)
     from .ilu import ILU0
     if not isinstance(M, ILU0):
         return None
@@ -106,7 +129,9 @@ def bicgstab(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8
     residual ``s_k``), after ``maxiter`` iterations (default ``10 n``), or on a breakdown (``rhat.v``, ``rho``, ``t.t`` or
     ``t.s`` zero or NaN).  ``M``: ``None``, ``"jacobi"`` (``1 ./ diag(A)``, formed on the device; no diagonal entry may be
     zero), an HPCVector holding the inverse diagonal to apply, or the ``ILU0`` object of ``hp.ilu0(A)`` (``ph = M p``,
-    ``sh = M s``: its triangular sweeps, enqueued from here between the gated steps).  ``x0`` defaults to zero.  Returns
+    ``sh = M s``: its triangular sweeps, enqueued from here between the gated steps), or the ``AMG`` object of ``hp.amg`` (one V-cycle
+    each, enqueued the same way in level vectors that belong to the workspace; ``hp.amg(A, symmetric=False)`` for a nonsymmetric
+    ``A``, and a symmetric hierarchy is a valid fixed operator too).  ``x0`` defaults to zero.  Returns
     ``(x, CGInfo)``; x is the workspace's vector, ``residual_norms[j]`` is ``||r_j||`` (``||s_j||`` for a half-step stop) of the
     recurrence.
 
@@ -118,7 +143,7 @@ def bicgstab(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8
     plan = get_vector_plan(A, ws.p)
     if plan.result_partition_hash != ws.p.structural_hash:
         raise ValueError("bicgstab: b must be partitioned like the rows of A")
-    op = _ilu_operator(A, M, "bicgstab")
+    op = _ilu_operator(A, M, "bicgstab", ws)
     dinv = None if op is not None else _bicgstab_dinv(A, b, M)
 
     # -- setup: r0 = b - A x0, rhat = p0 = r0, ph0 = dinv p0, pair 0, the state ------------------------------------------

@@ -366,6 +366,9 @@ def _cg_amg(A, M):
     top = M.levels[0].A
     if not np.array_equal(top.row_partition, A.row_partition) or top.shape != A.shape:
         raise ValueError("cg: the AMG preconditioner was built for a matrix of another shape or partition")
+    if not M.symmetric:
+        raise ValueError("cg: the AMG preconditioner was built with symmetric=False: its cycle is not a symmetric operator "
+                         "(it is for hp.gmres and hp.bicgstab)")
     return M
 
 
@@ -397,7 +400,8 @@ def cg(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, atol
     along p).  ``M``: ``None``, ``"jacobi"`` (``1 ./ diag(A)``, formed on the device; the diagonal must be positive), an
     HPCVector holding the inverse diagonal to apply, or the ``FSAI`` object of ``hp.fsai(A)`` (``z = Gt (G r)``: two more SpMVs
     per iteration, ``r.M r`` formed as ``sum (G r)^2``), or the ``AMG`` object of ``hp.amg(A)`` (``z`` = one multigrid V-cycle on
-    ``r``, enqueued from here between the gated steps).  ``x0`` defaults to zero.  Returns ``(x, CGInfo)``; x is the workspace's
+    ``r``, enqueued from here between the gated steps; a hierarchy built with ``symmetric=False`` is refused with ValueError:
+    its cycle is not symmetric).  ``x0`` defaults to zero.  Returns ``(x, CGInfo)``; x is the workspace's
     vector.
 
     The stop test and the breakdown test run on the device.  The host enqueues ``check_every`` iterations in one library

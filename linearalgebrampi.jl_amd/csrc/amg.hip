@@ -23,6 +23,19 @@
 //             Roots are numbered by the scan of the root flags in row order.
 // P           p_ic = [c == agg(i)] - s_i * (A T)_ic on the stored pattern of A T (global columns through col_indices).
 //
+// For a nonsymmetric A (hp.amg(A, symmetric=False)) two more entries:
+// symmetrise  the roots and the join assume an undirected graph, so the strength graph E becomes E u E^T on the device:
+//             hpcla_amg_symmetrise_count adds the in-degrees of E (one integer atomic per edge) to its out-degrees and scans
+//             them (scan.h) into the combined row pointer; hpcla_amg_symmetrise_fill copies each row's out-list, sets the
+//             row's cursor behind it, and every edge (i, c) then takes a slot of row c through an integer atomic on c's cursor
+//             and stores i there.  Every store is bounded by the row's end.  The order of a row's in-list follows the order
+//             the atomics happen to be served in, and an edge stored in both directions appears twice; the neighbour maxima
+//             and the join take maxima over distinct keys, which depend on the SET of a row's neighbours only, so two builds
+//             give identical aggregates all the same.  Ghost columns are in neither E nor E^T.  The graph has one index form
+//             (int64 row pointer, int32 local columns) whatever A's is.  No float atomics, no kernel waits for another.
+// R           r_cj = [agg(j) == c] - (T^t A)_cj * s_j on the stored pattern of T^t A: the Petrov-Galerkin restriction
+//             T^t (I - A S).  Its columns are the level's rows, all owned (one rank).
+//
 // A group of AMG_G = 8 lanes serves one row in the neighbour loops (8 rows per wave): the grids and their coarse levels
 // store 5 to about 30 entries per row, so a whole wave per row would idle most lanes; a longer row loops in steps of 8.
 // Products and sums are separately rounded (-ffp-contract=off).  No instantiation uses scratch.
@@ -128,6 +141,59 @@ __global__ __launch_bounds__(AMG_THREADS) void amg_strength_fill_kernel(const I 
     for (int64_t e = e0; e < e1; ++e) {
         const int64_t c = (int64_t)colval[e] - base;
         if (amg_strong(i, c, nzval[e], diag, n_own, theta) && pos < end) s_cols[pos++] = (int32_t)c;
+    }
+}
+
+// indeg[c] += 1 for every edge (i, c) of the graph; a group of lanes per row
+__global__ __launch_bounds__(AMG_THREADS) void amg_indegree_kernel(const int64_t *__restrict__ s_rowptr,
+                                                                   const int32_t *__restrict__ s_cols, int64_t nrows,
+                                                                   int64_t *__restrict__ indeg)
+{
+    const int64_t i = ((int64_t)blockIdx.x * AMG_THREADS + threadIdx.x) / AMG_G;
+    const int l = threadIdx.x & (AMG_G - 1);
+    if (i >= nrows) return;
+    for (int64_t e = s_rowptr[i] + l; e < s_rowptr[i + 1]; e += AMG_G) {
+        const int64_t c = s_cols[e];
+        if (c >= 0 && c < nrows) atomicAdd(reinterpret_cast<unsigned long long *>(indeg + c), 1ULL);
+    }
+}
+
+struct AmgDegreeLoad {
+    const int64_t *s_rowptr, *indeg;
+    __device__ int64_t operator()(int64_t i) const { return s_rowptr[i + 1] - s_rowptr[i] + indeg[i]; }
+};
+
+// row i of the combined graph starts with its out-list; cursor[i] is left behind it
+__global__ __launch_bounds__(AMG_THREADS) void amg_symmetrise_copy_kernel(const int64_t *__restrict__ s_rowptr,
+                                                                          const int32_t *__restrict__ s_cols, int64_t nrows,
+                                                                          const int64_t *__restrict__ u_rowptr,
+                                                                          int64_t *__restrict__ cursor, int32_t *__restrict__ u_cols)
+{
+    const int64_t i = ((int64_t)blockIdx.x * AMG_THREADS + threadIdx.x) / AMG_G;
+    const int l = threadIdx.x & (AMG_G - 1);
+    if (i >= nrows) return;
+    const int64_t e0 = s_rowptr[i], m = s_rowptr[i + 1] - e0;
+    const int64_t pos = u_rowptr[i], end = u_rowptr[i + 1];
+    for (int64_t k = l; k < m; k += AMG_G)
+        if (pos + k < end) u_cols[pos + k] = s_cols[e0 + k];
+    if (l == 0) cursor[i] = pos + m < end ? pos + m : end;
+}
+
+// edge (i, c): row c takes i into the next free slot of its in-list
+__global__ __launch_bounds__(AMG_THREADS) void amg_symmetrise_scatter_kernel(const int64_t *__restrict__ s_rowptr,
+                                                                             const int32_t *__restrict__ s_cols, int64_t nrows,
+                                                                             const int64_t *__restrict__ u_rowptr,
+                                                                             int64_t *__restrict__ cursor,
+                                                                             int32_t *__restrict__ u_cols)
+{
+    const int64_t i = ((int64_t)blockIdx.x * AMG_THREADS + threadIdx.x) / AMG_G;
+    const int l = threadIdx.x & (AMG_G - 1);
+    if (i >= nrows) return;
+    for (int64_t e = s_rowptr[i] + l; e < s_rowptr[i + 1]; e += AMG_G) {
+        const int64_t c = s_cols[e];
+        if (c < 0 || c >= nrows) continue;
+        const int64_t pos = (int64_t)atomicAdd(reinterpret_cast<unsigned long long *>(cursor + c), 1ULL);
+        if (pos >= u_rowptr[c] && pos < u_rowptr[c + 1]) u_cols[pos] = (int32_t)i;
     }
 }
 
@@ -260,6 +326,27 @@ __global__ __launch_bounds__(AMG_THREADS) void amg_prolongator_kernel(const I *_
     }
 }
 
+// row c of T^t A (the aggregate row_offset + c): r_cj = [agg(j) == row_offset + c] - ta_cj * s_j; a column outside 0..ncols is left
+template <typename I>
+__global__ __launch_bounds__(AMG_THREADS) void amg_restrictor_kernel(const I *__restrict__ rowptr, const I *__restrict__ colval,
+                                                                     const int64_t *__restrict__ col_indices,
+                                                                     const double *__restrict__ ta, const int64_t *__restrict__ agg,
+                                                                     const double *__restrict__ s, int64_t nrows, int64_t ncols,
+                                                                     int64_t row_offset, int base, double *__restrict__ r)
+{
+    const int64_t c = ((int64_t)blockIdx.x * AMG_THREADS + threadIdx.x) / AMG_G;
+    const int l = threadIdx.x & (AMG_G - 1);
+    if (c >= nrows) return;
+    const int64_t mine = row_offset + c;
+    const int64_t e0 = (int64_t)rowptr[c] - base, e1 = (int64_t)rowptr[c + 1] - base;
+    for (int64_t e = e0 + l; e < e1; e += AMG_G) {
+        const int64_t j = col_indices[(int64_t)colval[e] - base];
+        if (j < 0 || j >= ncols) continue;
+        const double one = agg[j] == mine ? 1.0 : 0.0;
+        r[e] = one - ta[e] * s[j];
+    }
+}
+
 // MODE 0: x = s .* b          MODE 1: x = x + s .* (b - t)         (16-byte accesses, the odd element by one thread)
 template <int MODE>
 __global__ __launch_bounds__(256) void amg_smooth_kernel(const double *__restrict__ s, const double *__restrict__ b,
@@ -370,6 +457,24 @@ static int amg_prolongator_impl(const I *rowptr, const I *colval, const int64_t 
     return HPCLA_OK;
 }
 
+template <typename I>
+static int amg_restrictor_impl(const I *rowptr, const I *colval, const int64_t *col_indices, const double *ta, const int64_t *agg,
+                               const double *s_dev, int64_t nrows, int64_t ncols, int64_t row_offset, int index_base, double *r,
+                               void *stream)
+{
+    if (nrows < 0 || ncols < 0 || row_offset < 0) return set_error(HPCLA_ERR_INVALID, "amg_restrictor: negative size or offset");
+    if (index_base != 0 && index_base != 1) return set_error(HPCLA_ERR_INVALID, "amg_restrictor: index_base must be 0 or 1");
+    if (nrows == 0) return HPCLA_OK;
+    if (!rowptr || !colval || !col_indices || !ta || !agg || !s_dev || !r)
+        return set_error(HPCLA_ERR_INVALID, "amg_restrictor: null array");
+    HPCLA_CHECK_GRID((nrows * AMG_G + AMG_THREADS - 1) / AMG_THREADS, "amg_restrictor");
+    amg_restrictor_kernel<I><<<amg_group_grid(nrows), AMG_THREADS, 0, as_stream(stream)>>>(rowptr, colval, col_indices, ta, agg,
+                                                                                          s_dev, nrows, ncols, row_offset,
+                                                                                          index_base, r);
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
 template <int MODE>
 static int amg_smooth_impl(const double *s_dev, const double *b, const double *t, double *x, int64_t n, void *stream)
 {
@@ -459,6 +564,43 @@ HPCLA_API int hpcla_amg_strength_fill_f64_i64(const int64_t *rowptr, const int64
                                            s_cols_dev, stream);
 }
 
+HPCLA_API int hpcla_amg_symmetrise_count(const int64_t *s_rowptr_dev, const int32_t *s_cols_dev, int64_t nrows, int64_t *indeg_dev,
+                                         int64_t *u_rowptr_dev, int64_t *info_dev, void *work, void *stream)
+{
+    if (nrows < 0 || nrows > 0x7fffffffLL) return set_error(HPCLA_ERR_INVALID, "amg_symmetrise_count: needs 0 <= nrows < 2^31");
+    if (!u_rowptr_dev || !info_dev || !work) return set_error(HPCLA_ERR_INVALID, "amg_symmetrise_count: null rowptr / info / work");
+    hipStream_t s = as_stream(stream);
+    HPCLA_CHECK_HIP(hipMemsetAsync(info_dev, 0, sizeof(int64_t), s));
+    if (nrows == 0) {
+        HPCLA_CHECK_HIP(hipMemsetAsync(u_rowptr_dev, 0, sizeof(int64_t), s));
+        return HPCLA_OK;
+    }
+    if (!s_rowptr_dev || !indeg_dev) return set_error(HPCLA_ERR_INVALID, "amg_symmetrise_count: null array");   // s_cols may be NULL
+    HPCLA_CHECK_HIP(hipMemsetAsync(indeg_dev, 0, sizeof(int64_t) * (size_t)nrows, s));
+    amg_indegree_kernel<<<amg_group_grid(nrows), AMG_THREADS, 0, s>>>(s_rowptr_dev, s_cols_dev, nrows, indeg_dev);
+    HPCLA_CHECK_LAUNCH();
+    int64_t *sums = reinterpret_cast<int64_t *>(work);
+    return exclusive_scan(AmgDegreeLoad{s_rowptr_dev, indeg_dev}, nrows, AmgRowptrEmit{nrows, u_rowptr_dev, info_dev}, sums + 1, sums,
+                          s);
+}
+
+HPCLA_API int hpcla_amg_symmetrise_fill(const int64_t *s_rowptr_dev, const int32_t *s_cols_dev, int64_t nrows,
+                                        const int64_t *u_rowptr_dev, int64_t *cursor_dev, int32_t *u_cols_dev, void *stream)
+{
+    if (nrows < 0 || nrows > 0x7fffffffLL) return set_error(HPCLA_ERR_INVALID, "amg_symmetrise_fill: needs 0 <= nrows < 2^31");
+    if (nrows == 0) return HPCLA_OK;
+    if (!s_rowptr_dev || !u_rowptr_dev || !cursor_dev)
+        return set_error(HPCLA_ERR_INVALID, "amg_symmetrise_fill: null array");            // both column arrays NULL: no edges
+    hipStream_t s = as_stream(stream);
+    amg_symmetrise_copy_kernel<<<amg_group_grid(nrows), AMG_THREADS, 0, s>>>(s_rowptr_dev, s_cols_dev, nrows, u_rowptr_dev,
+                                                                            cursor_dev, u_cols_dev);
+    HPCLA_CHECK_LAUNCH();
+    amg_symmetrise_scatter_kernel<<<amg_group_grid(nrows), AMG_THREADS, 0, s>>>(s_rowptr_dev, s_cols_dev, nrows, u_rowptr_dev,
+                                                                               cursor_dev, u_cols_dev);
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
 HPCLA_API int hpcla_amg_mis_init(int64_t nrows, int64_t row_start, int64_t *key_dev, int64_t *state_dev, void *stream)
 {
     if (nrows < 0 || nrows > 0x7fffffffLL || row_start < 0)
@@ -541,6 +683,22 @@ HPCLA_API int hpcla_amg_prolongator_f64_i64(const int64_t *at_rowptr, const int6
 {
     return amg_prolongator_impl<int64_t>(at_rowptr, at_colval, at_col_indices_dev, at_nzval, agg_dev, s_dev, nrows, index_base,
                                          p_nzval, stream);
+}
+
+HPCLA_API int hpcla_amg_restrictor_f64_i32(const int32_t *ta_rowptr, const int32_t *ta_colval, const int64_t *ta_col_indices_dev,
+                                           const double *ta_nzval, const int64_t *agg_dev, const double *s_dev, int64_t nrows,
+                                           int64_t ncols, int64_t row_offset, int index_base, double *r_nzval, void *stream)
+{
+    return amg_restrictor_impl<int32_t>(ta_rowptr, ta_colval, ta_col_indices_dev, ta_nzval, agg_dev, s_dev, nrows, ncols, row_offset,
+                                        index_base, r_nzval, stream);
+}
+
+HPCLA_API int hpcla_amg_restrictor_f64_i64(const int64_t *ta_rowptr, const int64_t *ta_colval, const int64_t *ta_col_indices_dev,
+                                           const double *ta_nzval, const int64_t *agg_dev, const double *s_dev, int64_t nrows,
+                                           int64_t ncols, int64_t row_offset, int index_base, double *r_nzval, void *stream)
+{
+    return amg_restrictor_impl<int64_t>(ta_rowptr, ta_colval, ta_col_indices_dev, ta_nzval, agg_dev, s_dev, nrows, ncols, row_offset,
+                                        index_base, r_nzval, stream);
 }
 
 HPCLA_API int hpcla_amg_presmooth_f64(const double *s_dev, const double *b, double *x, int64_t n, void *stream)

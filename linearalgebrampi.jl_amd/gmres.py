@@ -9,7 +9,7 @@ with one read of the basis; ``gmres_update``: the whole running subtraction in o
 stop rule and breakdown test stay on the device; the host enqueues ``check_every`` inner steps per library call
 (``hpcla_gmres_iterations_f64_*``) and reads 16 bytes of state per chunk, exactly as the other two solvers do.
 
-Right-preconditioned, ``K`` = identity, ``dinv .*`` or the operator of ``hp.ilu0`` (ilu.py; ``_gmres_operator`` enqueues the same
+Right-preconditioned, ``K`` = identity, ``dinv .*`` or the operator of ``hp.ilu0`` / ``hp.amg`` (ilu.py, amg.py; ``_gmres_operator`` enqueues the same
 steps with ``dinv == NULL`` one by one and applies ``K`` between them); gate order and rounding order (tests/_gmres_cases.py restates them):
 
     start / restart   w = b - A x (w = b when x is zero);  rr = w.w
@@ -29,7 +29,7 @@ from __future__ import annotations
 from typing import Optional, Tuple
 
 from . import _capi
-from .bicgstab import _bicgstab_dinv, _ilu_operator
+from .bicgstab import _AMGOperator, _bicgstab_dinv, _ilu_operator
 from .cg import CGInfo, _PairHistory, _residual_norms, _run_chunks, _solver_arguments, _stop_rule_or_done
 from .sparse import get_vector_plan, mul_
 from .vectors import HPCVector, current_stream_ptr, dptr, norm, rd16_vector
@@ -109,9 +109,13 @@ def _open_columns(status: int, iterations: int, maxiter: int, m: int) -> int:
 
 def _gmres_operator(A, b: HPCVector, x0, rtol: float, atol: float, m: int, maxiter: int, op, check_every: int,
                     ws: GMRESWorkspace) -> Tuple[HPCVector, CGInfo]:
-    """``gmres`` with ``K = op.apply`` (the ILU0 of ilu.py): the order of hpcla_gmres_iterations_*, enqueued from here through
-    the exported gated entries with dinv == NULL; each ``dinv .*`` is ``op.apply``.  The application is not gated: behind the
-    deciding step its input is frozen and it rewrites z and its own scratch with what they held.  ``x = x + K (V y)`` goes
+    """``gmres`` with ``K = op.apply`` (the ILU0 of ilu.py, or the multigrid cycle of amg.py): the order of
+    hpcla_gmres_iterations_*, enqueued from here through the exported gated entries with dinv == NULL; each ``dinv .*`` is
+    ``op.apply``.  The application is not gated: behind the deciding step its input is frozen and it rewrites z and its own
+    scratch with what they held (the cycle is a fixed sequence of launches on the basis column, the hierarchy and level vectors
+    that nothing else writes: the same input gives the same bits in every one of them).  The ILU0 reads the basis column through
+    its raw pointer; the cycle reads it as an HPCVector over the column's storage (the pitch keeps it 16-byte aligned).
+    ``x = x + K (V y)`` goes
     through a scratch vector: u = 0, the gated update adds V y into u, ku = K u, and a gated update of one column adds
     1 * ku into x -- behind a stop u stays zero and nothing is added."""
     ws.with_operator()
@@ -122,7 +126,11 @@ def _gmres_operator(A, b: HPCVector, x0, rtol: float, atol: float, m: int, maxit
     column = lambda c: ws.V.data_ptr() + 8 * c * ldv
 
     def apply_to_column(c):
-        if n:
+        if not n:
+            return
+        if isinstance(op, _AMGOperator):
+            op.apply(HPCVector(ws.x.structural_hash, ws.x.partition, ws.V[c * ldv:c * ldv + n], ws.x.backend), out=ws.z)
+        else:
             op._enqueue(column(c), dptr(ws.z.v))
 
     def start_cycle(k):                                          # the residual (w holds A x, or 0), gate R, V_0, z = K V_0
@@ -193,7 +201,9 @@ def gmres(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, a
     new Hessenberg column that is zero or NaN: ``A`` is singular on the Krylov space).  ``restart`` is the cycle length, 1..64;
     a cycle keeps ``restart + 1`` basis vectors.  ``M``: ``None``, ``"jacobi"`` (``1 ./ diag(A)``, formed on the device; no
     diagonal entry may be zero), an HPCVector holding the inverse diagonal to apply, or the ``ILU0`` object of ``hp.ilu0(A)``
-    (its triangular sweeps, enqueued from here between the gated steps).  ``x0`` defaults to zero.  Returns
+    (its triangular sweeps, enqueued from here between the gated steps), or the ``AMG`` object of ``hp.amg`` (one V-cycle per
+    step, enqueued the same way in level vectors that belong to the workspace; ``hp.amg(A, symmetric=False)`` for a nonsymmetric
+    ``A``, and a symmetric hierarchy is a valid fixed operator too).  ``x0`` defaults to zero.  Returns
     ``(x, CGInfo)``; x is the workspace's vector.  ``iterations`` counts inner steps: one SpMV each, plus one per restart.
     ``residual_norms[k]`` is the Givens estimate ``|g_{j+1}|`` of ``||r_k||`` after step k -- with the preconditioner on the
     right that is the norm of the true residual ``b - A x_k`` -- and entry 0 is the true ``||b - A x0||``; it never rises.
@@ -213,7 +223,7 @@ def gmres(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, a
     plan = get_vector_plan(A, ws.x)
     if plan.result_partition_hash != ws.x.structural_hash:
         raise ValueError("gmres: b must be partitioned like the rows of A")
-    op = _ilu_operator(A, M, "gmres")
+    op = _ilu_operator(A, M, "gmres", ws)
     if op is not None:
         return _gmres_operator(A, b, x0, rtol, atol, m, maxiter, op, check_every, ws)
     dinv = _bicgstab_dinv(A, b, M, "gmres")
