@@ -1134,8 +1134,8 @@ int hpcla_amg_postsmooth_f64(const double *s_dev, const double *b, const double 
  *                   order; 2, 4, 8: a lane group per row, partial sums joined by shuffles, subtracted once.  in == NULL: the
  *                   sum is empty; dinv_dev == NULL: no scaling.  in and out are two buffers.  No alignment is asked for.
  *   ilu_apply       out = N_U(N_L(r)) in 2 solve_sweeps + 1 trisweep launches: y_0 = r, y_{m+1} = r - L y_m;  z_0 = dinv .* y,
- *                   z_{m+1} = dinv .* (y - U z_m), solve_sweeps (1..16) times each.  t0, t1: scratch of nrows doubles; r, t0,
- *                   t1 and out are distinct.
+ *                   z_{m+1} = dinv .* (y - U z_m), solve_sweeps (1..16) times each.  t0, t1: scratch of nrows doubles, distinct
+ *                   from each other, from r and from out.  out may be r: r is last read before out is first written.
  * All only enqueue (vector atomic min on info_dev, no waiting); every result is fixed by the inputs. */
 int64_t hpcla_ilu_work_bytes(int64_t nrows);
 int hpcla_ilu_count_f64_i32(const int32_t *a_rowptr, const int32_t *a_colval_split, int64_t nrows, int64_t n_own,

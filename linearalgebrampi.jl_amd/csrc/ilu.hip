@@ -25,6 +25,7 @@
 // one kernel per sweep, the row's split taken from b_diag.  LANES = 1: one lane per row walks its part in stored order, a
 // running subtraction.  LANES = 2, 4, 8: a group of lanes strides the part, the partial sums meet by shuffles and are
 // subtracted from rhs_i once.  `in` and `out` are distinct buffers; in == NULL stands for an empty sum (z_0 = dinv .* y).
+// hpcla_ilu_apply_f64 reads r in the lower sweeps only and writes out in the upper ones only, so its out may be its r.
 #include "common.h"
 #include "scan.h"
 
@@ -391,7 +392,7 @@ HPCLA_API int hpcla_ilu_apply_f64(const int32_t *b_rowptr_dev, const int32_t *b_
     if (!b_rowptr_dev || !b_cols_dev || !b_diag_dev || !f_dev || !dinv_dev || !r || !t0 || !t1 || !out)
         return set_error(HPCLA_ERR_INVALID, "ilu_apply: null array");
     if (t0 == t1 || t0 == out || t1 == out || r == t0 || r == t1)
-        return set_error(HPCLA_ERR_INVALID, "ilu_apply: r, t0, t1 and out must be distinct buffers");
+        return set_error(HPCLA_ERR_INVALID, "ilu_apply: t0 and t1 must be distinct from each other, from r and from out");
     hipStream_t s = as_stream(stream);
     double *t[2] = {t0, t1};
     // y_0 = r, y_{m+1} = r - L y_m: the sweeps land in t0, t1, t0, ...

@@ -112,13 +112,26 @@ class ILU0:
         self._f, self._g = torch.zeros(nnz, **f64), torch.zeros(nnz, **f64)
         self._dinv = torch.zeros(n, **f64)
 
-    def _factor(self, A: HPCSparseMatrix) -> None:
+    def _check_diagonal(self) -> None:
+        """The fill's test of the stored diagonals (zero or NaN: code 2) on the values just gathered, for ``update``: the fill
+        saw the first matrix's values only.  Every row stores its diagonal, or the build had raised.  Leaves the error word at
+        the smallest failing row's, or at all ones; enqueues only."""
+        torch = _torch()
+        d = self._a[self._diag.to(torch.int64)]
+        rows = torch.arange(self.n, dtype=torch.int64, device=d.device)
+        words = torch.where((d == 0) | (d != d), (rows << 2) | _BAD_DIAG, torch.full_like(rows, 2 ** 62))
+        word = words.min()
+        self._info[1:2] = torch.where(word < 2 ** 62, word, torch.full_like(word, -1))
+
+    def _factor(self, A: HPCSparseMatrix, new_values: bool = False) -> None:
         """Values, the initial guess, the sweeps, the pivots: enqueued in a row; then the one read-back of the error word."""
         from .backends import comm_allgather
         s = current_stream_ptr()
         n, nnz = self.n, self.nnz
         index = (dptr(self._cols), dptr(self._rows), dptr(self._diag))
         _capi.call("hpcla_ilu_gather_f64", dptr(A.nzval), dptr(self._map), nnz, dptr(self._a), s)
+        if new_values and n:
+            self._check_diagonal()
         _capi.call("hpcla_ilu_init_f64", *index, dptr(self._a), nnz, dptr(self._f), s)
         for _ in range(self.sweeps):
             _capi.call("hpcla_ilu_sweep_f64", dptr(self._rowptr), *index, dptr(self._cptr), dptr(self._cpos), dptr(self._a),
@@ -134,12 +147,13 @@ class ILU0:
             raise ValueError(error_message(code, row, self.sweeps))
 
     def update(self, A: HPCSparseMatrix) -> "ILU0":
-        """New values of ``A`` on the structure this object was built for: one gather and the sweeps, no index work."""
+        """New values of ``A`` on the structure this object was built for: one gather and the sweeps, no index work.  Raises as
+        ``ilu0`` does, a zero or NaN diagonal among the new values included; the object can be updated again afterwards."""
         if tuple(int(v) for v in A.shape) != self.shape or not np.array_equal(A.row_partition, self.row_partition) \
                 or int(A.nrows_local) != self.n or int(A.nnz) < self.nnz:
             raise ValueError("ilu0: update needs a matrix with the structure the factors were built for")
         self._info[1:2].fill_(-1)                                  # the error word, as the count leaves it
-        self._factor(A)
+        self._factor(A, new_values=True)
         return self
 
     # -- application ------------------------------------------------------------------------------------------------------------

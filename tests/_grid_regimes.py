@@ -84,6 +84,9 @@ _as_first, _as_stride = _ints(
     "amg.hip", _pat("int64_t i = ( int64_t ) blockIdx . x * # + threadIdx . x ; const int64_t stride = ( int64_t ) gridDim . x * # ;") +
     _WS + _pat("for ( ; i < n2 ; i += stride ) {"))
 assert _as_m1 == AMG_SMOOTH_T - 1 and _as_cap == AMG_SMOOTH_CAP and _as_t == AMG_SMOOTH_T == _as_first == _as_stride
+# the ILU(0) kernels (ilu.hip): one lane per row, per entry or per (row, lane of the group), workgroups of ILU_THREADS lanes
+ILU_THREADS, = _ints("ilu.hip", _pat("constexpr int ILU_THREADS = # ;"))
+_ints("ilu.hip", _pat("const int64_t nb = ( nrows * lanes + ILU_THREADS - 1 ) / ILU_THREADS ;"))
 
 
 # ---- the grid functions ----------------------------------------------------------------------------------------------------
@@ -125,6 +128,11 @@ def digest_trips(n):
 def amg_smooth_grid(n):
     """Workgroups of amg_smooth_kernel over n doubles (n // 2 double2, the odd element by one thread)."""
     return min(max(_ceil_div(n // AMG_SMOOTH_WIDTH, AMG_SMOOTH_T), 1), AMG_SMOOTH_CAP)
+
+
+def ilu_grid(items):
+    """Workgroups of an ILU(0) kernel over `items` rows, entries or rows * lanes."""
+    return _ceil_div(items, ILU_THREADS)
 
 
 def partials_two_stage(np_):

@@ -86,3 +86,15 @@ def test_scan_windows_partial_counts_and_digest_sizes():
     assert [(gr.digest_grid(n), gr.digest_trips(n)) for n in gr.DIGEST_SIZES] == [(1, 1), (1, 1), (2, 1), (4096, 1), (4096, 2),
                                                                                   (4096, 3)]
     assert gr.DIGEST_SIZES[4] - 1 == gr.DIGEST_CAP * gr.DIGEST_T            # element 1 048 576 opens the second trip
+
+
+def test_ilu_kernels_sizes_land_on_both_sides_of_a_workgroup():
+    from tests import _ilu_cases as ic
+    assert gr.ILU_THREADS == 256
+    assert [gr.ilu_grid(n) for n in ic.NNZ_EDGES] == [1, 1, 1, 2] and [gr.ilu_grid(n) for n in ic.PIVOT_SIZES] == [1, 1, 2, 3]
+    assert [gr.ilu_grid(n) for n in ic.ROW_EDGES] == [1, 1, 1, 1, 2, 4, 4, 5, 9, 1025]
+    items = sorted({n * lanes for n in ic.RAGGED_SIZES for lanes in ic.LANES})
+    for lanes in ic.LANES[1:]:                                      # a row count whose lanes end on, before and behind a workgroup
+        mod = {(n * lanes) % gr.ILU_THREADS for n in ic.RAGGED_SIZES if n * lanes >= gr.ILU_THREADS - lanes}
+        assert {0, lanes, gr.ILU_THREADS - lanes} <= mod, (lanes, sorted(mod))
+    assert {255, 256, 257} <= set(items) and max(gr.ilu_grid(v) for v in items) == 32

@@ -269,3 +269,228 @@ def test_history_heads_spread_less_than_a_tenth_of_the_margin(systems, size):
           f"bicgstab {sb:.2e} ({ic.HEAD_BICGSTAB} entries); bicgstab counts {counts}")
     assert sg < ic.HIST_RTOL / 10 and sb < ic.HIST_RTOL / 10
     assert max(counts) - min(counts) <= 2
+
+
+# ---- the restatements of the single kernels (tests/test_gpu_ilu_kernels.py) -------------------------------------------------------
+@pytest.fixture(scope="module")
+def kernel_cases(orc):
+    return ic.kernel_cases(orc)
+
+
+def test_work_bytes_at_the_scan_block_edges(hp):
+    from tests import _grid_regimes as gr
+    lib = hp._capi.load()
+    for n in (0, 1, 1024, 1025):
+        assert lib.hpcla_ilu_work_bytes(n) == 8 * (1 + gr.scan_blocks(max(n, 1))), n
+    assert ic.ROW_EDGES[-1] == gr.SCAN_T * gr.SCAN_B + 1 == gr.SCAN_CARRY_AT + 1
+    assert [gr.scan_blocks(n) for n in ic.ROW_EDGES] == [1, 1, 1, 1, 1, 1, 1, 2, 3, 257]
+    assert [gr.scan_trips(n) for n in ic.ROW_EDGES] == [1] * 9 + [2]
+    assert gr.ILU_THREADS == 256
+    large = pc.LARGE_SIZE[0] * pc.LARGE_SIZE[1]
+    assert large == 4095 and gr.scan_blocks(large) == 4 and large == 4 * gr.SCAN_B - 1
+
+
+def test_block_of_split_agrees_with_block_csr_on_every_block(kernel_cases):
+    from tests import _amg_cases as ac
+    chains = with_ghosts = 0
+    for name, matrix in kernel_cases.items():
+        rowptr, colidx, vals = matrix
+        A = ic.to_scipy(*matrix)
+        for k, j, part in ic.block_inputs(name, matrix):
+            lo, hi = part[j], part[j + 1]
+            a, b = int(rowptr[lo]), int(rowptr[hi])
+            bp, bcols, bv = ic.block_csr(rowptr[lo:hi + 1] - a, colidx[a:b], vals[a:b], lo)
+            first = None
+            for base, Ti in ((0, np.int32), (1, np.int64)):
+                r, split, v, n_own, ghosts = ac.split_block(A, part, j, base, Ti)
+                got = ic.block_of_split(r, split, v, n_own, base)
+                assert np.array_equal(got[0], bp) and np.array_equal(got[1], bcols), (name, k, j)
+                assert np.array_equal(pc.bits(got[5]), pc.bits(bv)) and got[6] == ic.NO_FAILURE, (name, k, j)
+                assert np.array_equal(got[2], np.repeat(np.arange(hi - lo), np.diff(bp)))
+                assert np.array_equal(got[1][got[3]], np.arange(hi - lo)) and np.array_equal(v[got[4]], bv)
+                first = first or got
+                assert all(np.array_equal(x, y) for x, y in zip(got[:6], first[:6]))
+            chains += 1
+            with_ghosts += int(len(ghosts) > 0)
+            if k > 1 and hi - lo > 1 and name != "diagonal":
+                assert len(ghosts) > 0, (name, k, j)
+    print(f"{chains} (case, blocks, block) inputs, {with_ghosts} of them with ghost columns")
+    assert chains >= 150 and with_ghosts >= 100
+
+
+def test_the_non_raising_chain_is_sweep_factors_on_healthy_input(kernel_cases):
+    """init_values / sweep_once (the literal merge) against sweep_factors (the products by set intersection), bit for bit."""
+    longest = 0
+    for name in ("convdiff24x20", "banded3", "banded16", "asymmetric", "diagonal", "one", "arrow", "comb"):
+        matrix = kernel_cases[name]
+        n = len(matrix[0]) - 1
+        for part, j in (([0, n], 0), (ic.equal_blocks(n, 3), 1)):
+            if name in ("arrow", "comb", "one") and len(part) > 2:
+                continue
+            ref = ic.block_reference(matrix, part, j)
+            for sweeps in (0, 1, 3):
+                want = ic.sweep_factors(ref["bp"], ref["bc"], ref["a_vals"], sweeps, part[j])
+                assert np.array_equal(pc.bits(ref["f"][sweeps]), pc.bits(want)), (name, len(part) - 1, sweeps)
+            longest = max(longest, int(ref["products"][3][:, 0].max()))
+    print(f"longest merged sum {longest} products")
+    assert longest == ic.ARROW_N - 1
+
+
+def test_arrow_and_comb_walk_the_merge_as_stated(kernel_cases):
+    ref = ic.block_reference(kernel_cases["arrow"], [0, ic.ARROW_N], 0)
+    n = ic.ARROW_N
+    assert np.diff(ref["bp"]).max() == n and np.diff(ref["c_ptr"]).max() == n
+    corner = int(ref["bp"][n]) - 1
+    assert (ref["brows"][corner], ref["bc"][corner]) == (n - 1, n - 1) and ref["products"][3][corner].tolist() == [n - 1, 0, 0, 1]
+    A = bc.dense_of(*kernel_cases["arrow"])
+    assert not np.allclose(A, A.T) and np.all(np.diag(A) > np.abs(A).sum(axis=1) - np.diag(A))
+    # the corner's sum depends on its order: the descending sum differs in bits
+    up = ic.sweep_factors(ref["bp"], ref["bc"], ref["a_vals"], 1)[corner]
+    down = ic.sweep_factors(ref["bp"], ref["bc"], ref["a_vals"], 1, descending=True)[corner]
+    assert up != down
+    ref = ic.block_reference(kernel_cases["comb"], [0, ic.COMB_N], 0)
+    stats = ref["products"][3]
+    every = np.flatnonzero((stats[:, 0] >= 5) & (stats[:, 1] >= 5) & (stats[:, 2] >= 5))
+    print(f"comb: {len(stats)} entries, {len(every)} take every branch 5 times or more, {int(stats[:, 3].sum())} end at the break")
+    assert 90 <= len(ref["bp"]) - 1 <= 100 and len(every) >= 1 and np.any(stats[every, 3] == 1)
+    A = bc.dense_of(*kernel_cases["comb"])
+    assert np.all(np.diag(A) > np.abs(A).sum(axis=1) - np.diag(A))
+    # a walk that advanced the wrong pointer in a skip branch, or went on to k = m, would meet other products
+    i, j = int(ref["brows"][every[0]]), int(ref["bc"][every[0]])
+    ks = [k for k in range(min(i, j)) if A[i, k] != 0 and A[k, j] != 0]
+    assert stats[every[0], 0] == len(ks) and A[i, min(i, j)] != 0
+
+
+def test_counted_cases_have_the_counts_they_are_for(kernel_cases):
+    for nnz in ic.NNZ_EDGES:
+        rowptr, cols, vals = ic.nnz_edge(nnz)
+        assert rowptr[-1] == len(cols) == len(vals) == nnz
+        got = ic.block_of_split(rowptr, cols, vals, len(rowptr) - 1)
+        assert got[6] == ic.NO_FAILURE and len(got[1]) == nnz
+    # the duplicated columns: ties in stored order, the last stored diagonal
+    rowptr, split, vals, n_own = ic.duplicated_block()
+    bp, bcols, brows, bdiag, bmap, a_vals, word = ic.block_of_split(rowptr, split, vals, n_own)
+    assert bp.tolist() == [0, 3, 7, 10, 11] and bcols.tolist() == [0, 0, 1, 0, 1, 1, 3, 2, 3, 3, 3]
+    assert bmap.tolist() == [1, 2, 0, 6, 4, 7, 8, 11, 9, 10, 14] and bdiag.tolist() == [1, 5, 7, 10]
+    assert a_vals.tolist() == [4.0, 5.0, -1.0, -2.0, 6.0, 0.0, 1.5, 7.0, -1.0, -2.0, 8.0] and word == (1 << 2) | ic.BAD_DIAG
+    # generated rows: ghosts, unsorted rows, no duplicate, every diagonal
+    for n in ic.ROW_EDGES[:-1]:
+        rowptr, colval, vals = ic.generated_rows(n)
+        assert len(rowptr) == n + 1 and np.all(np.diff(rowptr) >= 1) and np.all(np.diff(rowptr) <= 3)
+        got = ic.block_of_split(rowptr, colval, vals, n)
+        assert np.all(got[3] >= 0) and got[6] == ic.NO_FAILURE
+        if n >= 255:
+            assert np.any(colval >= n) and np.any(np.diff(colval)[np.diff(np.repeat(np.arange(n), np.diff(rowptr))) == 0] < 0)
+            assert all(len(set(colval[rowptr[i]:rowptr[i + 1]])) == rowptr[i + 1] - rowptr[i] for i in range(0, n, 7))
+            assert 0 < len(got[1]) < len(colval)
+    # the word of the fill on the three faults
+    for heal, want in enumerate([(40 << 2) | ic.BAD_DIAG, (300 << 2) | ic.NO_DIAG, (520 << 2) | ic.BAD_DIAG, ic.NO_FAILURE]):
+        rowptr, cols, vals = ic.three_faults(heal)
+        got = ic.block_of_split(rowptr, cols, vals, 600)
+        assert got[6] == want and (got[3][300] == -1) == (heal < 2)
+    # the shuffled rows leave the block where it was
+    from tests import _amg_cases as ac
+    for name in ic.SHUFFLED_ON:
+        matrix = kernel_cases[name]
+        part = ic.equal_blocks(len(matrix[0]) - 1, 3)
+        between = 0
+        for j in range(3):
+            rowptr, split, vals, n_own, _ = ac.split_block(ic.to_scipy(*matrix), part, j)
+            cols2, vals2, perm = ic.shuffled_rows(rowptr, split, vals, np.random.default_rng(5 + j))
+            a, b = ic.block_of_split(rowptr, split, vals, n_own), ic.block_of_split(rowptr, cols2, vals2, n_own)
+            assert not np.array_equal(cols2, split)
+            assert all(np.array_equal(a[t], b[t]) for t in (0, 1, 2, 3, 5)) and np.array_equal(perm[b[4]], a[4])
+            own = np.flatnonzero(cols2 < n_own)                 # a ghost stands between two owned entries of some row
+            row_of = np.repeat(np.arange(n_own), np.diff(rowptr))
+            between += int(np.sum((row_of[own][1:] == row_of[own][:-1]) & (np.diff(own) > 1)))
+        assert between >= 1, name
+
+
+def test_faults_spoil_only_the_rows_from_their_own_on(kernel_cases):
+    clean = ic.block_reference(ic.fault_case(None), [0, ic.BANDED_N], 0)
+    assert np.array_equal(pc.bits(clean["f"][3]), pc.bits(ic.sweep_factors(clean["bp"], clean["bc"], clean["a_vals"], 3)))
+    r = ic.FAULT_ROW
+    for kind in ic.FAULT_KINDS:
+        ref = ic.block_reference(ic.fault_case(kind), [0, ic.BANDED_N], 0)
+        head = int(ref["bp"][r])
+        assert head == clean["bp"][r]
+        for t in range(4):
+            assert np.array_equal(pc.bits(ref["f"][t][:head]), pc.bits(clean["f"][t][:head])), (kind, t)
+        changed = not np.array_equal(pc.bits(ref["f"][3][head:]), pc.bits(clean["f"][3][head:])) or len(ref["bc"]) != len(clean["bc"])
+        assert changed, kind
+        dinv, word = ic.pivots(ref["bdiag"], ref["f"][3], ref["word"])
+        print(f"{kind}: {int(np.isnan(ref['f'][3]).sum())} NaN and {int(np.isinf(ref['f'][3]).sum())} Inf entries after 3 sweeps, "
+              f"word of the fill {ref['word']}, after the pivots {word}")
+        assert (ref["word"] == ic.NO_FAILURE) == (kind in ("inf_diagonal", "nan_off", "inf_off", "negative_zero_off"))
+
+
+def test_pivots_restatement_at_its_special_values():
+    for n in ic.PIVOT_SIZES:
+        bdiag, f = ic.pivot_case(n)
+        dinv, word = ic.pivots(bdiag, f)
+        if n == 1:
+            assert word == ic.NO_FAILURE and dinv[0] == 1.0 / f[0]
+            continue
+        assert np.isnan(dinv[1]) and np.isnan(dinv[n - 2]) and word >> 2 not in (1, n - 2)
+        rows = np.linspace(3, n - 1, 8).astype(np.int64)
+        u = f[bdiag[rows]]
+        assert np.array_equal(pc.bits(u), pc.bits(np.array(ic.PIVOT_SPECIALS)))
+        failing = rows[[1, 3, 5, 6, 7]]                          # +Inf, 0.0, NaN, -0.0, -Inf
+        assert word == (int(failing[0]) << 2) | ic.BAD_PIVOT
+        assert np.isinf(dinv[rows[0]]) and np.isinf(dinv[rows[2]]) and dinv[rows[4]] == 1e-308       # denormal pivots: no code
+        assert np.signbit(dinv[rows[6]]) and np.isinf(dinv[rows[6]]) and dinv[rows[7]] == 0.0 and np.signbit(dinv[rows[7]])
+        if n == 600:
+            assert sorted(set((failing // 256).tolist())) == [0, 1, 2]
+        # the word coming in: a smaller row stays, a larger one and all ones give way, the same row's structural code stays
+        first = int(failing[0])
+        assert ic.pivots(bdiag, f, (2 << 2) | ic.NO_DIAG)[1] == (2 << 2) | ic.NO_DIAG
+        assert ic.pivots(bdiag, f, ((n + 5) << 2) | ic.BAD_DIAG)[1] == word
+        for code in (ic.NO_DIAG, ic.BAD_DIAG):
+            assert ic.pivots(bdiag, f, (first << 2) | code)[1] == (first << 2) | code
+
+
+def test_trisweep_and_apply_chain_restatements(kernel_cases):
+    differ = 0
+    for n in ic.RAGGED_SIZES:
+        rowptr, cols, vals = ic.ragged(n)
+        lower = np.array([np.sum(cols[rowptr[i]:rowptr[i + 1]] < i) for i in range(n)])
+        upper = np.array([np.sum(cols[rowptr[i]:rowptr[i + 1]] > i) for i in range(n)])
+        assert np.array_equal(lower, np.minimum(np.arange(n), (7 * np.arange(n)) % 20))
+        assert np.array_equal(upper, np.minimum(n - 1 - np.arange(n), (5 * np.arange(n)) % 19))
+        if n >= 127:
+            for lanes in ic.LANES[1:]:                           # part lengths below, at and above the lane count, and 2 lanes + 1
+                assert {lanes - 1, lanes, lanes + 1, 2 * lanes + 1} <= set(lower.tolist()) & set(upper.tolist()), (n, lanes)
+        bp, bcols, brows, bdiag, bmap, f, word = ic.block_of_split(rowptr, cols, vals, n)
+        rng = np.random.default_rng(n)
+        r, x = rng.uniform(-1, 1, n), rng.uniform(-1, 1, n)
+        dinv = 1.0 / f[bdiag]
+        for up in (0, 1):
+            outs = [ic.trisweep(bp, bcols, bdiag, f, r, x, dinv, up, lanes) for lanes in ic.LANES]
+            L, U, d = ic.split_factors(bp, bcols, f)
+            want = (r - pc.matvec(*(U if up else L), x)) / d if n > 1 else r / d
+            for out in outs:
+                assert np.allclose(out, want, rtol=1e-12, atol=1e-12 * np.abs(want).max()), (n, up)
+            rows = [i for i in range(n) if len({int(pc.bits(out[i:i + 1])[0]) for out in outs}) == 4]
+            differ += len(rows)
+            assert np.array_equal(pc.bits(ic.trisweep(bp, bcols, bdiag, f, r, None, dinv, up, 4)), pc.bits(r * dinv))
+            assert np.array_equal(pc.bits(ic.trisweep(bp, bcols, bdiag, f, r, None, None, up, 1)), pc.bits(r))
+        for s in (1, 3):
+            got = ic.apply_chain(bp, bcols, bdiag, f, dinv, r, s, 1)
+            want = ic.apply(bp, bcols, f, r, s)
+            assert np.allclose(got, want, rtol=1e-12, atol=1e-12 * np.abs(want).max()), (n, s)
+    print(f"{differ} (size, part, row) triples on which lanes 1, 2, 4 and 8 give four different bit patterns")
+    assert differ >= 1
+    for name in ("arrow", "banded16", "convdiff16x16", "asymmetric"):
+        matrix = kernel_cases[name]
+        n = len(matrix[0]) - 1
+        ref = ic.block_reference(matrix, [0, n], 0)
+        f = ref["f"][3]
+        dinv, word = ic.pivots(ref["bdiag"], f)
+        assert word == ic.NO_FAILURE
+        r = np.random.default_rng(3).uniform(-1, 1, n)
+        for s in (1, 2, 3, 16):
+            want = ic.apply(ref["bp"], ref["bc"], f, r, s)
+            for lanes in ic.LANES:
+                got = ic.apply_chain(ref["bp"], ref["bc"], ref["bdiag"], f, dinv, r, s, lanes)
+                assert lanes > 1 or np.allclose(got, want, rtol=1e-12, atol=1e-12 * np.abs(want).max()), (name, s)
+                assert np.allclose(got, want, rtol=1e-10, atol=1e-10 * np.abs(want).max()), (name, s, lanes)
