@@ -22,6 +22,12 @@ def trace(path, nbytes, last):
     mean = sum(us) / len(us)
     print(f"launches_total={len(rows)} last{len(tail)}: kernel={names} mean_us={mean:.2f} min_us={min(us):.2f} max_us={max(us):.2f} "
           f"bytes={nbytes} GB/s={nbytes / mean / 1e3:.1f}")
+    # launches of one matrix alternate their sweep direction (HPCLA_SPMV_SWEEP): the two parities of the launch index apart
+    for parity in (0, 1):
+        sel = [u for i, u in enumerate(us, len(rows) - len(tail)) if i % 2 == parity]
+        if sel:
+            print(f"  launch index {'even' if parity == 0 else 'odd'}: n={len(sel)} mean_us={sum(sel) / len(sel):.2f} "
+                  f"min_us={min(sel):.2f} max_us={max(sel):.2f}")
 
 
 def pmc(path, last):

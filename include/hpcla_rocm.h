@@ -152,15 +152,36 @@ int hpcla_spmv_block_order_hint(const void *rowptr, int group);
 /* Plan-time choice of that order BY MEASUREMENT (run once per structure, next to the VectorPlan build of
  * src/sparse.jl:1875-1984, never inside a timed or captured region: it synchronises): times the split-column SpMV of
  * this matrix -- the arguments of hpcla_spmv_split_f64_*, results discarded into `y_scratch` (nrows doubles) -- under the
- * natural order and groups of 8 / 32 / 64 row blocks, interleaved over four rounds of four launches each, keeps the
- * fastest registered for `rowptr` (the natural order unless a grouped one is >= 1 % faster) and returns it in
- * *chosen_group (1 = natural).  Matrices below 4096 row blocks keep the natural order unmeasured. */
+ * natural order and groups of 8 / 32 / 64 row blocks, interleaved over one warm-up round of two launches and five
+ * counted rounds of eight launches each (168 launches, with the alternating sweep below active), keeps the winner by
+ * hpcla_block_order_decide registered for `rowptr` and returns it in *chosen_group (1 = natural).  Matrices below 4096
+ * row blocks keep the natural order unmeasured. */
 int hpcla_spmv_tune_block_order_f64_i32(const int32_t *rowptr, const int32_t *colval_split, const double *nzval,
                                         const double *x_own, const double *x_ghost, int64_t n_own, double *y_scratch,
                                         int64_t nrows, int64_t nnz, int index_base, void *stream, int *chosen_group);
 int hpcla_spmv_tune_block_order_f64_i64(const int64_t *rowptr, const int64_t *colval_split, const double *nzval,
                                         const double *x_own, const double *x_ghost, int64_t n_own, double *y_scratch,
                                         int64_t nrows, int64_t nnz, int index_base, void *stream, int *chosen_group);
+
+/* The tuner's decision rule alone (host code, no device work).  ms[c * n_rounds + r] is the time of candidate c in counted
+ * round r; candidate 0 is the natural order.  A grouped candidate is kept only if it beat the natural order in EVERY
+ * round (compared pair by pair within the round) and the median of its ratios to the natural order is <= 0.99; of those
+ * the smallest median wins, the first on a tie; otherwise *chosen_index = 0.  Null pointers, n_cand < 1, n_rounds
+ * outside 1 ... 64 and times that are not positive and finite are HPCLA_ERR_INVALID. */
+int hpcla_block_order_decide(const float *ms, int n_cand, int n_rounds, int *chosen_index);
+
+/* Sweep direction of repeated products (no reference counterpart).  A plain SpMV launch over a contiguous run of row
+ * blocks -- every entry above without a block list, every index form, with or without the dot epilogue -- that repeats
+ * the calling thread's last such launch (same rowptr, nzval, nrows and run) walks the run in the opposite direction, so
+ * that it starts on the lines the last launch left in the Infinity Cache and the L2s; every row block stays on its XCD.
+ * Anything else starts forwards.  Results are bit-identical in both directions (each row is still one sequential sum,
+ * dot partials stay indexed by row block).  Listed launches and the fused distributed launch always go forwards.
+ * mode: 0 every launch forwards, 1 alternate, -1 back to the default (alternate); process-wide.  The library reads no
+ * environment variable for it: the Python host layer applies HPCLA_SPMV_SWEEP=forward|alternate through this call when
+ * it loads the library.  hpcla_spmv_last_sweep: *reversed = 1 if the calling thread's last plain contiguous launch went
+ * downwards, else 0 (also before any launch). */
+int hpcla_set_spmv_sweep(int mode);
+int hpcla_spmv_last_sweep(int *reversed);
 
 /* Plan-time helpers (run once per (A, x.partition), cached with the VectorPlan like
  * _vector_plan_cache, src/HPCLinearAlgebra.jl:133).

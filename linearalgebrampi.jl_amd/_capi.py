@@ -55,6 +55,9 @@ _SIGNATURES = {
     "hpcla_spmv_longrows_f64_i32": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _vp],
     "hpcla_spmv_longrows_f64_i64": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _vp],
     "hpcla_spmv_block_order_hint": [_vp, _i32],
+    "hpcla_block_order_decide": [_vp, _i32, _i32, _vp],
+    "hpcla_set_spmv_sweep": [_i32],
+    "hpcla_spmv_last_sweep": [_vp],
     "hpcla_spmv_tune_block_order_f64_i32": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp],
     "hpcla_spmv_tune_block_order_f64_i64": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp],
     "hpcla_spmv_tune_block_order_cols16_f64_i32": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i64, _i64, _vp, _vp],
@@ -441,7 +444,16 @@ def load() -> ctypes.CDLL:
         fn.argtypes = argtypes
         fn.restype = _RESTYPES.get(name, ctypes.c_int)
     _lib = lib
+    apply_spmv_sweep_env()
     return lib
+
+
+def apply_spmv_sweep_env() -> None:
+    """``HPCLA_SPMV_SWEEP=forward`` keeps every SpMV launch of this process forwards (the OFF leg of A/B measurements of the
+    alternating sweep direction, csrc/spmv.hip next_sweep); ``alternate`` or unset: the library's default.  Applied when the
+    library is loaded, through hpcla_set_spmv_sweep: the library itself reads no environment variable for it."""
+    want = os.environ.get("HPCLA_SPMV_SWEEP", "alternate").strip().lower()
+    call("hpcla_set_spmv_sweep", 0 if want.startswith("f") else -1)
 
 
 def last_error() -> str:

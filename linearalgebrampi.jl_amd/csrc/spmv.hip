@@ -113,8 +113,10 @@ struct BlockSel {
     int64_t n_first;
     int64_t n_run;               // length of the contiguous run the group order applies to (plain: the launch; WAIT: n_first)
     int32_t group_log2;          // > 0: XCD-grouped order of the contiguous run, groups of 2^group_log2 row blocks
-    int32_t nt_y;                // != 0: y is stored non-temporally (row-gather kernel; see spmv_nt_y below)
+    int32_t nt_y;                // flag word: BS_NT_Y, BS_REVERSED
 };
+constexpr int32_t BS_NT_Y = 1;       // y is stored non-temporally (row-gather kernel; see spmv_nt_y below)
+constexpr int32_t BS_REVERSED = 2;   // plain contiguous launches: the run is walked downwards (reversed_index, next_sweep below)
 
 // XCD-grouped order of a contiguous run of n row blocks.  The hardware deals workgroups to the 8 XCDs round-robin by
 // workgroup id, so in the natural order block b runs on XCD b % 8 and the x lines two blocks shared are fetched into
@@ -133,6 +135,19 @@ __device__ __forceinline__ int64_t xcd_group_index(int64_t b, int64_t n, int gro
     return ((((q >> group_log2) << NUM_XCD_LOG2) + xcd) << group_log2) + (q & (((int64_t)1 << group_log2) - 1));
 }
 
+// Reversed walk of a contiguous run of n row blocks (sweep direction, see next_sweep).  Workgroup b = 8 q + xcd takes the
+// position that the LAST workgroup of its XCD but q takes forwards: the sequence of eights is reversed, the residue is
+// not.  XCD `xcd` owns the positions xcd, xcd + 8, ... < n, (n - xcd + 7) / 8 of them, and its q-th workgroup takes the
+// q-th from the end -- a bijection on [0, n) for every n (a ragged last eight included: the XCDs past it simply own one
+// position less).  Composed IN FRONT of xcd_group_index: position c runs on XCD c % 8 in both directions, so every row
+// block stays on the XCD it ran on forwards, for every n and every group size, tail included; the launch walks the same
+// moving window downwards (the ragged tail of the grouped order first, then the spans from the last to the first).
+__device__ __forceinline__ int64_t reversed_index(int64_t b, int64_t n)
+{
+    const int64_t xcd = b & ((1 << NUM_XCD_LOG2) - 1), q = b >> NUM_XCD_LOG2;
+    return ((((n - xcd + ((1 << NUM_XCD_LOG2) - 1)) >> NUM_XCD_LOG2) - 1 - q) << NUM_XCD_LOG2) + xcd;
+}
+
 template <bool WAIT>
 __device__ __forceinline__ int64_t select_block(const BlockSel &bs, bool &wait, int lead)
 {
@@ -147,7 +162,8 @@ __device__ __forceinline__ int64_t select_block(const BlockSel &bs, bool &wait, 
         return bs.list ? (int64_t)bs.list[b - bs.n_first] : bs.base + (b - bs.n_first);
     }
     if (bs.list) return (int64_t)bs.list[b];
-    return bs.base + (bs.group_log2 > 0 ? xcd_group_index(b, bs.n_run, bs.group_log2) : b);
+    const int64_t c = (bs.nt_y & BS_REVERSED) ? reversed_index(b, bs.n_run) : b;
+    return bs.base + (bs.group_log2 > 0 ? xcd_group_index(c, bs.n_run, bs.group_log2) : c);
 }
 
 // Fused x.y epilogue (CG's p.Ap): every workgroup leaves the
@@ -398,7 +414,7 @@ __global__ __launch_bounds__(RPB) void spmv_rowgather_kernel(
             __builtin_amdgcn_wave_barrier();
         }
         if (lane < nrw && !(LONGR && is_long)) {
-            if (bs.nt_y) __builtin_nontemporal_store(acc, y + rw + lane);
+            if (bs.nt_y & BS_NT_Y) __builtin_nontemporal_store(acc, y + rw + lane);
             else y[rw + lane] = acc;
         } else if (LONGR && lane < nrw) {
             // a row left to the long-row kernels: NaN now, its tree sum over it later in stream order.  A qualifying row the
@@ -643,6 +659,34 @@ static int spmv_nt_y(bool /*with_dot*/)
     return on;
 }
 
+// Sweep direction of repeated products.  A product of a large matrix streams far more than the 256 MiB Infinity Cache
+// holds, so a launch that starts where the last one started finds nothing of it on die; one that walks the run DOWNWARDS
+// starts on the lines the last launch touched last.  A plain launch over a contiguous run (no block list; the fused
+// distributed launch has an order of its own) therefore alternates its direction when it repeats the calling thread's last
+// such launch: same rowptr, nzval, nrows and run.  Anything else starts forwards, so two matrices multiplied in turn keep
+// the forward order.  One thread_local record: no map, no finaliser, no lock; rank-hosting threads do not see each other.
+// hpcla_set_spmv_sweep(0) keeps every launch forwards (the host layer calls it for HPCLA_SPMV_SWEEP=forward when it loads
+// the library, like its other plan switches).  Every order is a bijection: same bits.
+enum { SWEEP_FORWARD = 0, SWEEP_ALTERNATE = 1 };
+static std::atomic<int> g_sweep_mode{SWEEP_ALTERNATE};
+static int sweep_mode() { return g_sweep_mode.load(std::memory_order_relaxed); }
+
+struct SweepRecord {
+    const void *rowptr, *nzval;
+    int64_t nrows, base, len;
+    int reversed;
+};
+static thread_local SweepRecord t_sweep = {nullptr, nullptr, 0, 0, 0, 0};
+
+static int next_sweep(const void *rowptr, const void *nzval, int64_t nrows, int64_t base, int64_t len)
+{
+    SweepRecord &t = t_sweep;
+    const bool again = t.rowptr == rowptr && t.nzval == nzval && t.nrows == nrows && t.base == base && t.len == len;
+    const int reversed = (again && sweep_mode() == SWEEP_ALTERNATE) ? !t.reversed : 0;
+    t = SweepRecord{rowptr, nzval, nrows, base, len, reversed};
+    return reversed;
+}
+
 // (I: an index policy -- int32_t / int64_t arrays, or Cols16: Int32 row pointers with the plan's 16-bit column copy)
 template <typename I>
 static int spmv_launch(const typename IndexPolicy<I>::row_t *rowptr, const typename IndexPolicy<I>::col_t *colval,
@@ -682,16 +726,19 @@ static int spmv_launch(const typename IndexPolicy<I>::row_t *rowptr, const typen
     using IP = IndexPolicy<I>;
     const bool aligned = (reinterpret_cast<uintptr_t>(colval) % (IP::VEC * sizeof(typename IP::col_t)) == 0) &&
                          (reinterpret_cast<uintptr_t>(nzval) % 32 == 0);
+    // the narrow form has no fallback kernel of its own: the callers send misaligned arrays down the Int32 path (cols16_usable)
+    if (std::is_same<I, Cols16>::value && !aligned)
+        return set_error(HPCLA_ERR_INVALID, "spmv: 16-bit columns need a 16-byte aligned copy and 32-byte aligned nzval");
+    // a listed launch keeps the list's order and leaves the thread's sweep record alone
+    const int reversed = block_list ? 0 : next_sweep(rowptr, nzval, nrows, block_base, launch_blocks);
     const BlockSel bs{block_list, block_base, nullptr, 0, 0, launch_blocks, block_list ? 0 : block_order_of(rowptr),
-                      spmv_nt_y(dot_partial != nullptr)};
+                      spmv_nt_y(dot_partial != nullptr) | (reversed ? BS_REVERSED : 0)};
     HaloWait nowait;
     memset(&nowait, 0, sizeof(nowait));
     PushArgs nopush;
     memset(&nopush, 0, sizeof(nopush));
     if constexpr (std::is_same<I, Cols16>::value) {
-        // the narrow form has no fallback kernel of its own: the callers send misaligned arrays down the Int32 path (cols16_usable)
-        if (!aligned) return set_error(HPCLA_ERR_INVALID, "spmv: 16-bit columns need a 16-byte aligned copy and 32-byte aligned nzval");
-        if (pat)       // the plan holds a table of repeating block patterns: the same launch in the pattern form
+        if (pat)     // the plan holds a table of repeating block patterns: the same launch in the pattern form
             spmv_rowgather_kernel<Pat16, false, false><<<grid, block, 0, s>>>(
                 rowptr, colval, nzval, x_own, nullptr, 0, y, nrows, nnz, index_base, bs, dot_partial, nowait, nopush, 0, *pat);
         else
@@ -866,12 +913,55 @@ static void set_block_order(const void *rowptr, int group_log2)
     g_order_count.store((int)g_order.size(), std::memory_order_relaxed);
 }
 
+// The tuner's decision rule, on the timings alone (host code: tested without a GPU through hpcla_block_order_decide).
+// ms[c * n_rounds + r]: candidate c in counted round r; candidate 0 is the natural order.  Every grouped candidate is
+// compared with the natural order PAIR BY PAIR within a round -- clocks and the neighbours on the box drift between
+// rounds, hardly inside one -- and stays in the race only if it won EVERY round and the median of its ratios is at most
+// 0.99 (the 1 % the rule always asked for).  Of those the smallest median ratio wins, the first on a tie; none: natural.
+constexpr int DECIDE_MAX_ROUNDS = 64;
+static int block_order_decide(const float *ms, int n_cand, int n_rounds, int *chosen_index)
+{
+    if (!ms || !chosen_index || n_cand < 1 || n_rounds < 1 || n_rounds > DECIDE_MAX_ROUNDS)
+        return set_error(HPCLA_ERR_INVALID, "block_order_decide: null table, or n_cand < 1, or n_rounds outside 1 ... 64");
+    for (int i = 0; i < n_cand * n_rounds; ++i)
+        if (!(ms[i] > 0.0f) || ms[i] > 3.0e38f) return set_error(HPCLA_ERR_INVALID, "block_order_decide: times must be positive and finite");
+    int best = 0;
+    double best_ratio = 0.99;
+    bool have = false;
+    for (int c = 1; c < n_cand; ++c) {
+        double ratio[DECIDE_MAX_ROUNDS];
+        bool every_round = true;
+        for (int r = 0; r < n_rounds; ++r) {
+            ratio[r] = (double)ms[c * n_rounds + r] / (double)ms[r];
+            every_round = every_round && ratio[r] < 1.0;
+        }
+        if (!every_round) continue;
+        for (int i = 1; i < n_rounds; ++i)                   // insertion sort: a handful of rounds
+            for (int j = i; j > 0 && ratio[j] < ratio[j - 1]; --j) {
+                const double t = ratio[j];
+                ratio[j] = ratio[j - 1];
+                ratio[j - 1] = t;
+            }
+        const double med = (n_rounds & 1) ? ratio[n_rounds / 2] : 0.5 * (ratio[n_rounds / 2 - 1] + ratio[n_rounds / 2]);
+        if (have ? med < best_ratio : med <= best_ratio) {
+            best = c;
+            best_ratio = med;
+            have = true;
+        }
+    }
+    *chosen_index = best;
+    return HPCLA_OK;
+}
+
 // Plan-time choice of the block order BY MEASUREMENT: the same launch the plan will make, timed under the natural order
-// and groups of 8 / 32 / 64 row blocks, interleaved over a few rounds; the fastest stays registered for `rowptr`.  The
-// natural order is kept unless a grouped one is >= 1 % faster.  (A model of which x lines two XCDs share predicts
+// and groups of 8 / 32 / 64 row blocks, interleaved over a few rounds; the winner by block_order_decide stays registered
+// for `rowptr`.  (A model of which x lines two XCDs share predicts
 // config 4's planes and the 256^3 cube, but not that 4096- and 8192-wide 2-D grids gain 3 % from groups of 32 / 64
 // although their neighbours already share an XCD in the natural order, nor that a 1000-wide grid loses 1 % with
 // groups of 64 -- profiles/r03_spmv_xcd_group_order.log -- so the choice is measured, like an FFT plan's.)
+// A timed window is TUNE_REPS = 8 launches (milliseconds, not the 0.7 ms of four: profiles/MEASUREMENTS_sweep_direction.md),
+// an even number, so under the alternating sweep -- which is active here as in the plan's use -- every window holds as
+// many downward launches as upward ones.  One warm-up round of two launches per candidate (clocks, TLBs), then five counted.
 // (I: an index policy, see IndexPolicy.  run_base >= 0: the launches cover the contiguous run of run_blocks row blocks from
 //  run_base -- the interior run of a plan whose boundary blocks take another kernel form -- instead of every block.)
 template <typename I>
@@ -889,41 +979,54 @@ static int tune_block_order(const typename IndexPolicy<I>::row_t *rowptr, const 
     if (run_base >= 0 && (run_blocks <= 0 || run_base + run_blocks > n_blocks))
         return run_blocks == 0 ? HPCLA_OK : set_error(HPCLA_ERR_INVALID, "spmv_tune_block_order: block run out of bounds");
     if (!y_scratch) return set_error(HPCLA_ERR_INVALID, "spmv_tune_block_order: null scratch vector");
-    constexpr int NC = 4, ROUNDS = 4, REPS = 4;            // round 0 warms up (clocks, TLBs) and is not counted
+    constexpr int NC = 4, ROUNDS = 5, TUNE_REPS = 8, WARM_REPS = 2;     // 4 x (2 + 5 x 8) = 168 launches
+    static_assert(TUNE_REPS % 2 == 0 && WARM_REPS % 2 == 0, "every window sees both sweep directions equally");
     const int cand[NC] = {0, 3, 5, 6};
-    float ms[NC][ROUNDS];
+    float ms[NC * ROUNDS], warm;
     hipEvent_t e0, e1;
     HPCLA_CHECK_HIP(hipEventCreate(&e0));
     HPCLA_CHECK_HIP(hipEventCreate(&e1));
     hipStream_t s = as_stream(stream);
     int rc = HPCLA_OK;
-    for (int r = 0; r < ROUNDS && rc == HPCLA_OK; ++r)
+    for (int r = -1; r < ROUNDS && rc == HPCLA_OK; ++r)    // round -1 warms up and is not counted
         for (int c = 0; c < NC && rc == HPCLA_OK; ++c) {
             set_block_order(rowptr, cand[c]);
             if (hipEventRecord(e0, s) != hipSuccess) { rc = set_error(HPCLA_ERR_HIP, "spmv_tune_block_order: event"); break; }
-            for (int i = 0; i < REPS && rc == HPCLA_OK; ++i)
+            for (int i = 0; i < (r < 0 ? WARM_REPS : TUNE_REPS) && rc == HPCLA_OK; ++i)
                 rc = spmv_launch<I>(rowptr, colval_split, nzval, x_own, x_ghost, n_own, true, y_scratch, nrows, nnz,
                                     index_base, nullptr, run_base >= 0 ? run_blocks : 0, stream, nullptr, run_base, pat);
             if (rc != HPCLA_OK) break;
             if (hipEventRecord(e1, s) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
-                hipEventElapsedTime(&ms[c][r], e0, e1) != hipSuccess)
+                hipEventElapsedTime(r < 0 ? &warm : &ms[c * ROUNDS + r], e0, e1) != hipSuccess)
                 rc = set_error(HPCLA_ERR_HIP, "spmv_tune_block_order: timing");
         }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     set_block_order(rowptr, 0);
     if (rc != HPCLA_OK) return rc;
-    float best_t[NC];
-    for (int c = 0; c < NC; ++c) {                         // median of the three counted rounds
-        float a = ms[c][1], b = ms[c][2], d = ms[c][3];
-        best_t[c] = a > b ? (b > d ? b : (a > d ? d : a)) : (a > d ? a : (b > d ? d : b));
-    }
     int best = 0;
-    for (int c = 1; c < NC; ++c)
-        if (best_t[c] < best_t[best]) best = c;
-    if (best != 0 && best_t[best] > 0.99f * best_t[0]) best = 0;
+    if ((rc = block_order_decide(ms, NC, ROUNDS, &best)) != HPCLA_OK) return rc;
     set_block_order(rowptr, cand[best]);
     if (chosen_group) *chosen_group = 1 << cand[best];
+    return HPCLA_OK;
+}
+
+HPCLA_API int hpcla_block_order_decide(const float *ms, int n_cand, int n_rounds, int *chosen_index)
+{
+    return block_order_decide(ms, n_cand, n_rounds, chosen_index);
+}
+
+HPCLA_API int hpcla_set_spmv_sweep(int mode)
+{
+    if (mode < -1 || mode > 1) return set_error(HPCLA_ERR_INVALID, "set_spmv_sweep: mode must be -1 (the default), 0 (forward) or 1 (alternate)");
+    g_sweep_mode.store(mode < 0 ? (int)SWEEP_ALTERNATE : mode, std::memory_order_relaxed);
+    return HPCLA_OK;
+}
+
+HPCLA_API int hpcla_spmv_last_sweep(int *reversed)
+{
+    if (!reversed) return set_error(HPCLA_ERR_INVALID, "spmv_last_sweep: null output");
+    *reversed = t_sweep.reversed;
     return HPCLA_OK;
 }
 

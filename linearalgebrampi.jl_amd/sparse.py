@@ -411,7 +411,7 @@ class VectorPlan:
                 sys.stderr.write(f"hpcla: block-order measurement failed ({exc}); natural order\n")
                 chosen = ctypes.c_int(1)
             self.block_group = int(chosen.value)
-            self.block_group_measured = (A.nrows_local + 255) // 256 >= 4096      # the tuner's own threshold (64 launches)
+            self.block_group_measured = (A.nrows_local + 255) // 256 >= 4096      # the tuner's own threshold (168 launches)
             # the tuner left it registered for the rowptr array it was given: the matrix's, or this plan's Int32 copy
             owner = self if self.narrowed else A
             owner._block_order_hint = A._block_order_hint = self.block_group
