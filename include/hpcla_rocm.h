@@ -302,6 +302,68 @@ int hpcla_sparse_diag_f64_i64(const int64_t *rowptr, const int64_t *colval, cons
                               int index_base, const int64_t *col_indices, int64_t n_col_indices, int64_t row_start,
                               int reciprocal, double *out, void *stream);
 
+/* ---- COO assembly with a reusable structure: sparse(I, J, V, m, n) on the device (csrc/assemble.hip) --------------
+ * Replaces the host idiom sparse(I, J, V, m, n) + HPCSparseMatrix(A, backend) (src/sparse.jl:398-413) of a loop that
+ * produces new values V on the same (I, J) at every step.  The structure is an inverted index: the caller sorts the keys
+ * (row - row_lo) * ncols + col STABLY (any sort; the library's Python layer uses torch.sort) and keeps the permutation
+ * `perm`; `seg_ptr` cuts the sorted list where the key changes; output entry e is the sum of the values at the positions
+ * perm[seg_ptr[e]] ... perm[seg_ptr[e + 1] - 1], which ascend.  No float atomics anywhere.
+ *
+ * Sum order (it fixes the bits; CH = hpcla_assemble_chunk()).  A segment of L <= CH contributions: s = v[p1];
+ * s = s + v[p2]; ... left to right, started from the first value and not from 0.0, so a lone -0.0 stays -0.0.  L > CH:
+ * consecutive chunks of CH contributions, each summed by that rule, and the partial sums added left to right in chunk
+ * order.  Only adds occur: the result does not depend on contraction, and two calls give the same bits.  A segment
+ * without contributions (the vector form) stores +0.0.
+ *
+ * Positions (seg_ptr, perm) are always 0-based; rows / cols in and rowptr / column ids out carry `index_base`.  The
+ * _i32 / _i64 suffix is the width of seg_ptr and perm (int32 needs the list length <= 2^31 - 1), except for row_starts,
+ * where it is the width of the output.
+ *
+ * keys: key_out[i] = (rows[i] - row_lo) * ncols + cols[i] for a triplet of this rank's rows [row_lo, row_hi); cols NULL
+ *   with ncols 1 is the vector form.  counts_dev (device, 4 words, set here): [0] triplets with a row outside
+ *   [0, nrows_global) or a column outside [0, ncols), [1] the first such position or -1, [2] triplets inside the matrix
+ *   but outside this rank's rows, [3] the first such position or -1.  A refused triplet gets the key INT64_MAX.  Needs
+ *   (row_hi - row_lo) * ncols < 2^63.  No synchronisation.
+ * segments: seg_ptr_out (capacity n + 1) and ukey_out (capacity n; the distinct keys, ascending) from the sorted keys;
+ *   the number of segments returns to the host: synchronises the stream once, like hpcla_compress_columns_*.  `work`:
+ *   hpcla_assemble_work_bytes(n) device bytes.  Elements per workgroup of the scan: hpcla_submatrix_scan_chunk().
+ * row_starts: out[r] = index_base + the first position of keys_sorted whose key is >= r * ncols, for r in [0, nrows]
+ *   (nrows + 1 words).  Over the distinct keys this is rowptr; over the sorted keys of the vector form (ncols 1) it is
+ *   seg_ptr, with an empty segment for every index nothing contributes to.  No synchronisation.
+ * columns: colidx_out[u] = ukey[u] mod ncols + index_base.  No synchronisation.
+ * values: out[e] for e in [0, nseg).  The rank's value list is [vals (n_own) | ghost (n_ghost)]: a position p of perm
+ *   reads vals[p] if p < n_own, else ghost[p - n_own]; a position outside both reads as +0.0.  n_in: the length of perm.
+ *   A workgroup owns hpcla_assemble_run() consecutive output entries and walks its span of the list in passes of
+ *   hpcla_assemble_pass() contributions (tests cross both).  max_len: an upper bound of the segment lengths, or -1 when
+ *   unknown; when it exceeds CH (or is -1) a first launch sums the chunks of the long segments on separate waves into
+ *   `work` (hpcla_assemble_values_work_bytes(n_in) device bytes, else it may be NULL), and the long entries add their
+ *   partial sums in chunk order.  A max_len below the true maximum leaves +0.0 in the longer entries.  Plain stores, no
+ *   read-back, no synchronisation. */
+int64_t hpcla_assemble_chunk(void);
+int64_t hpcla_assemble_run(void);
+int64_t hpcla_assemble_pass(void);
+int64_t hpcla_assemble_work_bytes(int64_t n);
+int64_t hpcla_assemble_values_work_bytes(int64_t n_in);
+int hpcla_assemble_keys(const int64_t *rows, const int64_t *cols, int64_t n, int64_t row_lo, int64_t row_hi,
+                        int64_t nrows_global, int64_t ncols, int index_base, int64_t *key_out, int64_t *counts_dev,
+                        void *stream);
+int hpcla_assemble_segments_i32(const int64_t *keys_sorted, int64_t n, int32_t *seg_ptr_out, int64_t *ukey_out,
+                                int64_t *nnz_out_host, void *work, void *stream);
+int hpcla_assemble_segments_i64(const int64_t *keys_sorted, int64_t n, int64_t *seg_ptr_out, int64_t *ukey_out,
+                                int64_t *nnz_out_host, void *work, void *stream);
+int hpcla_assemble_row_starts_i32(const int64_t *keys_sorted, int64_t n, int64_t nrows, int64_t ncols, int index_base,
+                                  int32_t *out, void *stream);
+int hpcla_assemble_row_starts_i64(const int64_t *keys_sorted, int64_t n, int64_t nrows, int64_t ncols, int index_base,
+                                  int64_t *out, void *stream);
+int hpcla_assemble_columns(const int64_t *ukey, int64_t nnz, int64_t ncols, int index_base, int64_t *colidx_out,
+                           void *stream);
+int hpcla_assemble_values_f64_i32(const int32_t *seg_ptr, const int32_t *perm, int64_t nseg, int64_t n_in,
+                                  const double *vals, int64_t n_own, const double *ghost, int64_t n_ghost, int64_t max_len,
+                                  double *out, void *work, void *stream);
+int hpcla_assemble_values_f64_i64(const int64_t *seg_ptr, const int64_t *perm, int64_t nseg, int64_t n_in,
+                                  const double *vals, int64_t n_own, const double *ghost, int64_t n_ghost, int64_t max_len,
+                                  double *out, void *work, void *stream);
+
 /* ---- SpGEMM local product (sparse x sparse): replaces the CPU SparseArrays multiply inside
  * Base.:*(A::HPCSparseMatrix, B::HPCSparseMatrix) (`CT = plan.AT * A_csc`, src/sparse.jl:991-1059).
  * G = the rows of B named by A.col_indices, gathered by the MatrixPlan (src/sparse.jl:554-978), as

@@ -35,6 +35,9 @@ Layout
                      eigensolver's rotate for both restarts
   qr.py              qr(), lstsq(): tall-skinny Householder QR (TSQR) of a dense HPCMatrix of k <= 32 columns, Q formed from the
                      stored reflectors, and dense least squares through the augmented block [X b] (csrc/qr.hip)
+  assemble.py        assembly_plan(), sparse_from_coo(): Julia's sparse(I, J, V, m, n) on the device with a reusable structure: a
+                     stable sort and an inverted index once per (I, J), then one kernel per new V that sums every entry's
+                     contributions in a fixed order without atomics (csrc/assemble.hip); off-rank triplets travel by a halo plan
   indexing.py        v[a:b], X[r, c], A[r, c], A[:, k], diag(A) and SubmatrixPlan (csrc/submatrix.hip)
   transpose.py matmat.py addition.py repartition.py   the SURVEY 8f "next" rows and their plans
 
@@ -76,6 +79,7 @@ from .transpose import (HostTransposeStructure, TransposedHPCSparseMatrix, Trans
                         transpose)
 from .addition import add_scaled_identity, sparse_add
 from .indexing import SubmatrixPlan, diag, get_submatrix_plan
+from .assemble import AssemblyPlan, assembly_plan, sparse_from_coo
 from .repartition import (RangePlan, SparseRepartitionPlan, clear_repartition_cache, exchange_ranges,
                           get_sparse_repartition_plan, get_vector_repartition_plan, repartition)
 

@@ -310,6 +310,20 @@ _SIGNATURES = {
     "hpcla_sparse_column_i64": [_i32, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp],
     "hpcla_sparse_diag_f64_i32": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _vp],
     "hpcla_sparse_diag_f64_i64": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _vp],
+    # COO assembly with a reusable structure (hp.assembly_plan, csrc/assemble.hip)
+    "hpcla_assemble_chunk": [],
+    "hpcla_assemble_run": [],
+    "hpcla_assemble_pass": [],
+    "hpcla_assemble_work_bytes": [_i64],
+    "hpcla_assemble_values_work_bytes": [_i64],
+    "hpcla_assemble_keys": [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp],
+    "hpcla_assemble_segments_i32": [_vp, _i64, _vp, _vp, _vp, _vp, _vp],
+    "hpcla_assemble_segments_i64": [_vp, _i64, _vp, _vp, _vp, _vp, _vp],
+    "hpcla_assemble_row_starts_i32": [_vp, _i64, _i64, _i64, _i32, _vp, _vp],
+    "hpcla_assemble_row_starts_i64": [_vp, _i64, _i64, _i64, _i32, _vp, _vp],
+    "hpcla_assemble_columns": [_vp, _i64, _i64, _i32, _vp, _vp],
+    "hpcla_assemble_values_f64_i32": [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp],
+    "hpcla_assemble_values_f64_i64": [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp],
     "hpcla_digest_i32": [_vp, _i64, _vp, _vp],
     "hpcla_digest_i64": [_vp, _i64, _vp, _vp],
     "hpcla_poisson2d_nnz": [_i64, _i64, _i64, _i64],
@@ -391,6 +405,11 @@ _RESTYPES = {
     "hpcla_colspace_work_bytes": _i64,
     "hpcla_submatrix_work_bytes": _i64,
     "hpcla_submatrix_scan_chunk": _i64,
+    "hpcla_assemble_chunk": _i64,
+    "hpcla_assemble_run": _i64,
+    "hpcla_assemble_pass": _i64,
+    "hpcla_assemble_work_bytes": _i64,
+    "hpcla_assemble_values_work_bytes": _i64,
     "hpcla_poisson2d_nnz": _i64,
     "hpcla_poisson3d_nnz": _i64,
     "hpcla_spgemm_bin_cap": _i64,
