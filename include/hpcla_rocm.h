@@ -302,6 +302,68 @@ int hpcla_sparse_diag_f64_i64(const int64_t *rowptr, const int64_t *colval, cons
                               int index_base, const int64_t *col_indices, int64_t n_col_indices, int64_t row_start,
                               int reciprocal, double *out, void *stream);
 
+/* ---- index-set selection: A[rows, cols] for index lists, v[idx], v[idx] = src (csrc/select.hip) -------------------
+ * Replaces Base.getindex(A::HPCSparseMatrix, row_idx::HPCVector{Int}, col_idx::HPCVector{Int}) (src/indexing.jl:1654-1815:
+ * the Dict from column to position :1675-1678, the walk of every selected row through it, extract_sparse_row :1743-1765),
+ * Base.getindex(v, idx) (:1339-1460) and Base.setindex!(v, src, idx) (:1871-1985).  The reference returns a DENSE
+ * HPCMatrix (:1640-1644); these entries build the CSR of a sparse result.  The caller gathers the ranks' column lists
+ * (:1662, 1821-1844), sorts the list stably with its positions (any sort) and refuses duplicates; the library does the rest.
+ *
+ * A kept entry goes to rowptr'[r] + (the number of kept entries of its row with a smaller new column): new columns are
+ * distinct within a row, so the ranks are unique, columns ascend within every output row and nothing but integers is
+ * compared.  Values are moved by size (elem_bytes 8 or 4): every bit survives.  `rows`, `sorted_pos` and `src_out` are
+ * 0-based positions whatever `index_base` is; rowptr / colval (in and out), col_indices_src, sorted_cols and
+ * col_indices_out carry `index_base`.
+ *
+ * structure: `rows` (nsel local rows in output order, repeats allowed; NULL: rows 0 .. nsel - 1), `sorted_cols` (nsorted
+ *   global column ids, ascending, distinct) with `sorted_pos` (the position of each in the caller's list: the new global
+ *   column, in [0, width)); nsorted = -1: all columns in order (new column = old column, width = the matrix's).  Writes
+ *   rowptr_out (nsel + 1) and col_indices_out (capacity min(width, ncomp): the new columns that occur, ascending); returns
+ *   the new nnz, the new compressed column count and the longest kept row to the host: synchronises the stream once.
+ *   Where the new nnz (plus index_base) does not fit the index type, rowptr_out has wrapped: the three host values are
+ *   still returned, the status is HPCLA_ERR_UNSUPPORTED, and rowptr_out must not be used.
+ *   `work`: hpcla_select_work_bytes(nsel, ncomp, width) device bytes; it starts with the table from A's compressed column
+ *   to the result's that `fill` reads, so it must live until the fill has run.
+ * fill: colval_out / nzval_out / src_out (nnz_out entries each; src_out[p] = the position in the source's nzval of output
+ *   entry p).  Three forms by kept row length n: n <= hpcla_select_short_cap() (lane groups), n <= hpcla_select_tile() (a
+ *   workgroup per row, the row in LDS), longer (a workgroup per row, every tile ranked against the whole row: quadratic,
+ *   the slow case).  max_row: the longest kept row as `structure` returned it, or -1 when unknown; the two long forms are
+ *   launched only when it asks for them.  No synchronisation.
+ * values of another matrix of the same structure: out[p] = nzval2[src_out[p]]: hpcla_gather_f64_i64 for 8-byte elements,
+ *   hpcla_gather_b32_i64 for 4-byte ones (x holds nx items; a position outside reads as 0).
+ * take: out[i] = p < n_own ? v[p] : ghost[p - n_own] for p = pos[i] - index_base (outside both: +0.0).
+ * put:  v[p] = src[i] for p = pos[i] - index_base in [0, n_own); positions must be distinct.  _i32 / _i64: the width of pos. */
+int64_t hpcla_select_short_cap(void);
+int64_t hpcla_select_tile(void);
+int64_t hpcla_select_work_bytes(int64_t nsel, int64_t ncomp, int64_t width);
+int hpcla_select_structure_i32(const int32_t *rowptr, const int32_t *colval, int64_t nrows, int64_t nnz,
+                               const int64_t *col_indices_src, int64_t ncomp, const int64_t *rows, int64_t nsel,
+                               const int64_t *sorted_cols, const int64_t *sorted_pos, int64_t nsorted, int64_t width,
+                               int index_base, int32_t *rowptr_out, int64_t *col_indices_out, int64_t *nnz_out_host,
+                               int64_t *ncols_out_host, int64_t *max_row_host, void *work, void *stream);
+int hpcla_select_structure_i64(const int64_t *rowptr, const int64_t *colval, int64_t nrows, int64_t nnz,
+                               const int64_t *col_indices_src, int64_t ncomp, const int64_t *rows, int64_t nsel,
+                               const int64_t *sorted_cols, const int64_t *sorted_pos, int64_t nsorted, int64_t width,
+                               int index_base, int64_t *rowptr_out, int64_t *col_indices_out, int64_t *nnz_out_host,
+                               int64_t *ncols_out_host, int64_t *max_row_host, void *work, void *stream);
+int hpcla_select_fill_i32(int elem_bytes, const int32_t *rowptr, const int32_t *colval, const void *nzval, int64_t nrows,
+                          int64_t nnz, int64_t ncomp, const int64_t *rows, int64_t nsel, const int32_t *rowptr_out,
+                          int64_t nnz_out, int64_t max_row, int index_base, const void *work, int32_t *colval_out,
+                          void *nzval_out, int64_t *src_out, void *stream);
+int hpcla_select_fill_i64(int elem_bytes, const int64_t *rowptr, const int64_t *colval, const void *nzval, int64_t nrows,
+                          int64_t nnz, int64_t ncomp, const int64_t *rows, int64_t nsel, const int64_t *rowptr_out,
+                          int64_t nnz_out, int64_t max_row, int index_base, const void *work, int64_t *colval_out,
+                          void *nzval_out, int64_t *src_out, void *stream);
+int hpcla_gather_b32_i64(const void *x, const int64_t *src, void *out, int64_t n, int64_t nx, int index_base, void *stream);
+int hpcla_select_take_f64_i32(const double *v, int64_t n_own, const double *ghost, int64_t n_ghost, const int32_t *pos,
+                              int64_t n, int index_base, double *out, void *stream);
+int hpcla_select_take_f64_i64(const double *v, int64_t n_own, const double *ghost, int64_t n_ghost, const int64_t *pos,
+                              int64_t n, int index_base, double *out, void *stream);
+int hpcla_select_put_f64_i32(double *v, int64_t n_own, const int32_t *pos, const double *src, int64_t n, int index_base,
+                             void *stream);
+int hpcla_select_put_f64_i64(double *v, int64_t n_own, const int64_t *pos, const double *src, int64_t n, int index_base,
+                             void *stream);
+
 /* ---- COO assembly with a reusable structure: sparse(I, J, V, m, n) on the device (csrc/assemble.hip) --------------
  * Replaces the host idiom sparse(I, J, V, m, n) + HPCSparseMatrix(A, backend) (src/sparse.jl:398-413) of a loop that
  * produces new values V on the same (I, J) at every step.  The structure is an inverted index: the caller sorts the keys

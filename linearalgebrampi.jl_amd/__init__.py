@@ -39,6 +39,10 @@ Layout
                      stable sort and an inverted index once per (I, J), then one kernel per new V that sums every entry's
                      contributions in a fixed order without atomics (csrc/assemble.hip); off-rank triplets travel by a halo plan
   indexing.py        v[a:b], X[r, c], A[r, c], A[:, k], diag(A) and SubmatrixPlan (csrc/submatrix.hip)
+  select.py          select(), take(), put_(), selection_plan(), index_plan(): A[rows, cols], v[idx] and v[idx] = src for index
+                     LISTS (Dirichlet elimination, symmetric permutations, non-contiguous blocks): a column look-up, two scans
+                     and a per-row rank-and-fill that keeps columns ascending (csrc/select.hip); off-rank vector entries
+                     travel by a halo plan
   transpose.py matmat.py addition.py repartition.py   the SURVEY 8f "next" rows and their plans
 
 The directory name contains a dot, so it is imported through the top-level alias module
@@ -80,6 +84,7 @@ from .transpose import (HostTransposeStructure, TransposedHPCSparseMatrix, Trans
 from .addition import add_scaled_identity, sparse_add
 from .indexing import SubmatrixPlan, diag, get_submatrix_plan
 from .assemble import AssemblyPlan, assembly_plan, sparse_from_coo
+from .select import SelectionPlan, VectorIndexPlan, index_plan, put_, select, selection_plan, take
 from .repartition import (RangePlan, SparseRepartitionPlan, clear_repartition_cache, exchange_ranges,
                           get_sparse_repartition_plan, get_vector_repartition_plan, repartition)
 

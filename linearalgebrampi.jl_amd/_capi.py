@@ -324,6 +324,21 @@ _SIGNATURES = {
     "hpcla_assemble_columns": [_vp, _i64, _i64, _i32, _vp, _vp],
     "hpcla_assemble_values_f64_i32": [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp],
     "hpcla_assemble_values_f64_i64": [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp],
+    # index-set selection (hp.select, hp.take, hp.put_, csrc/select.hip)
+    "hpcla_select_short_cap": [],
+    "hpcla_select_tile": [],
+    "hpcla_select_work_bytes": [_i64, _i64, _i64],
+    "hpcla_select_structure_i32": [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp],
+    "hpcla_select_structure_i64": [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp],
+    "hpcla_select_fill_i32": [_i32, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp],
+    "hpcla_select_fill_i64": [_i32, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp],
+    "hpcla_gather_b32_i64": [_vp, _vp, _vp, _i64, _i64, _i32, _vp],
+    "hpcla_select_take_f64_i32": [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _vp],
+    "hpcla_select_take_f64_i64": [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _vp],
+    "hpcla_select_put_f64_i32": [_vp, _i64, _vp, _vp, _i64, _i32, _vp],
+    "hpcla_select_put_f64_i64": [_vp, _i64, _vp, _vp, _i64, _i32, _vp],
     "hpcla_digest_i32": [_vp, _i64, _vp, _vp],
     "hpcla_digest_i64": [_vp, _i64, _vp, _vp],
     "hpcla_poisson2d_nnz": [_i64, _i64, _i64, _i64],
@@ -405,6 +420,9 @@ _RESTYPES = {
     "hpcla_colspace_work_bytes": _i64,
     "hpcla_submatrix_work_bytes": _i64,
     "hpcla_submatrix_scan_chunk": _i64,
+    "hpcla_select_short_cap": _i64,
+    "hpcla_select_tile": _i64,
+    "hpcla_select_work_bytes": _i64,
     "hpcla_assemble_chunk": _i64,
     "hpcla_assemble_run": _i64,
     "hpcla_assemble_pass": _i64,

@@ -153,7 +153,7 @@ def check_values(vals, n_in: int):
     return vals
 
 
-def _raise_together(comm, err: Optional[Exception]) -> None:
+def _raise_together(comm, err: Optional[Exception], what: str = "assembly_plan") -> None:
     """Every rank learns whether any rank refuses and all raise: a rank raising alone would leave the others waiting in the
     next collective (as spgemm_local does for its row limit)."""
     refused = comm_allgather(comm, np.array([1 if err is not None else 0], dtype=np.int64))
@@ -161,7 +161,7 @@ def _raise_together(comm, err: Optional[Exception]) -> None:
         raise err
     if refused.any():
         ranks = np.flatnonzero(refused).tolist()
-        raise ValueError(f"assembly_plan: refused on rank(s) {ranks}; this rank's arguments were accepted")
+        raise ValueError(f"{what}: refused on rank(s) {ranks}; this rank's arguments were accepted")
 
 
 class AssemblyPlan:

@@ -30,6 +30,7 @@
 //   column  one lane per row, one lower-bound search: out[i] = the stored value of column jk, else +0.0.
 #include "common.h"
 #include "scan.h"
+#include "store16.h"
 
 namespace hpcla {
 
@@ -104,26 +105,6 @@ struct ColumnEmit {                       // lut[i] = rank of local column j0 + 
         if (present) col_indices_out[before] = col_indices_src ? col_indices_src[j0 + i] - col_shift : j0 + i;
     }
 };
-
-template <typename T> struct Vec16;
-template <> struct Vec16<uint32_t> { using type = uint4; static constexpr int N = 4; };
-template <> struct Vec16<uint64_t> { using type = ulonglong2; static constexpr int N = 2; };
-template <> struct Vec16<int32_t> { using type = uint4; static constexpr int N = 4; };
-template <> struct Vec16<int64_t> { using type = ulonglong2; static constexpr int N = 2; };
-
-// FILL_V consecutive items at a 16-byte aligned dst
-template <typename T>
-__device__ __forceinline__ void store_run(T *dst, const T (&v)[FILL_V])
-{
-    using V = typename Vec16<T>::type;
-    constexpr int N = Vec16<T>::N;
-#pragma unroll
-    for (int q = 0; q < FILL_V / N; ++q) {
-        V w;
-        __builtin_memcpy(&w, &v[q * N], 16);
-        *reinterpret_cast<V *>(dst + q * N) = w;
-    }
-}
 
 // Output entry e of output row i reads source entry src_start[i] + (e - rowptr'[i]).  COLS: also colval' = lut[colval - j0].
 template <typename I, typename E, bool COLS>

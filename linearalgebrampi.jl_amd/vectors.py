@@ -31,8 +31,16 @@ def current_stream_ptr() -> ctypes.c_void_p:
     return ctypes.c_void_p(_torch().cuda.current_stream().cuda_stream)
 
 
+class DevicePointer(ctypes.c_void_p):
+    """A device pointer that keeps its tensor referenced for as long as the pointer object itself lives, that is, while it
+    sits in the argument list of an entry-point call.  A temporary built inside an argument list (``dptr(x.contiguous())``,
+    ``dptr(upload(a))``) would otherwise die as soon as its pointer is taken, and the caching allocator may hand its block
+    to the NEXT temporary of the same list, whose upload then overwrites it before the entry point is even called.  Nothing
+    outlives the call: no list of recent operands is kept."""
+
+
 def dptr(t) -> ctypes.c_void_p:
-    """Raw device pointer of a torch tensor (None -> NULL)."""
+    """Raw device pointer of a torch tensor (None -> NULL); the returned object owns a reference to the tensor."""
     if t is None:
         return ctypes.c_void_p(0)
     if t.device.type != "cuda":
@@ -40,7 +48,9 @@ def dptr(t) -> ctypes.c_void_p:
         # to_backend(x, cpu_version(b))) is an error, never a silent host fallback
         raise TypeError("operand lives in host memory; this build has no CPU compute path "
                         "(move it with to_backend(x, rocm_backend), or use the reference package on the CPU)")
-    return ctypes.c_void_p(t.data_ptr())
+    p = DevicePointer(t.data_ptr())
+    p.tensor = t
+    return p
 
 
 def rd16(t):
