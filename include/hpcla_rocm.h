@@ -1203,7 +1203,30 @@ int hpcla_pcg_fsai_iterations_f64_i64(
  *                      the join depend on the set of a row's neighbours only.  One index form: the graph's own.
  *   amg_restrictor     r_cj = [agg(j) == row_offset + c] - (T^t A)_cj * s_j on the CSR of T^t A (compressed local columns, their
  *                      global ids, each in 0..ncols and owned): the Petrov-Galerkin restriction T^t (I - A S).
+ * With near-nullspace candidates (hp.amg(A, B=...)), 1 <= k <= 8 columns, k coarse unknowns per aggregate (k * agg + c):
+ *   amg_fit            per aggregate a (its members: members_dev[member_ptr_dev[a] .. member_ptr_dev[a + 1]), local rows,
+ *                      ascending) B[members, :] = Q R: Q into the rows of tv_dev (nrows x k, row-major, as b_dev), R into rows
+ *                      k a .. k a + k - 1 of bc_dev (k n_aggregates x k), +0.0 below the diagonal.  Classical Gram-Schmidt run
+ *                      twice, every sum by one lane in ascending member order (csrc/amg.hip has the arithmetic, which is part of
+ *                      the method's definition).  A column with !(nr > 1e-10 n0) is dropped (q_j = 0, row j of R = 0);
+ *                      info_dev[0] = all ones, or 8 a + j of the smallest aggregate that dropped one and its first such column.
+ *   amg_prolongator_b  p_e = (col / k == agg(i) ? tv[i, col - k agg(i)] : 0) - s_i * (A T)_e on the CSR of A T.
+ *   amg_restrictor_b   r_cj = (agg(j) == (row_offset + c) / k ? tv[j, (row_offset + c) % k] : 0) - (T^t A)_cj * s_j.
  * All only enqueue. */
+int hpcla_amg_fit_f64(const double *b_dev, int64_t nrows, int k, const int64_t *member_ptr_dev, const int64_t *members_dev,
+                      int64_t n_members, int64_t n_aggregates, double *tv_dev, double *bc_dev, int64_t *info_dev, void *stream);
+int hpcla_amg_prolongator_b_f64_i32(const int32_t *at_rowptr, const int32_t *at_colval, const int64_t *at_col_indices_dev,
+                                    const double *at_nzval, const int64_t *agg_dev, const double *s_dev, const double *tv_dev, int k,
+                                    int64_t nrows, int index_base, double *p_nzval, void *stream);
+int hpcla_amg_prolongator_b_f64_i64(const int64_t *at_rowptr, const int64_t *at_colval, const int64_t *at_col_indices_dev,
+                                    const double *at_nzval, const int64_t *agg_dev, const double *s_dev, const double *tv_dev, int k,
+                                    int64_t nrows, int index_base, double *p_nzval, void *stream);
+int hpcla_amg_restrictor_b_f64_i32(const int32_t *ta_rowptr, const int32_t *ta_colval, const int64_t *ta_col_indices_dev,
+                                   const double *ta_nzval, const int64_t *agg_dev, const double *s_dev, const double *tv_dev, int k,
+                                   int64_t nrows, int64_t ncols, int64_t row_offset, int index_base, double *r_nzval, void *stream);
+int hpcla_amg_restrictor_b_f64_i64(const int64_t *ta_rowptr, const int64_t *ta_colval, const int64_t *ta_col_indices_dev,
+                                   const double *ta_nzval, const int64_t *agg_dev, const double *s_dev, const double *tv_dev, int k,
+                                   int64_t nrows, int64_t ncols, int64_t row_offset, int index_base, double *r_nzval, void *stream);
 int64_t hpcla_amg_work_bytes(int64_t nrows);
 int64_t hpcla_amg_round_blocks(int64_t nrows);
 int hpcla_amg_weights_f64_i32(const int32_t *rowptr, const int32_t *colval_split, const double *nzval, int64_t nrows,

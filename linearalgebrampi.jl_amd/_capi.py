@@ -209,6 +209,11 @@ _SIGNATURES = {
     "hpcla_amg_symmetrise_fill": [_vp, _vp, _i64, _vp, _vp, _vp, _vp],
     "hpcla_amg_restrictor_f64_i32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp],
     "hpcla_amg_restrictor_f64_i64": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp],
+    "hpcla_amg_fit_f64": [_vp, _i64, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp],
+    "hpcla_amg_prolongator_b_f64_i32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp],
+    "hpcla_amg_prolongator_b_f64_i64": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp],
+    "hpcla_amg_restrictor_b_f64_i32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp, _vp],
+    "hpcla_amg_restrictor_b_f64_i64": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp, _vp],
     "hpcla_amg_presmooth_f64": [_vp, _vp, _vp, _i64, _vp],
     "hpcla_amg_postsmooth_f64": [_vp, _vp, _vp, _vp, _i64, _vp],
     # BiCGStab for nonsymmetric A (hp.bicgstab): the gated steps and the chunk of iterations

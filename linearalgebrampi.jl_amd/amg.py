@@ -30,10 +30,27 @@ positive diagonal, so the weights and the smoother stay):
 The cycle is then a fixed linear operator that is not symmetric: right-preconditioned GMRES and BiCGStab take it, ``cg`` refuses it.
 
 Limits: Float64; ``cg`` for ``A`` symmetric positive definite, ``gmres`` / ``bicgstab`` for either mode; a positive stored diagonal
-on every level (a strongly convective or non-M-matrix ``A`` can give a coarse diagonal that is not: the setup raises), the
-constant as the only near-nullspace candidate, rows and columns partitioned alike, one rank (the aggregation is rank-local and
-runs on several; the products and transposes of the setup move values between ranks through RCCL only, so the hierarchy across
-ranks waits for a transport that ranks sharing a GPU have too).
+on every level (a strongly convective or non-M-matrix ``A`` can give a coarse diagonal that is not: the setup raises), rows and
+columns partitioned alike, one rank (the aggregation is rank-local and runs on several; the products and transposes of the
+setup move values between ranks through RCCL only, so the hierarchy across ranks waits for a transport that ranks sharing a GPU
+have too).
+
+``B=`` (an HPCVector, or an HPCMatrix of k <= 8 columns, on A's rows) gives the near-nullspace candidates the tentative prolongator
+is fitted to: ``1 ./ d`` for a scaled scalar problem ``D A D``, the rigid-body modes for elasticity.  Without it T is the
+constant's, one 1.0 per row, and every launch is the one it was.  With it a level changes in these steps and no other:
+  unknowns    k per aggregate, the coarse unknown k agg + c; ``coarse_partition`` is k times the aggregates'; the aggregation
+              itself runs on the rows of A as before (on unknowns: it is not node-blocked)
+  stall       k n_aggregates >= 0.8 n, decided after the fit: every aggregation made is checked for dropped columns, also the
+              one of a level that then stalls (few members per aggregate is what makes a level stall and a column drop)
+  members     the rows of every aggregate in ascending order: a stable sort of the aggregate ids, the pointer from a bincount
+  fit         per aggregate B[members, :] = Q R (csrc/amg.hip: hpcla_amg_fit_f64, whose arithmetic is part of the method): Q
+              fills the dense n x k ``Tv``, R the rows k a .. k a + k - 1 of the next level's candidates.  A column that is
+              dropped (an aggregate with fewer members than candidates, candidates that are dependent on it, a zero column, a
+              NaN) is an error: ValueError on every rank, naming the first member's global row
+  T           k stored entries per row, columns k agg(i) .. k agg(i) + k - 1, values Tv[i, :], exact zeros stored
+  P, R        T - diag(s) (A T) and, with ``symmetric=False``, Tt - (Tt A) diag(s), on the patterns of A T and Tt A
+The candidates are not smoothed, and ``hp.spgemm``'s bound on the candidate products of an output row is reached k times sooner
+(the split into runs and its NotImplementedError apply unchanged).
 """
 from __future__ import annotations
 
@@ -55,9 +72,13 @@ def _torch():
     return torch
 
 
+MAX_CANDIDATES = 8             # AMG_G of csrc/amg.hip: the lanes of the group that fits an aggregate
+
+
 def check_arguments(T, shape, row_partition, col_partition, theta=0.0, max_levels=12, coarse_size=128, coarse_sweeps=4,
-                    symmetric=True) -> None:
-    """The argument rules, on host values only: ``T`` the element type, ``shape`` and the partitions A's."""
+                    symmetric=True, B=None) -> None:
+    """The argument rules, on host values only: ``T`` the element type, ``shape`` and the partitions A's; ``B`` None or the
+    candidates' (element type, global shape (rows, k), row partition)."""
     if not isinstance(symmetric, (bool, np.bool_)):
         raise TypeError(f"amg: symmetric must be a bool, got {symmetric!r}")
     if np.dtype(T) != np.dtype(np.float64):
@@ -74,6 +95,16 @@ def check_arguments(T, shape, row_partition, col_partition, theta=0.0, max_level
         raise ValueError(f"amg: coarse_size must lie in 1..{MAX_COARSE_SIZE}")
     if int(coarse_sweeps) < 1:
         raise ValueError("amg: coarse_sweeps must be at least 1")
+    if B is not None:
+        TB, shape_B, partition_B = B
+        if np.dtype(TB) != np.dtype(np.float64):
+            raise TypeError("amg: the candidates B must be Float64")
+        if not (1 <= int(shape_B[1]) <= MAX_CANDIDATES):
+            raise ValueError(f"amg: B must have 1..{MAX_CANDIDATES} columns, got {shape_B[1]}")
+        if int(shape_B[0]) != int(shape[0]):
+            raise ValueError(f"amg: B has {shape_B[0]} rows, A has {shape[0]}")
+        if not np.array_equal(np.asarray(partition_B), np.asarray(row_partition)):
+            raise ValueError("amg: B must be partitioned like the rows of A")
 
 
 class AMGLevel:
@@ -82,11 +113,13 @@ class AMGLevel:
     ``aggregates`` (global ids of the local rows, a device tensor), ``n_roots`` (this rank's), ``coarse_partition``, and the
     runs the two products were split into (``galerkin``; ``restriction_split`` for ``Tt A``, nonsymmetric mode only).  A level
     that stalled keeps its aggregation.  The last level has ``inverse`` (an HPCMatrix: this rank's rows of the dense inverse)
-    or ``sweeps``."""
+    or ``sweeps``.  Built with ``B=``: ``candidates`` (this level's n_local x k block, a row-major device tensor) and, where
+    the level has a P, ``Tv`` (n_local x k: row i holds the k values of row i of T) and ``T``; None otherwise."""
 
     def __init__(self, A: HPCSparseMatrix):
         self.A = A
         self.n = int(A.shape[0])
+        self.candidates = self.Tv = self.T = None
         self.s = self.w = self.rho = None
         self.P = self.Pt = self.R = self.aggregates = self.coarse_partition = self.inverse = None
         self.n_roots = self.rounds = self.sweeps = self.galerkin = self.restriction_split = None
@@ -108,12 +141,15 @@ class AMGWorkspace:
 
 class AMG:
     """The hierarchy.  ``levels``: AMGLevel objects, fine to coarse; ``operator_complexity``: the stored entries of every
-    level's A over those of the first (global counts); ``symmetric``: the mode it was built in."""
+    level's A over those of the first (global counts); ``symmetric``: the mode it was built in; ``candidates_per_aggregate``:
+    the columns of ``B`` (None without)."""
 
-    def __init__(self, levels: List[AMGLevel], operator_complexity: float, symmetric: bool = True):
+    def __init__(self, levels: List[AMGLevel], operator_complexity: float, symmetric: bool = True,
+                 candidates_per_aggregate: Optional[int] = None):
         self.levels = levels
         self.operator_complexity = float(operator_complexity)
         self.symmetric = bool(symmetric)
+        self.candidates_per_aggregate = candidates_per_aggregate
         self._work: Optional[AMGWorkspace] = None
 
     def workspace(self) -> AMGWorkspace:
@@ -248,8 +284,9 @@ def _aggregate(lvl: AMGLevel, plan, sfx: str, diag, theta: float, row_start: int
     lvl.aggregates = agg
 
 
-def _restrictor(lvl: AMGLevel, T: HPCSparseMatrix, lo: int) -> HPCSparseMatrix:
-    """R = Tt (I - A S) on the pattern of Tt A (one rank: every column of Tt A is a local row of the level)."""
+def _restrictor(lvl: AMGLevel, T: HPCSparseMatrix, lo: int, k: Optional[int] = None) -> HPCSparseMatrix:
+    """R = Tt (I - A S) on the pattern of Tt A (one rank: every column of Tt A is a local row of the level).  ``k``: the
+    candidates per aggregate of a level with ``Tv``; ``lo`` is then the rank's first coarse unknown."""
     from .indexing import _col_indices_dev
     from .transpose import transpose
     A = lvl.A
@@ -257,14 +294,49 @@ def _restrictor(lvl: AMGLevel, T: HPCSparseMatrix, lo: int) -> HPCSparseMatrix:
     TA, lvl.restriction_split = _split_product(Tt, A, 1, lvl, "restriction")
     vals = _torch().zeros_like(TA.nzval)
     sfx = "i64" if TA.Ti == np.dtype(np.int64) else "i32"
-    _capi.call(f"hpcla_amg_restrictor_f64_{sfx}", dptr(TA.rowptr_target), dptr(TA.colval_target()), dptr(_col_indices_dev(TA)),
-               dptr(TA.nzval), dptr(lvl.aggregates), dptr(lvl.s.v), TA.nrows_local, A.nrows_local, lo, 0, dptr(vals),
-               current_stream_ptr())
+    pattern = (dptr(TA.rowptr_target), dptr(TA.colval_target()), dptr(_col_indices_dev(TA)), dptr(TA.nzval), dptr(lvl.aggregates),
+               dptr(lvl.s.v))
+    if k is None:
+        _capi.call(f"hpcla_amg_restrictor_f64_{sfx}", *pattern, TA.nrows_local, A.nrows_local, lo, 0, dptr(vals),
+                   current_stream_ptr())
+    else:
+        _capi.call(f"hpcla_amg_restrictor_b_f64_{sfx}", *pattern, dptr(lvl.Tv), k, TA.nrows_local, A.nrows_local, lo, 0, dptr(vals),
+                   current_stream_ptr())
     return TA._with_values(vals)
 
 
-def _prolongator(lvl: AMGLevel, symmetric: bool = True) -> HPCSparseMatrix:
-    """P on the pattern of A T, and R (Pt, or the Petrov-Galerkin restriction); returns the next level's A."""
+def _fit(lvl: AMGLevel, k: int, first_aggregate: int, row_start: int):
+    """The members of every aggregate (ascending local rows), ``lvl.Tv`` and the next level's candidates from
+    ``lvl.candidates``; raises on every rank for a dropped column."""
+    torch = _torch()
+    A = lvl.A
+    backend, dev, n = A.backend, A.backend.torch_device, A.nrows_local
+    n_agg = lvl.n_roots
+    local = lvl.aggregates - first_aggregate
+    members = torch.sort(local, stable=True).indices
+    mptr = torch.zeros(n_agg + 1, dtype=torch.int64, device=dev)
+    mptr[1:] = torch.cumsum(torch.bincount(local, minlength=n_agg)[:n_agg], 0)
+    lvl.Tv = torch.zeros((n, k), dtype=torch.float64, device=dev)
+    coarse = torch.zeros((n_agg * k, k), dtype=torch.float64, device=dev)
+    info = torch.zeros(1, dtype=torch.int64, device=dev)
+    _capi.call("hpcla_amg_fit_f64", dptr(lvl.candidates), n, k, dptr(mptr), dptr(members), n, n_agg, dptr(lvl.Tv), dptr(coarse),
+               dptr(info), current_stream_ptr())
+    word = int(info.item())
+    first, size, column = -1, 0, 0
+    if word >= 0:                                            # 8 a + j: the smallest aggregate that dropped a column, its first
+        a, column = word >> 3, word & 7
+        e0, e1 = (int(v) for v in mptr[a:a + 2].cpu().tolist())
+        first, size = int(members[e0].item()), e1 - e0
+    _raise_together(backend, first, row_start,
+                    lambda row: f"amg: the aggregate of row {row} (level of {lvl.n} rows) has {size} members and cannot carry "
+                                f"candidate column {column} of B's {k}: too few members, or candidates that are dependent, zero "
+                                "or not finite on it")
+    return coarse
+
+
+def _prolongator(lvl: AMGLevel, symmetric: bool = True, k: Optional[int] = None) -> HPCSparseMatrix:
+    """P on the pattern of A T, and R (Pt, or the Petrov-Galerkin restriction); returns the next level's A.  ``k``: the
+    candidates per aggregate of a level that ``_fit`` has run on (``lvl.Tv``; ``lvl.coarse_partition`` counts unknowns)."""
     from .backends import comm_rank
     from .indexing import _col_indices_dev
     from .matmat import spgemm
@@ -275,20 +347,32 @@ def _prolongator(lvl: AMGLevel, symmetric: bool = True) -> HPCSparseMatrix:
     part = lvl.coarse_partition
     nc = int(part[-1])
     lo = int(part[comm_rank(backend.comm)])
-    window = (lo, lo + lvl.n_roots - 1) if lvl.n_roots > 0 else (0, 0)
-    T = HPCSparseMatrix_local_device(torch.arange(n + 1, dtype=torch.int64, device=dev), lvl.aggregates,
-                                     torch.ones(n, dtype=torch.float64, device=dev), nc, backend, col_partition=part,
-                                     col_window=window)
-    AT = spgemm(A, T)
-    vals = torch.empty_like(AT.nzval)
-    sfx = "i64" if AT.Ti == np.dtype(np.int64) else "i32"
-    _capi.call(f"hpcla_amg_prolongator_f64_{sfx}", dptr(AT.rowptr_target), dptr(AT.colval_target()), dptr(_col_indices_dev(AT)),
-               dptr(AT.nzval), dptr(lvl.aggregates), dptr(lvl.s.v), n, 0, dptr(vals), current_stream_ptr())
+    sfx = lambda M: "i64" if M.Ti == np.dtype(np.int64) else "i32"
+    if k is None:
+        window = (lo, lo + lvl.n_roots - 1) if lvl.n_roots > 0 else (0, 0)
+        T = HPCSparseMatrix_local_device(torch.arange(n + 1, dtype=torch.int64, device=dev), lvl.aggregates,
+                                         torch.ones(n, dtype=torch.float64, device=dev), nc, backend, col_partition=part,
+                                         col_window=window)
+        AT = spgemm(A, T)
+        vals = torch.empty_like(AT.nzval)
+        _capi.call(f"hpcla_amg_prolongator_f64_{sfx(AT)}", dptr(AT.rowptr_target), dptr(AT.colval_target()),
+                   dptr(_col_indices_dev(AT)), dptr(AT.nzval), dptr(lvl.aggregates), dptr(lvl.s.v), n, 0, dptr(vals),
+                   current_stream_ptr())
+    else:
+        window = (lo, lo + k * lvl.n_roots - 1) if lvl.n_roots > 0 else (0, 0)
+        cols = (lvl.aggregates * k).unsqueeze(1) + torch.arange(k, dtype=torch.int64, device=dev)
+        T = lvl.T = HPCSparseMatrix_local_device(torch.arange(n + 1, dtype=torch.int64, device=dev) * k, cols.reshape(-1),
+                                                 lvl.Tv.reshape(-1), nc, backend, col_partition=part, col_window=window)
+        AT = spgemm(A, T)
+        vals = torch.empty_like(AT.nzval)
+        _capi.call(f"hpcla_amg_prolongator_b_f64_{sfx(AT)}", dptr(AT.rowptr_target), dptr(AT.colval_target()),
+                   dptr(_col_indices_dev(AT)), dptr(AT.nzval), dptr(lvl.aggregates), dptr(lvl.s.v), dptr(lvl.Tv), k, n, 0,
+                   dptr(vals), current_stream_ptr())
     lvl.P = AT._with_values(vals)
     if symmetric:
         lvl.R = lvl.Pt = transpose(lvl.P).materialize()
     else:
-        lvl.R = _restrictor(lvl, T, lo)
+        lvl.R = _restrictor(lvl, T, lo, k)
     return galerkin(lvl, A)
 
 
@@ -386,8 +470,18 @@ def aggregate_level(A: HPCSparseMatrix, theta: float = 0.0, symmetric: bool = Tr
     return lvl
 
 
+def _candidate_block(B):
+    """(local block as a 2-D device tensor, row partition) of an HPCVector (one column) or an HPCMatrix."""
+    from .dense import HPCMatrix
+    if isinstance(B, HPCVector):
+        return B.v.reshape(-1, 1), B.partition
+    if isinstance(B, HPCMatrix):
+        return B.A, B.row_partition
+    raise TypeError(f"amg: B must be an HPCVector or an HPCMatrix, got {type(B).__name__}")
+
+
 def amg(A: HPCSparseMatrix, theta: float = 0.0, max_levels: int = 12, coarse_size: int = 128, coarse_sweeps: int = 4,
-        symmetric: bool = True) -> AMG:
+        symmetric: bool = True, B=None) -> AMG:
     """Build the smoothed-aggregation multigrid preconditioner of a symmetric positive definite ``A`` for
     ``hp.cg(A, b, M=hp.amg(A))``, or with ``symmetric=False`` that of a nonsymmetric ``A`` with a positive diagonal for
     ``hp.gmres`` and ``hp.bicgstab`` (which take a hierarchy of either mode; ``hp.cg`` refuses one built with ``symmetric=False``).
@@ -399,14 +493,27 @@ def amg(A: HPCSparseMatrix, theta: float = 0.0, max_levels: int = 12, coarse_siz
     level whose coarse matrix is over ``hp.spgemm``'s bound in both orders of the product.
 
     ``symmetric=False`` (a bool) aggregates on the symmetrised strength graph E u E^T, restricts with the Petrov-Galerkin
-    ``R = Tt (I - A S)`` in place of ``Pt`` (``AMGLevel.R``; ``Pt`` stays None) and inverts the last level's matrix as it is.  The
-    tentative prolongator is the constant vector, so a two-sided scaling of ``A`` takes most of the gain away; a strongly
-    convective or non-M-matrix ``A`` can give a coarse diagonal that is not positive, which raises as above."""
+    ``R = Tt (I - A S)`` in place of ``Pt`` (``AMGLevel.R``; ``Pt`` stays None) and inverts the last level's matrix as it is.  A
+    strongly convective or non-M-matrix ``A`` can give a coarse diagonal that is not positive, which raises as above.
+
+    ``B``: the near-nullspace candidates, an HPCVector or an HPCMatrix of k = 1..8 columns on A's row partition, Float64, in
+    either mode.  Without it the tentative prolongator is the constant vector's, and a two-sided scaling ``D A D`` takes most
+    of the gain away: pass ``B = 1 ./ d`` there, and the rigid-body modes for elasticity.  Every aggregate then carries k coarse
+    unknowns (``AMG.candidates_per_aggregate``; the stall rule counts k per aggregate), and one that cannot (fewer members than
+    candidates, candidates dependent, zero or not finite on it) raises ValueError with the global row of its first member.
+    rho is not invariant under a rough scaling, so with the right ``B`` a scaled problem converges at a rate independent of
+    the grid but not at the unscaled problem's (README)."""
     from .backends import comm_allgather, comm_rank, comm_size
     f64_only(A.backend, "amg")
-    check_arguments(A.backend.T, A.shape, A.row_partition, A.col_partition, theta, max_levels, coarse_size, coarse_sweeps, symmetric)
+    block = None if B is None else _candidate_block(B)
+    check_arguments(A.backend.T, A.shape, A.row_partition, A.col_partition, theta, max_levels, coarse_size, coarse_sweeps, symmetric,
+                    None if B is None else (B.backend.T, (int(block[1][-1]), int(block[0].shape[1])), block[1]))
     symmetric = bool(symmetric)
     backend = A.backend
+    k = None if B is None else int(block[0].shape[1])
+    candidates = None if B is None else block[0].contiguous()   # a block that is not row-major is packed here, once
+    if B is not None and int(candidates.shape[0]) != A.nrows_local:
+        raise ValueError(f"amg: B holds {candidates.shape[0]} local rows, A {A.nrows_local}")
     if comm_size(backend.comm) > 1:                              # the same on every rank
         raise NotImplementedError("amg: one rank only in this version.  Across ranks the setup's products and transposes move "
                                   "their values through RCCL, which ranks that share one GPU do not have, so the hierarchy and "
@@ -416,6 +523,7 @@ def amg(A: HPCSparseMatrix, theta: float = 0.0, max_levels: int = 12, coarse_siz
     nnz = []
     while True:
         lvl = AMGLevel(A)
+        lvl.candidates = candidates
         levels.append(lvl)
         nnz.append(int(comm_allgather(backend.comm, np.array([A.nnz], dtype=np.int64)).sum()))
         plan = get_vector_plan(A, HPCVector.zeros(A.col_partition, backend))
@@ -425,11 +533,14 @@ def amg(A: HPCSparseMatrix, theta: float = 0.0, max_levels: int = 12, coarse_siz
         last = lvl.n <= coarse_size or len(levels) >= max_levels
         if not last:
             _aggregate(lvl, plan, sfx, diag, theta, row_start, symmetric)
+            if k is not None:                                    # k unknowns per aggregate; the fit comes before the stall
+                lvl.coarse_partition = lvl.coarse_partition * k  # rule, so every aggregation made is checked for dropped columns
+                candidates = _fit(lvl, k, int(lvl.coarse_partition[rank]) // k, row_start)
             last = int(lvl.coarse_partition[-1]) >= STALL * lvl.n
         if last:
             if lvl.n <= coarse_size:
                 _dense_inverse(lvl, symmetric)
             else:
                 lvl.sweeps = int(coarse_sweeps)
-            return AMG(levels, sum(nnz) / max(nnz[0], 1), symmetric)
-        A = _prolongator(lvl, symmetric)
+            return AMG(levels, sum(nnz) / max(nnz[0], 1), symmetric, k)
+        A = _prolongator(lvl, symmetric, k)

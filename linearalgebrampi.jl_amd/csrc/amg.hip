@@ -36,6 +36,21 @@
 // R           r_cj = [agg(j) == c] - (T^t A)_cj * s_j on the stored pattern of T^t A: the Petrov-Galerkin restriction
 //             T^t (I - A S).  Its columns are the level's rows, all owned (one rank).
 //
+// With near-nullspace candidates (hp.amg(A, B=...), k <= 8 = AMG_G columns) three more entries:
+// fit         per aggregate B[members, :] = Q R by classical Gram-Schmidt run twice, the members ascending: Q goes to the rows
+//             of the dense n x k array Tv (row i: the k values of row i of T), R to rows k a .. k a + k - 1 of the next level's
+//             candidates, +0.0 below the diagonal.  The arithmetic is part of the method's definition.  Column j, v = B[members, j]:
+//             n0 = sqrt(sum v_m^2); twice: h_c = sum_m q_c[m] v[m] for every c < j, all taken before any update, then
+//             v[m] = v[m] - h_c q_c[m] for c ascending; R_cj = the first pass's h_c plus the second's; nr = sqrt(sum v_m^2),
+//             R_jj = nr, q_j = v / nr (a division).  Every sum over the members belongs to ONE lane, which adds in ascending
+//             member order from +0.0.  !(nr > 1e-10 n0) (a zero column and NaN included) drops the column: q_j = 0, row j of R
+//             = 0, the column takes no part in later ones, and the error word is lowered to 8 a + j (vector atomic min), so the
+//             smallest aggregate's first dropped column is what the host reads.  One group per aggregate: lanes c < j take the
+//             dot products of a pass side by side, lane j the norms, the updates stride the members over the group; v lives in
+//             its final place in Tv.  An aggregate of any size loops.  No LDS, no float atomics.
+// P, R with B the two value kernels with T's k entries per row: p_e = (col / k == agg(i) ? Tv[i, col - k agg(i)] : 0) - s_i at_e,
+//             r_cj = (agg(j) == c / k ? Tv[j, c - k agg(j)] : 0) - ta_cj s_j.
+//
 // A group of AMG_G = 8 lanes serves one row in the neighbour loops (8 rows per wave): the grids and their coarse levels
 // store 5 to about 30 entries per row, so a whole wave per row would idle most lanes; a longer row loops in steps of 8.
 // Products and sums are separately rounded (-ffp-contract=off).  No instantiation uses scratch.
@@ -347,6 +362,154 @@ __global__ __launch_bounds__(AMG_THREADS) void amg_restrictor_kernel(const I *__
     }
 }
 
+__device__ __forceinline__ double amg_group_get(double v, int lane) { return __shfl(v, lane, AMG_G); }
+
+// What one lane has written to Tv, the other lanes of its group read: the group is part of one wave, whose loads and stores go
+// through one vector cache in the order they were issued, so a workgroup-scope fence is all it takes: it keeps the compiler from
+// moving an access across it and costs no cache operation.
+__device__ __forceinline__ void amg_group_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); }
+
+// B[members of aggregate a, :] = Q R, K columns, the group's lane l = threadIdx & 7.  Column j, see the note on the fit above:
+//   pass 1    lane c < j: h_c = sum_m q_c[m] * b[m]; lane j: sum_m b[m]^2 (n0).  Sequential, ascending member order, from +0.0.
+//   update 1  v[m] = b[m] - h_0 q_0[m] - ... - h_{j-1} q_{j-1}[m] into Tv, the members strided over the group.
+//   pass 2    lane c < j: h'_c = sum_m q_c[m] * v[m];  update 2 in place (a lane updates the members it wrote);  R_cj = h_c + h'_c.
+//   norm      lane j: nr = sqrt(sum_m v[m]^2);  q_j = v / nr, R_jj = nr;  or the drop.
+// A member outside 0..nrows is passed over (no load, no store).  No shuffle stands inside a loop whose trip count differs
+// between the lanes of a group.
+template <int K>
+__global__ __launch_bounds__(AMG_THREADS) void amg_fit_kernel(const double *__restrict__ b, int64_t nrows,
+                                                              const int64_t *__restrict__ mptr, const int64_t *__restrict__ members,
+                                                              int64_t n_members, int64_t n_agg, double *tv, double *__restrict__ bc,
+                                                              int64_t *__restrict__ info)
+{
+    const int64_t a = ((int64_t)blockIdx.x * AMG_THREADS + threadIdx.x) / AMG_G;
+    const int l = threadIdx.x & (AMG_G - 1);
+    if (a >= n_agg) return;
+    int64_t e0 = mptr[a], e1 = mptr[a + 1];
+    e0 = e0 < 0 ? 0 : (e0 > n_members ? n_members : e0);
+    e1 = e1 < e0 ? e0 : (e1 > n_members ? n_members : e1);
+    const int64_t m = e1 - e0;
+    constexpr int H = K > 1 ? K - 1 : 1;
+    bool dropped = false;                                    // of column l
+    for (int j = 0; j < K; ++j) {
+        double h1 = 0.0;
+        if (l <= j) {
+            for (int64_t t = 0; t < m; ++t) {
+                const int64_t r = members[e0 + t];
+                if (r < 0 || r >= nrows) continue;
+                const double v = b[r * K + j];
+                const double x = l < j ? tv[r * K + l] : v;
+                h1 = h1 + x * v;
+            }
+        }
+        if (l < j && dropped) h1 = 0.0;
+        const double n0 = sqrt(amg_group_get(h1, j));
+        double hc[H];
+#pragma unroll
+        for (int c = 0; c < H; ++c) hc[c] = amg_group_get(h1, c);
+        for (int64_t t = l; t < m; t += AMG_G) {
+            const int64_t r = members[e0 + t];
+            if (r < 0 || r >= nrows) continue;
+            double v = b[r * K + j];
+#pragma unroll
+            for (int c = 0; c < H; ++c)
+                if (c < j) v = v - hc[c] * tv[r * K + c];
+            tv[r * K + j] = v;
+        }
+        amg_group_fence();
+        double h2 = 0.0;
+        if (l < j && !dropped) {
+            for (int64_t t = 0; t < m; ++t) {
+                const int64_t r = members[e0 + t];
+                if (r < 0 || r >= nrows) continue;
+                h2 = h2 + tv[r * K + l] * tv[r * K + j];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < H; ++c) hc[c] = amg_group_get(h2, c);
+        for (int64_t t = l; t < m; t += AMG_G) {
+            const int64_t r = members[e0 + t];
+            if (r < 0 || r >= nrows) continue;
+            double v = tv[r * K + j];
+#pragma unroll
+            for (int c = 0; c < H; ++c)
+                if (c < j) v = v - hc[c] * tv[r * K + c];
+            tv[r * K + j] = v;
+        }
+        amg_group_fence();
+        double sq = 0.0;
+        if (l == j) {
+            for (int64_t t = 0; t < m; ++t) {
+                const int64_t r = members[e0 + t];
+                if (r < 0 || r >= nrows) continue;
+                const double v = tv[r * K + j];
+                sq = sq + v * v;
+            }
+        }
+        const double nr = sqrt(amg_group_get(sq, j));
+        const bool drop = !(nr > 1e-10 * n0);
+        for (int64_t t = l; t < m; t += AMG_G) {
+            const int64_t r = members[e0 + t];
+            if (r < 0 || r >= nrows) continue;
+            tv[r * K + j] = drop ? 0.0 : tv[r * K + j] / nr;
+        }
+        amg_group_fence();
+        if (l < K) {
+            double rv = 0.0;                                 // below the diagonal, and the row of a dropped column
+            if (l < j) rv = h1 + h2;
+            else if (l == j && !drop) rv = nr;
+            bc[(a * K + l) * K + j] = rv;
+        }
+        if (l == j && drop) {
+            dropped = true;
+            atomicMin(reinterpret_cast<unsigned long long *>(info), (unsigned long long)(a * AMG_G + j));
+        }
+    }
+}
+
+// as amg_prolongator_kernel with K columns per aggregate: the global column c belongs to aggregate c / K
+template <typename I>
+__global__ __launch_bounds__(AMG_THREADS) void amg_prolongator_b_kernel(const I *__restrict__ rowptr, const I *__restrict__ colval,
+                                                                        const int64_t *__restrict__ col_indices,
+                                                                        const double *__restrict__ at, const int64_t *__restrict__ agg,
+                                                                        const double *__restrict__ s, const double *__restrict__ tv,
+                                                                        int64_t k, int64_t nrows, int base, double *__restrict__ p)
+{
+    const int64_t i = ((int64_t)blockIdx.x * AMG_THREADS + threadIdx.x) / AMG_G;
+    const int l = threadIdx.x & (AMG_G - 1);
+    if (i >= nrows) return;
+    const int64_t first = agg[i] * k;                        // the columns first .. first + k - 1 are the row's own
+    const double si = s[i];
+    const int64_t e0 = (int64_t)rowptr[i] - base, e1 = (int64_t)rowptr[i + 1] - base;
+    for (int64_t e = e0 + l; e < e1; e += AMG_G) {
+        const int64_t c = col_indices[(int64_t)colval[e] - base] - first;
+        const double t = c >= 0 && c < k ? tv[i * k + c] : 0.0;
+        p[e] = t - si * at[e];
+    }
+}
+
+// as amg_restrictor_kernel: row c of T^t A is the coarse unknown row_offset + c of the aggregate (row_offset + c) / K
+template <typename I>
+__global__ __launch_bounds__(AMG_THREADS) void amg_restrictor_b_kernel(const I *__restrict__ rowptr, const I *__restrict__ colval,
+                                                                       const int64_t *__restrict__ col_indices,
+                                                                       const double *__restrict__ ta, const int64_t *__restrict__ agg,
+                                                                       const double *__restrict__ s, const double *__restrict__ tv,
+                                                                       int64_t k, int64_t nrows, int64_t ncols, int64_t row_offset,
+                                                                       int base, double *__restrict__ r)
+{
+    const int64_t c = ((int64_t)blockIdx.x * AMG_THREADS + threadIdx.x) / AMG_G;
+    const int l = threadIdx.x & (AMG_G - 1);
+    if (c >= nrows) return;
+    const int64_t mine = (row_offset + c) / k, part = (row_offset + c) % k;
+    const int64_t e0 = (int64_t)rowptr[c] - base, e1 = (int64_t)rowptr[c + 1] - base;
+    for (int64_t e = e0 + l; e < e1; e += AMG_G) {
+        const int64_t j = col_indices[(int64_t)colval[e] - base];
+        if (j < 0 || j >= ncols) continue;
+        const double t = agg[j] == mine ? tv[j * k + part] : 0.0;
+        r[e] = t - ta[e] * s[j];
+    }
+}
+
 // MODE 0: x = s .* b          MODE 1: x = x + s .* (b - t)         (16-byte accesses, the odd element by one thread)
 template <int MODE>
 __global__ __launch_bounds__(256) void amg_smooth_kernel(const double *__restrict__ s, const double *__restrict__ b,
@@ -471,6 +634,50 @@ static int amg_restrictor_impl(const I *rowptr, const I *colval, const int64_t *
     amg_restrictor_kernel<I><<<amg_group_grid(nrows), AMG_THREADS, 0, as_stream(stream)>>>(rowptr, colval, col_indices, ta, agg,
                                                                                           s_dev, nrows, ncols, row_offset,
                                                                                           index_base, r);
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
+template <int K>
+static void amg_fit_launch(const double *b, int64_t nrows, const int64_t *mptr, const int64_t *members, int64_t n_members,
+                           int64_t n_agg, double *tv, double *bc, int64_t *info, hipStream_t s)
+{
+    amg_fit_kernel<K><<<amg_group_grid(n_agg), AMG_THREADS, 0, s>>>(b, nrows, mptr, members, n_members, n_agg, tv, bc, info);
+}
+
+template <typename I>
+static int amg_prolongator_b_impl(const I *rowptr, const I *colval, const int64_t *col_indices, const double *at,
+                                  const int64_t *agg, const double *s_dev, const double *tv, int k, int64_t nrows, int index_base,
+                                  double *p, void *stream)
+{
+    if (nrows < 0) return set_error(HPCLA_ERR_INVALID, "amg_prolongator_b: negative size");
+    if (k < 1 || k > AMG_G) return set_error(HPCLA_ERR_INVALID, "amg_prolongator_b: k must lie in 1..8");
+    if (index_base != 0 && index_base != 1) return set_error(HPCLA_ERR_INVALID, "amg_prolongator_b: index_base must be 0 or 1");
+    if (nrows == 0) return HPCLA_OK;
+    if (!rowptr || !colval || !col_indices || !at || !agg || !s_dev || !tv || !p)
+        return set_error(HPCLA_ERR_INVALID, "amg_prolongator_b: null array");
+    HPCLA_CHECK_GRID((nrows * AMG_G + AMG_THREADS - 1) / AMG_THREADS, "amg_prolongator_b");
+    amg_prolongator_b_kernel<I><<<amg_group_grid(nrows), AMG_THREADS, 0, as_stream(stream)>>>(rowptr, colval, col_indices, at, agg,
+                                                                                             s_dev, tv, k, nrows, index_base, p);
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
+template <typename I>
+static int amg_restrictor_b_impl(const I *rowptr, const I *colval, const int64_t *col_indices, const double *ta, const int64_t *agg,
+                                 const double *s_dev, const double *tv, int k, int64_t nrows, int64_t ncols, int64_t row_offset,
+                                 int index_base, double *r, void *stream)
+{
+    if (nrows < 0 || ncols < 0 || row_offset < 0) return set_error(HPCLA_ERR_INVALID, "amg_restrictor_b: negative size or offset");
+    if (k < 1 || k > AMG_G) return set_error(HPCLA_ERR_INVALID, "amg_restrictor_b: k must lie in 1..8");
+    if (index_base != 0 && index_base != 1) return set_error(HPCLA_ERR_INVALID, "amg_restrictor_b: index_base must be 0 or 1");
+    if (nrows == 0) return HPCLA_OK;
+    if (!rowptr || !colval || !col_indices || !ta || !agg || !s_dev || !tv || !r)
+        return set_error(HPCLA_ERR_INVALID, "amg_restrictor_b: null array");
+    HPCLA_CHECK_GRID((nrows * AMG_G + AMG_THREADS - 1) / AMG_THREADS, "amg_restrictor_b");
+    amg_restrictor_b_kernel<I><<<amg_group_grid(nrows), AMG_THREADS, 0, as_stream(stream)>>>(rowptr, colval, col_indices, ta, agg,
+                                                                                            s_dev, tv, k, nrows, ncols, row_offset,
+                                                                                            index_base, r);
     HPCLA_CHECK_LAUNCH();
     return HPCLA_OK;
 }
@@ -699,6 +906,72 @@ HPCLA_API int hpcla_amg_restrictor_f64_i64(const int64_t *ta_rowptr, const int64
 {
     return amg_restrictor_impl<int64_t>(ta_rowptr, ta_colval, ta_col_indices_dev, ta_nzval, agg_dev, s_dev, nrows, ncols, row_offset,
                                         index_base, r_nzval, stream);
+}
+
+HPCLA_API int hpcla_amg_fit_f64(const double *b_dev, int64_t nrows, int k, const int64_t *member_ptr_dev, const int64_t *members_dev,
+                                int64_t n_members, int64_t n_aggregates, double *tv_dev, double *bc_dev, int64_t *info_dev,
+                                void *stream)
+{
+    if (nrows < 0 || n_members < 0 || n_aggregates < 0) return set_error(HPCLA_ERR_INVALID, "amg_fit: negative size");
+    if (nrows > 0x7fffffffLL || n_aggregates > 0x7fffffffLL)
+        return set_error(HPCLA_ERR_UNSUPPORTED, "amg_fit: at most 2^31 - 1 rows and aggregates per rank");
+    if (k < 1 || k > AMG_G) return set_error(HPCLA_ERR_INVALID, "amg_fit: k must lie in 1..8");
+    if (!info_dev) return set_error(HPCLA_ERR_INVALID, "amg_fit: null info");
+    hipStream_t s = as_stream(stream);
+    HPCLA_CHECK_HIP(hipMemsetAsync(info_dev, 0xff, sizeof(int64_t), s));
+    if (n_aggregates == 0) return HPCLA_OK;
+    if (!member_ptr_dev || !tv_dev || !bc_dev || (n_members > 0 && (!b_dev || !members_dev)))
+        return set_error(HPCLA_ERR_INVALID, "amg_fit: null array");
+    if (b_dev == tv_dev) return set_error(HPCLA_ERR_INVALID, "amg_fit: B and Tv must be two arrays");
+    HPCLA_CHECK_GRID((n_aggregates * AMG_G + AMG_THREADS - 1) / AMG_THREADS, "amg_fit");
+    switch (k) {
+    case 1: amg_fit_launch<1>(b_dev, nrows, member_ptr_dev, members_dev, n_members, n_aggregates, tv_dev, bc_dev, info_dev, s); break;
+    case 2: amg_fit_launch<2>(b_dev, nrows, member_ptr_dev, members_dev, n_members, n_aggregates, tv_dev, bc_dev, info_dev, s); break;
+    case 3: amg_fit_launch<3>(b_dev, nrows, member_ptr_dev, members_dev, n_members, n_aggregates, tv_dev, bc_dev, info_dev, s); break;
+    case 4: amg_fit_launch<4>(b_dev, nrows, member_ptr_dev, members_dev, n_members, n_aggregates, tv_dev, bc_dev, info_dev, s); break;
+    case 5: amg_fit_launch<5>(b_dev, nrows, member_ptr_dev, members_dev, n_members, n_aggregates, tv_dev, bc_dev, info_dev, s); break;
+    case 6: amg_fit_launch<6>(b_dev, nrows, member_ptr_dev, members_dev, n_members, n_aggregates, tv_dev, bc_dev, info_dev, s); break;
+    case 7: amg_fit_launch<7>(b_dev, nrows, member_ptr_dev, members_dev, n_members, n_aggregates, tv_dev, bc_dev, info_dev, s); break;
+    default: amg_fit_launch<8>(b_dev, nrows, member_ptr_dev, members_dev, n_members, n_aggregates, tv_dev, bc_dev, info_dev, s); break;
+    }
+    HPCLA_CHECK_LAUNCH();
+    return HPCLA_OK;
+}
+
+HPCLA_API int hpcla_amg_prolongator_b_f64_i32(const int32_t *at_rowptr, const int32_t *at_colval, const int64_t *at_col_indices_dev,
+                                              const double *at_nzval, const int64_t *agg_dev, const double *s_dev,
+                                              const double *tv_dev, int k, int64_t nrows, int index_base, double *p_nzval,
+                                              void *stream)
+{
+    return amg_prolongator_b_impl<int32_t>(at_rowptr, at_colval, at_col_indices_dev, at_nzval, agg_dev, s_dev, tv_dev, k, nrows,
+                                           index_base, p_nzval, stream);
+}
+
+HPCLA_API int hpcla_amg_prolongator_b_f64_i64(const int64_t *at_rowptr, const int64_t *at_colval, const int64_t *at_col_indices_dev,
+                                              const double *at_nzval, const int64_t *agg_dev, const double *s_dev,
+                                              const double *tv_dev, int k, int64_t nrows, int index_base, double *p_nzval,
+                                              void *stream)
+{
+    return amg_prolongator_b_impl<int64_t>(at_rowptr, at_colval, at_col_indices_dev, at_nzval, agg_dev, s_dev, tv_dev, k, nrows,
+                                           index_base, p_nzval, stream);
+}
+
+HPCLA_API int hpcla_amg_restrictor_b_f64_i32(const int32_t *ta_rowptr, const int32_t *ta_colval, const int64_t *ta_col_indices_dev,
+                                             const double *ta_nzval, const int64_t *agg_dev, const double *s_dev,
+                                             const double *tv_dev, int k, int64_t nrows, int64_t ncols, int64_t row_offset,
+                                             int index_base, double *r_nzval, void *stream)
+{
+    return amg_restrictor_b_impl<int32_t>(ta_rowptr, ta_colval, ta_col_indices_dev, ta_nzval, agg_dev, s_dev, tv_dev, k, nrows, ncols,
+                                          row_offset, index_base, r_nzval, stream);
+}
+
+HPCLA_API int hpcla_amg_restrictor_b_f64_i64(const int64_t *ta_rowptr, const int64_t *ta_colval, const int64_t *ta_col_indices_dev,
+                                             const double *ta_nzval, const int64_t *agg_dev, const double *s_dev,
+                                             const double *tv_dev, int k, int64_t nrows, int64_t ncols, int64_t row_offset,
+                                             int index_base, double *r_nzval, void *stream)
+{
+    return amg_restrictor_b_impl<int64_t>(ta_rowptr, ta_colval, ta_col_indices_dev, ta_nzval, agg_dev, s_dev, tv_dev, k, nrows, ncols,
+                                          row_offset, index_base, r_nzval, stream);
 }
 
 HPCLA_API int hpcla_amg_presmooth_f64(const double *s_dev, const double *b, double *x, int64_t n, void *stream)
