@@ -364,6 +364,74 @@ int hpcla_select_put_f64_i32(double *v, int64_t n_own, const int32_t *pos, const
 int hpcla_select_put_f64_i64(double *v, int64_t n_own, const int64_t *pos, const double *src, int64_t n, int index_base,
                              void *stream);
 
+/* ---- reverse Cuthill-McKee ordering of a rank's owned block, and the bandwidth (hp.rcm, hp.bandwidth, csrc/rcm.hip) -----
+ * No reference counterpart: the reference never reorders.  Rows and columns of A are partitioned alike; a stored entry whose
+ * global column (col_indices_dev[colval - index_base] - index_base) lies in [row_start, row_start + nrows) names the local
+ * row column - row_start, every other entry and the diagonal are dropped.  Only structure is read.  nrows < 2^31 - 1 and fewer
+ * than 2^31 graph entries (the caller checks the latter from info_dev).
+ *   rcm_work_bytes      device bytes of `work` for the count's scan.
+ *   rcm_graph_count / _fill   g_rowptr_dev (nrows + 1, int64, 0-based), info_dev[0] = the graph's entries; then g_cols_dev
+ *                       (int32 local columns, stored order kept).
+ *   rcm_degrees         deg_dev[i] = the entries of row i of a graph; distinct != 0: the entries that no earlier entry of the
+ *                       row repeats (quadratic in the row), for a graph from hpcla_amg_symmetrise_fill, which lists an edge
+ *                       stored both ways twice.
+ *   rcm_init            by_degree_dev: the vertices sorted by (deg, index), the caller's stable sort.  rank_dev = its inverse,
+ *                       parent_dev = 2^31 - 1 (unvisited); the z vertices without a neighbour take order_dev[0 .. z) in index
+ *                       order and parent = their number; info_dev[0] = z.
+ * The walk numbers vertices into order_dev; order_dev[lo .. hi) is the current level, hi the next free number.  parent_dev is
+ * touched by agent-scope atomics only: an atomic min with the number of the level vertex claims, the lane that finds 2^31 - 1
+ * appends the neighbour to the candidates.  New vertices are numbered in ascending (parent << 32) | rank.
+ *   rcm_narrow          ONE workgroup walks levels while the frontier has at most hpcla_rcm_frontier_cap() vertices and its row
+ *                       lengths sum to at most hpcla_rcm_candidate_cap() (tested before parent is touched); frontier, keys and
+ *                       the bitonic sort live in LDS; a component that ends is followed by the first unvisited vertex of
+ *                       by_degree at or after `cursor`.  first_dev != NULL: lo = hi = cursor = first_dev[0] (rcm_init's z).
+ *                       record_dev (6 words): lo, hi, cursor, status (0: all nrows numbered, 1: the level [lo, hi) exceeds a
+ *                       cap and is untouched, 2: internal error), the levels walked and the components started in this call
+ *                       (a start is a level).  Waits on nothing but its own barrier.
+ *   rcm_expand          one level of any size: claims the neighbours of order_dev[lo .. hi), a lane group per vertex and chunk
+ *                       of 256 neighbours (longest_row: the longest row of the graph); cand_dev (nrows words) takes the claimed
+ *                       vertices in no defined order, count_dev[0] (reset here) their number: one atomic add per wave.
+ *   rcm_keys            keys_dev[i] = (parent << 32) | rank of cand_dev[i], in a launch after the expand.
+ *   rcm_number          order_dev[cnt + i] = by_degree_dev[keys_dev[i] & 0xffffffff] for the SORTED keys (the caller's sort).
+ *   rcm_finish          p_dev[i] = order_dev[nrows - 1 - i] + row_start (int64), inv_dev[order_dev[nrows - 1 - i]] = i.
+ *   rcm_graph_bandwidth out_dev[0] = max |inv[i] - inv[c]| over the graph's entries (inv_dev == NULL: |i - c|).
+ *   bandwidth           out_dev[0] = max |row_start + i - global column| over every stored entry of rows 0 .. nrows - 1.
+ * Both maxima: an integer maximum per workgroup, then one atomic max.  Integer atomics only; all only enqueue; every result
+ * is fixed by the inputs. */
+int64_t hpcla_rcm_frontier_cap(void);
+int64_t hpcla_rcm_candidate_cap(void);
+int64_t hpcla_rcm_work_bytes(int64_t nrows);
+int hpcla_rcm_graph_count_i32(const int32_t *rowptr, const int32_t *colval, const int64_t *col_indices_dev, int64_t nrows,
+                              int64_t row_start, int index_base, int64_t *g_rowptr_dev, int64_t *info_dev, void *work,
+                              void *stream);
+int hpcla_rcm_graph_count_i64(const int64_t *rowptr, const int64_t *colval, const int64_t *col_indices_dev, int64_t nrows,
+                              int64_t row_start, int index_base, int64_t *g_rowptr_dev, int64_t *info_dev, void *work,
+                              void *stream);
+int hpcla_rcm_graph_fill_i32(const int32_t *rowptr, const int32_t *colval, const int64_t *col_indices_dev, int64_t nrows,
+                             int64_t row_start, int index_base, const int64_t *g_rowptr_dev, int32_t *g_cols_dev, void *stream);
+int hpcla_rcm_graph_fill_i64(const int64_t *rowptr, const int64_t *colval, const int64_t *col_indices_dev, int64_t nrows,
+                             int64_t row_start, int index_base, const int64_t *g_rowptr_dev, int32_t *g_cols_dev, void *stream);
+int hpcla_rcm_degrees(const int64_t *g_rowptr_dev, const int32_t *g_cols_dev, int64_t nrows, int distinct, int32_t *deg_dev,
+                      void *stream);
+int hpcla_rcm_init(const int32_t *deg_dev, const int32_t *by_degree_dev, int64_t nrows, int32_t *rank_dev, int32_t *parent_dev,
+                   int32_t *order_dev, int64_t *info_dev, void *stream);
+int hpcla_rcm_narrow(const int64_t *g_rowptr_dev, const int32_t *g_cols_dev, const int32_t *by_degree_dev, const int32_t *rank_dev,
+                     int64_t nrows, int64_t lo, int64_t hi, int64_t cursor, const int64_t *first_dev, int32_t *parent_dev,
+                     int32_t *order_dev, int64_t *record_dev, void *stream);
+int hpcla_rcm_expand(const int64_t *g_rowptr_dev, const int32_t *g_cols_dev, int64_t nrows, const int32_t *order_dev, int64_t lo,
+                     int64_t hi, int64_t longest_row, int32_t *parent_dev, int32_t *cand_dev, int64_t *count_dev, void *stream);
+int hpcla_rcm_keys(const int32_t *cand_dev, int64_t ncand, int64_t nrows, int32_t *parent_dev, const int32_t *rank_dev,
+                   int64_t *keys_dev, void *stream);
+int hpcla_rcm_number(const int64_t *keys_dev, int64_t ncand, int64_t nrows, const int32_t *by_degree_dev, int64_t cnt,
+                     int32_t *order_dev, void *stream);
+int hpcla_rcm_finish(const int32_t *order_dev, int64_t nrows, int64_t row_start, int64_t *p_dev, int32_t *inv_dev, void *stream);
+int hpcla_rcm_graph_bandwidth(const int64_t *g_rowptr_dev, const int32_t *g_cols_dev, int64_t nrows, const int32_t *inv_dev,
+                              int64_t *out_dev, void *stream);
+int hpcla_bandwidth_i32(const int32_t *rowptr, const int32_t *colval, const int64_t *col_indices_dev, int64_t nrows,
+                        int64_t row_start, int index_base, int64_t *out_dev, void *stream);
+int hpcla_bandwidth_i64(const int64_t *rowptr, const int64_t *colval, const int64_t *col_indices_dev, int64_t nrows,
+                        int64_t row_start, int index_base, int64_t *out_dev, void *stream);
+
 /* ---- COO assembly with a reusable structure: sparse(I, J, V, m, n) on the device (csrc/assemble.hip) --------------
  * Replaces the host idiom sparse(I, J, V, m, n) + HPCSparseMatrix(A, backend) (src/sparse.jl:398-413) of a loop that
  * produces new values V on the same (I, J) at every step.  The structure is an inverted index: the caller sorts the keys

@@ -43,6 +43,9 @@ Layout
                      LISTS (Dirichlet elimination, symmetric permutations, non-contiguous blocks): a column look-up, two scans
                      and a per-row rank-and-fill that keeps columns ascending (csrc/select.hip); off-rank vector entries
                      travel by a halo plan
+  rcm.py             rcm(), bandwidth(): the reverse Cuthill-McKee ordering of a rank's owned block as an index list for select(),
+                     take() and put_(): ties broken by (degree, index), levels walked by one workgroup in LDS while they are
+                     narrow and device-wide otherwise, one integer state array under atomic min (csrc/rcm.hip); rank-local
   transpose.py matmat.py addition.py repartition.py   the SURVEY 8f "next" rows and their plans
 
 The directory name contains a dot, so it is imported through the top-level alias module
@@ -85,6 +88,7 @@ from .addition import add_scaled_identity, sparse_add
 from .indexing import SubmatrixPlan, diag, get_submatrix_plan
 from .assemble import AssemblyPlan, assembly_plan, sparse_from_coo
 from .select import SelectionPlan, VectorIndexPlan, index_plan, put_, select, selection_plan, take
+from .rcm import RCMInfo, bandwidth, rcm
 from .repartition import (RangePlan, SparseRepartitionPlan, clear_repartition_cache, exchange_ranges,
                           get_sparse_repartition_plan, get_vector_repartition_plan, repartition)
 

@@ -344,6 +344,24 @@ _SIGNATURES = {
     "hpcla_select_take_f64_i64": [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _vp],
     "hpcla_select_put_f64_i32": [_vp, _i64, _vp, _vp, _i64, _i32, _vp],
     "hpcla_select_put_f64_i64": [_vp, _i64, _vp, _vp, _i64, _i32, _vp],
+    # reverse Cuthill-McKee ordering and the bandwidth (hp.rcm, hp.bandwidth, csrc/rcm.hip)
+    "hpcla_rcm_frontier_cap": [],
+    "hpcla_rcm_candidate_cap": [],
+    "hpcla_rcm_work_bytes": [_i64],
+    "hpcla_rcm_graph_count_i32": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp],
+    "hpcla_rcm_graph_count_i64": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp],
+    "hpcla_rcm_graph_fill_i32": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp],
+    "hpcla_rcm_graph_fill_i64": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp],
+    "hpcla_rcm_degrees": [_vp, _vp, _i64, _i32, _vp, _vp],
+    "hpcla_rcm_init": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
+    "hpcla_rcm_narrow": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
+    "hpcla_rcm_expand": [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
+    "hpcla_rcm_keys": [_vp, _i64, _i64, _vp, _vp, _vp, _vp],
+    "hpcla_rcm_number": [_vp, _i64, _i64, _vp, _i64, _vp, _vp],
+    "hpcla_rcm_finish": [_vp, _i64, _i64, _vp, _vp, _vp],
+    "hpcla_rcm_graph_bandwidth": [_vp, _vp, _i64, _vp, _vp, _vp],
+    "hpcla_bandwidth_i32": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp],
+    "hpcla_bandwidth_i64": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp],
     "hpcla_digest_i32": [_vp, _i64, _vp, _vp],
     "hpcla_digest_i64": [_vp, _i64, _vp, _vp],
     "hpcla_poisson2d_nnz": [_i64, _i64, _i64, _i64],
@@ -428,6 +446,9 @@ _RESTYPES = {
     "hpcla_select_short_cap": _i64,
     "hpcla_select_tile": _i64,
     "hpcla_select_work_bytes": _i64,
+    "hpcla_rcm_frontier_cap": _i64,
+    "hpcla_rcm_candidate_cap": _i64,
+    "hpcla_rcm_work_bytes": _i64,
     "hpcla_assemble_chunk": _i64,
     "hpcla_assemble_run": _i64,
     "hpcla_assemble_pass": _i64,
