@@ -73,7 +73,8 @@ def test_path_choice_at_the_caps(hp):
     """Either side of each cap, the path that ran (the restatement's results were asserted above; here: which kernel)."""
     got = {}
     for name in ("star_cap", "star_cap_plus1", "tree_frontier_cap", "tree_frontier_cap_plus1", "degree_sum_cap",
-                 "degree_sum_cap_plus1", "path300", "pairs500", "random20000"):
+                 "degree_sum_cap_plus1", "path300", "pairs500", "random20000", "star_chunk_wrap", "path1024_k6", "path1025_k6",
+                 "path3000_k6", "tree_then_narrow"):
         p, info = hp.rcm(_matrix(hp, name, np.int32))
         assert np.array_equal(p.cpu().numpy(), rc.expected(name)[0]), name
         got[name] = (info.narrow_launches, info.wide_levels)
@@ -82,6 +83,9 @@ def test_path_choice_at_the_caps(hp):
     assert got["degree_sum_cap"] == (1, 0) and got["degree_sum_cap_plus1"] == (2, 2)
     assert got["path300"] == (1, 0) and got["pairs500"] == (1, 0)
     assert got["random20000"][1] > 1
+    assert got["star_chunk_wrap"] == (2, 2)                                 # the centre's row: one chunk more than the expand's grid.y
+    assert got["path1024_k6"] == got["path1025_k6"] == got["path3000_k6"] == (1, 0)
+    assert got["tree_then_narrow"] == (2, 1)                                # the second launch resumes on the wide level's 10 vertices
 
 
 def test_float32_values_are_never_read(hp):
@@ -102,6 +106,15 @@ def test_nonsymmetric_pattern(hp, Ti):
     assert info.narrow_launches == 1 and info.wide_levels == 0
     p, info = hp.rcm(A, symmetric=True)                                     # the promise broken: the directed walk
     _assert_result(p, info, "nonsymmetric", True)
+    # doubled lists longer than a lane group, device-wide levels that meet repeated neighbours: the numbering of the set
+    # union, the paths of the walk on the lists as the device holds them
+    W = _matrix(hp, "nonsymmetric_wide", Ti)
+    p, info = hp.rcm(W, symmetric=False)
+    _assert_result(p, info, "nonsymmetric_wide", False, paths=False)
+    paths = rc.trace_facts(rc.traced("nonsymmetric_wide", doubled=True)[0], W.shape[0])
+    assert (info.narrow_launches, info.wide_levels) == (paths["narrow_launches"], paths["wide_levels"]) and info.wide_levels > 1
+    p, info = hp.rcm(W, symmetric=True)
+    _assert_result(p, info, "nonsymmetric_wide", True)
     # on a symmetric pattern the two agree
     B = _matrix(hp, "delaunay2000", Ti)
     p, info = hp.rcm(B, symmetric=False)
