@@ -11,6 +11,8 @@ Layout
   dense.py           HPCMatrix, dense A*x and transpose(A)*x, transpose(X)*Y, X*A and transpose(X)*A
   spmm_plans.py      A*B for a sparse A and a dense B (SpMM): exchange entries, sequential and panel orders
   cg.py              fixed-iteration CG harness; cg(): the converging solver (Jacobi or FSAI preconditioner, device-side stop)
+  krylov.py          what the chunked solvers below share: CGInfo, the history of pairs, argument rules, the chunk loop with its
+                     16-byte read-back, the M of bicgstab() and gmres(); their host-side iteration loops are csrc/solvers.hip
   fsai.py            fsai(): the factorised sparse approximate inverse preconditioner G' G of an SPD A for cg(M=...): one small dense
                      Cholesky per row on the device (csrc/fsai.hip), applied as two SpMVs; rank-local couplings, <= 32 entries per row
   amg.py             amg(): the smoothed-aggregation multigrid preconditioner of an SPD A for cg(M=...): aggregation by a distance-2
@@ -68,7 +70,8 @@ from .dense import (HPCMatrix, HPCMatrix_local, TransposedHPCMatrix, clear_dense
                     dense_matvec_t, dense_sparse_matmat, dense_sparse_matmat_t)
 from .spmm_plans import clear_spmm_cache, spmm, spmm_block_order_of, spmm_exchange_bytes, spmm_runs_fit_of
 from .matmat import clear_matrix_plan_cache, get_matrix_plan, spgemm
-from .cg import CGGraphPair, CGInfo, CGWorkspace, PCGWorkspace, cg, cg_fixed_iterations, cg_iterate, cg_setup
+from .krylov import CGInfo
+from .cg import CGGraphPair, CGWorkspace, PCGWorkspace, cg, cg_fixed_iterations, cg_iterate, cg_setup
 from .fsai import FSAI, fsai
 from .amg import AMG, AMGLevel, AMGWorkspace, amg
 from .ilu import ILU0, ilu0

@@ -3,7 +3,7 @@
 The reference solves a general ``A \\ b`` through MUMPS on the host; a caller of its operators would compose a Krylov method
 from ``A*p`` (src/sparse.jl:2096-2128), ``dot`` (src/vectors.jl:798-812) and broadcast updates (src/vectors.jl:1203-1226): five
 host read-backs and about 13 launches per BiCGStab iteration.  Here an iteration is two SpMVs and five gated HIP steps
-(csrc/vecops.hip, ``hpcla_bicgstab_iterations_f64_*``) whose scalars, stop rule and breakdown tests stay on the device; the
+(csrc/vecops.hip, chained by ``hpcla_bicgstab_iterations_f64_*`` in csrc/solvers.hip) whose scalars, stop rule and breakdown tests stay on the device; the
 host enqueues ``check_every`` iterations per library call and reads 16 bytes of state per chunk, exactly as ``hp.cg`` does.
 
 Right-preconditioned, ``K`` = identity, ``dinv .*`` or the operator of ``hp.ilu0`` / ``hp.amg`` (ilu.py, amg.py; the same steps with ``dinv == NULL``,
@@ -21,15 +21,13 @@ enqueued one by one from here with ``K`` applied between them); gate order and r
 """
 from __future__ import annotations
 
-import math
 from typing import Optional, Tuple
 
-import numpy as np
-
 from . import _capi
-from .cg import CGInfo, _PairHistory, _residual_norms, _run_chunks, _solver_arguments, _stop_rule_or_done
+from .krylov import (CGInfo, _bicgstab_dinv, _ilu_operator, _PairHistory, _residual_norms, _run_chunks, _solver_arguments,
+                     _stop_rule_or_done)
 from .sparse import get_vector_plan, mul_
-from .vectors import HPCVector, current_stream_ptr, dptr, norm, rd16_vector
+from .vectors import HPCVector, current_stream_ptr, dptr, norm
 
 _STATUS = {0: "maxiter", 1: "converged", 2: "breakdown", 3: "converged"}     # 3: converged at the half step
 
@@ -65,59 +63,6 @@ class BiCGStabWorkspace(_PairHistory):
     def with_preconditioner(self) -> None:
         if self.ph is None:
             self.ph, self.sh = self.x.similar(), self.x.similar()
-
-
-def _bicgstab_dinv(A, b: HPCVector, M, name: str = "bicgstab") -> Optional[HPCVector]:
-    if M is None:
-        return None
-    if isinstance(M, str):
-        if M != "jacobi":
-            raise ValueError(f"{name}: unknown preconditioner {M!r} (None, 'jacobi' or an HPCVector of 1 ./ diagonal)")
-        from .indexing import diag
-        dinv = diag(A, reciprocal=True)
-        # minimum(abs(diag(A))) > 0  <=>  maximum(abs(1 ./ diag(A))) is finite (a missing or zero entry gives Inf)
-        if not math.isfinite(norm(dinv, math.inf)):
-            raise ValueError(f"{name}: M='jacobi' needs a diagonal without zeros (minimum(abs(diag(A))) > 0)")
-        return dinv
-    if not isinstance(M, HPCVector):
-        raise ValueError(f"{name}: M must be None, 'jacobi', an HPCVector on A's row partition, an ILU0 (hp.ilu0(A)) or an AMG "
-                         f"(hp.amg(A, symmetric=False))")
-    b._same_partition(M)
-    return rd16_vector(M)                                        # the step kernels read it 16 bytes at a time
-
-
-class _AMGOperator:
-    """The hierarchy of ``hp.amg`` (either mode) as the operator of one solver workspace: ``apply`` is one cycle in level vectors
-    that belong to that workspace (allocated once, kept for later solves with the same hierarchy), so two solves with one
-    hierarchy share none."""
-
-    def __init__(self, mg, ws):
-        from .amg import AMGWorkspace
-        if getattr(ws, "amg", None) is None or ws._amg_of is not mg:
-            ws.amg, ws._amg_of = AMGWorkspace(mg.levels), mg
-        self.mg, self.work = mg, ws.amg
-
-    def apply(self, r: HPCVector, out: HPCVector) -> HPCVector:
-        return self.mg.apply(r, out=out, workspace=self.work)
-
-
-def _ilu_operator(A, M, name: str, ws=None):
-    """M when it is the operator of ``hp.ilu0``, or the hierarchy of ``hp.amg`` wrapped for the workspace ``ws`` (ilu.py and
-    amg.py are looked at only for an M that is nothing else), checked against A."""
-    if M is None or isinstance(M, (str, HPCVector)):
-        return None
-    from .amg import AMG
-    if isinstance(M, AMG):
-        top = M.levels[0].A
-        if not np.array_equal(top.row_partition, A.row_partition) or top.shape != A.shape:
-            raise ValueError(f"{name}: the AMG preconditioner was built for a matrix of another shape or partition")
-        return _AMGOperator(M, ws)
-    from .ilu import ILU0
-    if not isinstance(M, ILU0):
-        return None
-    if not np.array_equal(M.row_partition, A.row_partition) or M.shape != tuple(int(v) for v in A.shape):
-        raise ValueError(f"{name}: the ILU0 preconditioner was built for a matrix of another shape or partition")
-    return M
 
 
 def bicgstab(A, b: HPCVector, x0: Optional[HPCVector] = None, rtol: float = 1e-8, atol: float = 0.0,

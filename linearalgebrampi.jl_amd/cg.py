@@ -23,20 +23,20 @@ iterations and nothing else; ``cg_fixed_iterations`` is the two together plus th
 
 ``cg`` is the solver built from the same launches: a stop rule, an optional preconditioner (a diagonal, or the factorised
 sparse approximate inverse of fsai.py: two more SpMVs and one reduction per iteration, ``hpcla_pcg_fsai_iterations_f64_*``) and
-a breakdown check, all decided on the device (csrc/vecops.hip, ``hpcla_pcg_iterations_f64_*``); the host reads 16 bytes of
-state once per ``check_every`` iterations, and the iterations enqueued behind the deciding one are no-ops.
+a breakdown check, all decided on the device (the gated kernels of csrc/vecops.hip, chained by ``hpcla_pcg_iterations_f64_*`` in
+csrc/solvers.hip); the host reads 16 bytes of state once per ``check_every`` iterations, and the iterations enqueued behind the
+deciding one are no-ops.  What ``cg`` shares with the other chunked solvers (``CGInfo``, the chunk loop) is in krylov.py.
 """
 from __future__ import annotations
 
 import math
-import time
-from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
 import numpy as np
 
 from . import _capi
 from .fsai import FSAI
+from .krylov import _STATUS, CGInfo, _PairHistory, _residual_norms, _run_chunks, _solver_arguments, _stop_rule_or_done
 from .sparse import get_vector_plan, mul_, mul_dot_
 from .vectors import HPCVector, _Scratch, cg_direction_, cg_residual_, current_stream_ptr, dot, dptr, norm, rd16_vector
 
@@ -215,107 +215,6 @@ def _cg_graph_replay(A, ws: CGWorkspace, plan, fused: bool, iters: int) -> None:
 
 
 # ---- the converging solver ---------------------------------------------------------------------------------------------
-_STATUS = {0: "maxiter", 1: "converged", 2: "breakdown"}
-
-
-@dataclass
-class CGInfo:
-    """What ``cg`` reports: ``iterations`` is the iteration the device stopped on (``maxiter`` when it did not stop),
-    ``residual_norms`` holds ||r_0|| ... ||r_iterations|| of the recurrence residual."""
-    converged: bool
-    iterations: int
-    status: str
-    residual_norms: List[float]
-
-
-class _PairHistory:
-    """The history of a chunked solve (``cg``, ``bicgstab``): pairs of doubles, pair j written by iteration j; it IS the
-    scalar storage of the iterations and grows by doubling between chunks."""
-
-    def hist_capacity(self) -> int:
-        return self.hist.numel() // 2 - 1                              # the last iteration whose pair fits
-
-    def grow_hist(self, upto: int) -> None:
-        torch = _torch()
-        cap = self.hist.numel() // 2
-        while cap - 1 < upto:
-            cap *= 2
-        new = torch.zeros(2 * cap, dtype=torch.float64, device=self.hist.device)
-        new[:self.hist.numel()].copy_(self.hist)
-        self.hist = new
-
-
-def _solver_arguments(name: str, A, rtol: float, atol: float, maxiter: Optional[int], check_every: int) -> Tuple[int, int]:
-    """The argument rules ``cg`` and ``bicgstab`` share.  Returns (maxiter, check_every)."""
-    from .vectors import f64_only
-    f64_only(A.backend, name)
-    if A.shape[0] != A.shape[1]:
-        raise ValueError(f"{name}: the matrix must be square, got {A.shape[0]} x {A.shape[1]}")
-    check_every = int(check_every)
-    if check_every < 1:
-        raise ValueError(f"{name}: check_every must be at least 1")
-    if not (rtol >= 0 and atol >= 0):
-        raise ValueError(f"{name}: rtol and atol must be non-negative")
-    maxiter = 10 * int(A.shape[0]) if maxiter is None else int(maxiter)
-    if maxiter < 0:
-        raise ValueError(f"{name}: maxiter must be non-negative")
-    return maxiter, check_every
-
-
-def _stop_rule_or_done(ws, b, have_x0: bool, rtol: float, atol: float, maxiter: int) -> Optional["CGInfo"]:
-    """After the setup (hist[0] = sum r_0^2, tmp[0] = |b|^2 when x0 was given): the setup's one read-back.  Returns the result
-    of a solve that needs no iteration (b = 0, r_0 within the stop rule, maxiter = 0), else writes thr into the state."""
-    rr0 = float(ws.hist[0].item())
-    bb = float(ws.tmp[0].item()) if have_x0 else rr0
-    if bb == 0.0:                                                # b = 0: x = 0
-        ws.x.v.zero_()
-        return CGInfo(True, 0, "converged", [0.0])
-    thr = max(rtol * math.sqrt(bb), atol) ** 2
-    if rr0 <= thr or maxiter == 0:
-        if rr0 != rr0:
-            from .sparse import check_exchange_health
-            check_exchange_health(b.backend)
-        return CGInfo(rr0 <= thr, 0, "converged" if rr0 <= thr else "maxiter", [math.sqrt(rr0)])
-    ws.work[-2:-1].fill_(thr)
-    return None
-
-
-def _run_chunks(ws, backend, maxiter: int, check_every: int, enqueue) -> Tuple[int, int]:
-    """Chunks of ``check_every`` iterations, ``enqueue(first_iter, count)`` each, one 16-byte read-back of the state per chunk.
-    Returns (iterations, status); a status other than 0 is the device's, 0 means ``maxiter`` iterations ran."""
-    from .backends import comm_allgather, comm_size
-    multi = comm_size(backend.comm) > 1
-    j, done_iter, status = 1, 0, 0
-    while j <= maxiter:
-        k = min(check_every, maxiter - j + 1)
-        if j + k - 1 > ws.hist_capacity():
-            ws.grow_hist(min(maxiter, 2 * (j + k)))
-        clock = getattr(ws, "enqueue_ms", None)                  # a list: the host's time in each chunk's enqueueing is appended
-        t0 = time.perf_counter() if clock is not None else 0.0
-        enqueue(j, int(k))
-        if clock is not None:
-            clock.append((time.perf_counter() - t0) * 1e3)
-        j += k
-        done_iter, status = (int(v) for v in ws.state[:2].cpu().tolist())
-        if multi:                                                # no rank leaves the loop alone, whatever produced its scalars
-            every = comm_allgather(backend.comm, np.array([done_iter, status], dtype=np.int64)).reshape(-1, 2)
-            stopped = every[every[:, 1] != 0]
-            if len(stopped):
-                done_iter, status = int(stopped[:, 0].min()), int(stopped[0, 1])
-        if status != 0:
-            break
-    return (done_iter if status != 0 else maxiter), status
-
-
-def _residual_norms(ws, backend, iterations: int) -> List[float]:
-    """sqrt of the first entries of pairs 0 .. iterations, read back once."""
-    h = ws.hist[0:2 * (iterations + 1):2].sqrt().cpu().tolist()
-    if h[-1] != h[-1]:                         # NaN: the poison of an expired exchange wait -- ask
-        from .sparse import check_exchange_health
-        check_exchange_health(backend)
-    return h
-
-
 class PCGWorkspace(_PairHistory):
     """What a ``cg`` solve allocates: x, r, p, Ap, the history of (sum r_j^2, sum r_j.(dinv r_j)) pairs (it IS the scalar
     storage of the iterations; it grows by doubling between chunks), pAp, and the scratch of the gated kernels whose last

@@ -28,14 +28,6 @@ static_assert(WIN_LINE_U64 == WIN_FLAG_STRIDE_U64, "flag stride");
 constexpr int AR_MAX = 8;                      // doubles per window all-reduce (larger counts: RCCL)
 constexpr int64_t WIN_DOUBLE_BUFFER_MAX = 64ll << 20;   // ghost bytes up to which two buffers are kept
 
-// slots of the MINRES solver's scalar buffer (include/hpcla_rocm.h): the kernels in vecops.hip read and write them, the
-// iterations loop in comm.hip points the SpMV's dot at MINRES_YT
-enum MinresSlot {
-    MINRES_BETA = 0, MINRES_OLDB = 1, MINRES_YT = 2, MINRES_BB = 3, MINRES_ALFA = 4, MINRES_CS = 5, MINRES_SN = 6, MINRES_DBAR = 7,
-    MINRES_EPSLN = 8, MINRES_OLDEPS = 9, MINRES_DELTA = 10, MINRES_GBAR = 11, MINRES_GAMMA = 12, MINRES_PHI = 13,
-    MINRES_PHIBAR = 14, MINRES_SCALARS = 16
-};
-
 struct WindowDesc {                            // HPCLA_WINDOW_DESC_BYTES, exchanged by the host runtime
     uint8_t ipc[64];                           // hipIpcMemHandle_t
     uint64_t host_id;                          // hash of the node identity: IPC needs one node

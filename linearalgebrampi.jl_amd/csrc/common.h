@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <initializer_list>
+
 #include "../../include/hpcla_rocm.h"
 
 #define HPCLA_API extern "C" __attribute__((visibility("default")))
@@ -39,6 +41,14 @@ int set_error(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3
     } while (0)
 
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+
+// true when any of the pointers is not 16-byte aligned (null counts as aligned): the guard of the kernels' vector loads
+static inline bool misaligned16(std::initializer_list<const void *> ptrs)
+{
+    uintptr_t m = 0;
+    for (const void *q : ptrs) m |= reinterpret_cast<uintptr_t>(q);
+    return (m & 15) != 0;
+}
 
 // Workgroup order: MI355X deals workgroups round-robin over its 8 XCDs (block b and b+8 share an L2).
 // An XCD-sliced remap (each XCD walking one contiguous eighth of the matrix) was measured SLOWER than

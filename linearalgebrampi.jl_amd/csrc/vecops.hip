@@ -8,9 +8,8 @@
 // Bytes per element: dot 16 (8 for x.x), nrm2sq/asum/amax 8, axpy/xpay 24, scale 16, axpby 24.
 #include <stdlib.h>
 
-#include <initializer_list>
-
 #include "comm_internal.h"
+#include "solver_slots.h"
 
 namespace hpcla {
 
@@ -1071,7 +1070,7 @@ __global__ __launch_bounds__(256) void lsqr_xw_kernel(const double *__restrict__
 // beta' = 0 is the lucky termination: sn = 0, phibar = 0 and gate C ends the solve before anything is divided by beta'.
 // Divides, multiplies, adds, subtractions and square roots are rounded separately, in the order written.
 // The state is PCG's (done_iter, status, thr): thr = max(rtol sqrt(b.M b), atol)^2 as a double.
-// The scalars live in MINRES_SCALARS doubles at the slots of MinresSlot (comm_internal.h: the iterations loop in comm.hip names
+// The scalars live in MINRES_SCALARS doubles at the slots of MinresSlot (solver_slots.h: the iterations loop in solvers.hip names
 // yt's slot too; yt is the SpMV's, the others are read and written here).
 // Cache policy: t in minres_r (HPCLA_CG_NT bit 2: its last use) and x in minres_xw (bit 0) are not touched again within the
 // iteration and go non-temporally; r, y and w are re-read by the next SpMV or kernel.
@@ -1912,13 +1911,6 @@ HPCLA_API int64_t hpcla_bicgstab_work_bytes(void)
     return (int64_t)(BICG_PARTIAL_ARRAYS * MAX_PARTIALS + PCG_STATE_WORDS) * (int64_t)sizeof(double);
 }
 
-static inline bool bicg_misaligned(std::initializer_list<const void *> ptrs)
-{
-    uintptr_t m = 0;
-    for (const void *q : ptrs) m |= reinterpret_cast<uintptr_t>(q);
-    return (m & 15) != 0;
-}
-
 HPCLA_API int hpcla_bicg_dot_f64(hpcla_comm_t *comm, const double *rhat, const double *v, int64_t n, int64_t iter,
                                  const double *rho_dev, int64_t *state_dev, double *rv_out_dev, void *work, void *stream)
 {
@@ -1926,7 +1918,7 @@ HPCLA_API int hpcla_bicg_dot_f64(hpcla_comm_t *comm, const double *rhat, const d
     if (!rho_dev || !state_dev || !rv_out_dev || !work)
         return set_error(HPCLA_ERR_INVALID, "bicg_dot: null scalar / state / out / work");
     if (n > 0 && (!rhat || !v)) return set_error(HPCLA_ERR_INVALID, "bicg_dot: null vector");
-    if (bicg_misaligned({rhat, v})) return set_error(HPCLA_ERR_INVALID, "bicg_dot: vectors must be 16-byte aligned");
+    if (misaligned16({rhat, v})) return set_error(HPCLA_ERR_INVALID, "bicg_dot: vectors must be 16-byte aligned");
     double *partial = reinterpret_cast<double *>(work);
     const int g = reduce_grid(n);
     hipStream_t s = as_stream(stream);
@@ -1950,7 +1942,7 @@ HPCLA_API int hpcla_bicg_s_f64(const double *rho_dev, const double *rv_dev, cons
     if (!rho_dev || !rv_dev || !state_dev) return set_error(HPCLA_ERR_INVALID, "bicg_s: null scalar / state");
     if (n == 0) return HPCLA_OK;
     if (!r || !v || !s || (dinv && !sh)) return set_error(HPCLA_ERR_INVALID, "bicg_s: null vector");
-    if (bicg_misaligned({r, v, dinv, s, dinv ? sh : nullptr}))
+    if (misaligned16({r, v, dinv, s, dinv ? sh : nullptr}))
         return set_error(HPCLA_ERR_INVALID, "bicg_s: vectors must be 16-byte aligned");
     hipStream_t st = as_stream(stream);
     if (dinv) bicg_s_kernel<true><<<ew_grid(n / 2), 256, 0, st>>>(rho_dev, rv_dev, r, v, dinv, s, sh, n, state_dev);
@@ -1965,7 +1957,7 @@ HPCLA_API int hpcla_bicg_tts_f64(hpcla_comm_t *comm, const double *t, const doub
     if (n < 0 || iter < 1) return set_error(HPCLA_ERR_INVALID, "bicg_tts: negative size or iteration < 1");
     if (!state_dev || !triple_out_dev || !work) return set_error(HPCLA_ERR_INVALID, "bicg_tts: null state / out / work");
     if (n > 0 && (!t || !s)) return set_error(HPCLA_ERR_INVALID, "bicg_tts: null vector");
-    if (bicg_misaligned({t, s})) return set_error(HPCLA_ERR_INVALID, "bicg_tts: vectors must be 16-byte aligned");
+    if (misaligned16({t, s})) return set_error(HPCLA_ERR_INVALID, "bicg_tts: vectors must be 16-byte aligned");
     double *p_ts = reinterpret_cast<double *>(work), *p_tt = p_ts + MAX_PARTIALS, *p_ss = p_tt + MAX_PARTIALS;
     const int g = reduce_grid(n);
     hipStream_t st = as_stream(stream);
@@ -1990,7 +1982,7 @@ HPCLA_API int hpcla_bicg_xr_f64(hpcla_comm_t *comm, const double *rho_dev, const
     if (!rho_dev || !rv_dev || !triple_dev || !state_dev || !pair_out_dev || !work)
         return set_error(HPCLA_ERR_INVALID, "bicg_xr: null scalar / state / out / work");
     if (n > 0 && (!ph || !s || !t || !rhat || !x || !r)) return set_error(HPCLA_ERR_INVALID, "bicg_xr: null vector");
-    if (bicg_misaligned({ph, sh, s, t, rhat, x, r}))
+    if (misaligned16({ph, sh, s, t, rhat, x, r}))
         return set_error(HPCLA_ERR_INVALID, "bicg_xr: vectors must be 16-byte aligned");
     double *p_rr = reinterpret_cast<double *>(work), *p_rho = p_rr + MAX_PARTIALS;
     const int g = reduce_grid(n);
@@ -2030,7 +2022,7 @@ HPCLA_API int hpcla_bicg_p_f64(const double *rho_new_dev, const double *rho_dev,
         return set_error(HPCLA_ERR_INVALID, "bicg_p: null scalar / state");
     if (n == 0) return HPCLA_OK;
     if (!r || !v || !p || (dinv && !ph)) return set_error(HPCLA_ERR_INVALID, "bicg_p: null vector");
-    if (bicg_misaligned({r, v, dinv, p, dinv ? ph : nullptr}))
+    if (misaligned16({r, v, dinv, p, dinv ? ph : nullptr}))
         return set_error(HPCLA_ERR_INVALID, "bicg_p: vectors must be 16-byte aligned");
     hipStream_t st = as_stream(stream);
     if (dinv)
@@ -2055,7 +2047,7 @@ HPCLA_API int hpcla_lsqr_u_f64(hpcla_comm_t *comm, double *scal_dev, const doubl
     if (n < 0 || iter < 1) return set_error(HPCLA_ERR_INVALID, "lsqr_u: negative size or iteration < 1");
     if (!scal_dev || !state_dev || !work) return set_error(HPCLA_ERR_INVALID, "lsqr_u: null scalars / state / work");
     if (n > 0 && (!tu || !uh)) return set_error(HPCLA_ERR_INVALID, "lsqr_u: null vector");
-    if (bicg_misaligned({tu, uh})) return set_error(HPCLA_ERR_INVALID, "lsqr_u: vectors must be 16-byte aligned");
+    if (misaligned16({tu, uh})) return set_error(HPCLA_ERR_INVALID, "lsqr_u: vectors must be 16-byte aligned");
     double *partial = reinterpret_cast<double *>(work);
     const int g = reduce_grid(n);
     hipStream_t s = as_stream(stream);
@@ -2074,7 +2066,7 @@ HPCLA_API int hpcla_lsqr_v_f64(hpcla_comm_t *comm, double *scal_dev, const doubl
     if (n < 0 || iter < 1) return set_error(HPCLA_ERR_INVALID, "lsqr_v: negative size or iteration < 1");
     if (!scal_dev || !state_dev || !work) return set_error(HPCLA_ERR_INVALID, "lsqr_v: null scalars / state / work");
     if (n > 0 && (!tv || !vh)) return set_error(HPCLA_ERR_INVALID, "lsqr_v: null vector");
-    if (bicg_misaligned({tv, vh})) return set_error(HPCLA_ERR_INVALID, "lsqr_v: vectors must be 16-byte aligned");
+    if (misaligned16({tv, vh})) return set_error(HPCLA_ERR_INVALID, "lsqr_v: vectors must be 16-byte aligned");
     double *partial = reinterpret_cast<double *>(work);
     const int g = reduce_grid(n);
     hipStream_t s = as_stream(stream);
@@ -2099,7 +2091,7 @@ HPCLA_API int hpcla_lsqr_xw_f64(const double *scal_dev, const double *vh, double
     if (!scal_dev || !state_dev) return set_error(HPCLA_ERR_INVALID, "lsqr_xw: null scalars / state");
     if (n == 0) return HPCLA_OK;
     if (!vh || !x || !w) return set_error(HPCLA_ERR_INVALID, "lsqr_xw: null vector");
-    if (bicg_misaligned({vh, x, w})) return set_error(HPCLA_ERR_INVALID, "lsqr_xw: vectors must be 16-byte aligned");
+    if (misaligned16({vh, x, w})) return set_error(HPCLA_ERR_INVALID, "lsqr_xw: vectors must be 16-byte aligned");
     hipStream_t s = as_stream(stream);
     if (cg_nt_mask() & 1) lsqr_xw_kernel<true><<<ew_grid(n / 2), 256, 0, s>>>(scal_dev, vh, x, w, n, iter, state_dev);
     else lsqr_xw_kernel<false><<<ew_grid(n / 2), 256, 0, s>>>(scal_dev, vh, x, w, n, iter, state_dev);
@@ -2122,7 +2114,7 @@ HPCLA_API int hpcla_minres_r_f64(hpcla_comm_t *comm, double *scal_dev, const dou
     if (n > 0 && (!t || !r2 || !r1 || (dinv && !yn))) return set_error(HPCLA_ERR_INVALID, "minres_r: null vector");
     if (n > 0 && (r1 == r2 || r1 == t || (dinv && (yn == r1 || yn == r2 || yn == t))))
         return set_error(HPCLA_ERR_INVALID, "minres_r: the written vectors must not alias the others");
-    if (bicg_misaligned({t, r2, dinv, r1, dinv ? yn : nullptr}))
+    if (misaligned16({t, r2, dinv, r1, dinv ? yn : nullptr}))
         return set_error(HPCLA_ERR_INVALID, "minres_r: vectors must be 16-byte aligned");
     double *partial = reinterpret_cast<double *>(work);
     const int g = reduce_grid(n);
@@ -2156,7 +2148,7 @@ HPCLA_API int hpcla_minres_xw_f64(const double *scal_dev, const double *y, const
     if (!y || !w2 || !w1 || !x) return set_error(HPCLA_ERR_INVALID, "minres_xw: null vector");
     if (w1 == w2 || w1 == y || w1 == x || x == y || x == w2)
         return set_error(HPCLA_ERR_INVALID, "minres_xw: the written vectors must not alias the others");
-    if (bicg_misaligned({y, w2, w1, x})) return set_error(HPCLA_ERR_INVALID, "minres_xw: vectors must be 16-byte aligned");
+    if (misaligned16({y, w2, w1, x})) return set_error(HPCLA_ERR_INVALID, "minres_xw: vectors must be 16-byte aligned");
     hipStream_t s = as_stream(stream);
     if (cg_nt_mask() & 1) minres_xw_kernel<true><<<ew_grid(n / 2), 256, 0, s>>>(scal_dev, y, w2, w1, x, n, iter, state_dev);
     else minres_xw_kernel<false><<<ew_grid(n / 2), 256, 0, s>>>(scal_dev, y, w2, w1, x, n, iter, state_dev);
@@ -2195,7 +2187,7 @@ HPCLA_API int hpcla_gmres_dots_f64(hpcla_comm_t *comm, const double *V, int64_t 
         return set_error(HPCLA_ERR_INVALID, "gmres_dots: negative size, odd or short pitch, or column count outside 1..64");
     if (!state_dev || !h_out_dev || !work) return set_error(HPCLA_ERR_INVALID, "gmres_dots: null state / out / work");
     if (n > 0 && (!V || !w)) return set_error(HPCLA_ERR_INVALID, "gmres_dots: null vector");
-    if (bicg_misaligned({V, w})) return set_error(HPCLA_ERR_INVALID, "gmres_dots: vectors must be 16-byte aligned");
+    if (misaligned16({V, w})) return set_error(HPCLA_ERR_INVALID, "gmres_dots: vectors must be 16-byte aligned");
     double *partial = reinterpret_cast<double *>(work);
     const int g = reduce_grid(n);
     hipStream_t s = as_stream(stream);
@@ -2238,7 +2230,7 @@ HPCLA_API int hpcla_gmres_update_f64(hpcla_comm_t *comm, const double *V, int64_
     if (!h_dev || !state_dev || (small_dev && (!hist_k_dev || !work)))
         return set_error(HPCLA_ERR_INVALID, "gmres_update: null coefficients / state / history / work");
     if (n > 0 && (!V || !w)) return set_error(HPCLA_ERR_INVALID, "gmres_update: null vector");
-    if (bicg_misaligned({V, w})) return set_error(HPCLA_ERR_INVALID, "gmres_update: vectors must be 16-byte aligned");
+    if (misaligned16({V, w})) return set_error(HPCLA_ERR_INVALID, "gmres_update: vectors must be 16-byte aligned");
     double *partial = reinterpret_cast<double *>(work);
     const int g = reduce_grid(n);
     hipStream_t s = as_stream(stream);
@@ -2268,7 +2260,7 @@ HPCLA_API int hpcla_gmres_next_f64(const double *w, const double *hn_dev, const 
     if (!hn_dev || !state_dev) return set_error(HPCLA_ERR_INVALID, "gmres_next: null scalar / state");
     if (n == 0) return HPCLA_OK;
     if (!w || !v_next || (dinv && !z)) return set_error(HPCLA_ERR_INVALID, "gmres_next: null vector");
-    if (bicg_misaligned({w, dinv, v_next, dinv ? z : nullptr}))
+    if (misaligned16({w, dinv, v_next, dinv ? z : nullptr}))
         return set_error(HPCLA_ERR_INVALID, "gmres_next: vectors must be 16-byte aligned");
     hipStream_t s = as_stream(stream);
     if (dinv) gmres_next_kernel<true><<<ew_grid(n / 2), 256, 0, s>>>(w, hn_dev, dinv, v_next, z, n, state_dev);
@@ -2298,7 +2290,7 @@ HPCLA_API int hpcla_gmres_xupdate_f64(const double *V, int64_t ldv, int ncols, c
     if (!y_dev) return set_error(HPCLA_ERR_INVALID, "gmres_xupdate: null coefficients");
     if (n == 0) return HPCLA_OK;
     if (!V || !x) return set_error(HPCLA_ERR_INVALID, "gmres_xupdate: null vector");
-    if (bicg_misaligned({V, dinv, x})) return set_error(HPCLA_ERR_INVALID, "gmres_xupdate: vectors must be 16-byte aligned");
+    if (misaligned16({V, dinv, x})) return set_error(HPCLA_ERR_INVALID, "gmres_xupdate: vectors must be 16-byte aligned");
     hipStream_t s = as_stream(stream);
     const uint32_t g = ew_grid(n / 2);
 #define HPCLA_GMRES_XUP(NX)                                                                                            \
@@ -2322,7 +2314,7 @@ HPCLA_API int hpcla_gmres_residual_f64(hpcla_comm_t *comm, const double *b, doub
     if (!small_dev || !hist_k_dev || !state_dev || !work)
         return set_error(HPCLA_ERR_INVALID, "gmres_residual: null small arrays / history / state / work");
     if (n > 0 && (!b || !w)) return set_error(HPCLA_ERR_INVALID, "gmres_residual: null vector");
-    if (bicg_misaligned({b, w})) return set_error(HPCLA_ERR_INVALID, "gmres_residual: vectors must be 16-byte aligned");
+    if (misaligned16({b, w})) return set_error(HPCLA_ERR_INVALID, "gmres_residual: vectors must be 16-byte aligned");
     GmresSmall q;
     gmres_small_layout(restart, small_dev, &q);
     double *partial = reinterpret_cast<double *>(work);
@@ -2437,7 +2429,7 @@ HPCLA_API int hpcla_eigsh_update_f64(hpcla_comm_t *comm, const double *V, int64_
     if (!h_dev || !state_dev || !small_dev || !work)
         return set_error(HPCLA_ERR_INVALID, "eigsh_update: null coefficients / state / small arrays / work");
     if (n > 0 && (!V || !w)) return set_error(HPCLA_ERR_INVALID, "eigsh_update: null vector");
-    if (bicg_misaligned({V, w})) return set_error(HPCLA_ERR_INVALID, "eigsh_update: vectors must be 16-byte aligned");
+    if (misaligned16({V, w})) return set_error(HPCLA_ERR_INVALID, "eigsh_update: vectors must be 16-byte aligned");
     double *partial = reinterpret_cast<double *>(work);
     const int g = reduce_grid(n);
     hipStream_t s = as_stream(stream);
@@ -2555,7 +2547,7 @@ HPCLA_API int hpcla_svds_update_f64(hpcla_comm_t *comm, const double *W, int64_t
     if (!state_dev || !small_dev || !work || (ncols > 0 && !h_dev))
         return set_error(HPCLA_ERR_INVALID, "svds_update: null coefficients / state / small arrays / work");
     if (n > 0 && (!w || (ncols > 0 && !W))) return set_error(HPCLA_ERR_INVALID, "svds_update: null vector");
-    if (bicg_misaligned({W, w})) return set_error(HPCLA_ERR_INVALID, "svds_update: vectors must be 16-byte aligned");
+    if (misaligned16({W, w})) return set_error(HPCLA_ERR_INVALID, "svds_update: vectors must be 16-byte aligned");
     double *partial = reinterpret_cast<double *>(work);
     const int g = reduce_grid(n);
     const int j = ncols - side;

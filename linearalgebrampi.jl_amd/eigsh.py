@@ -7,7 +7,7 @@ documented for.  The reference has no eigensolver; a caller of its operators com
 classical Gram-Schmidt the step that orthogonalises against ``c`` basis columns is ``2c`` dots, ``2c`` axpys and ``2c + 1`` host
 read-backs, and the restart is a dense product plus a copy back.  Here a step is one SpMV and the fused GMRES kernels of
 csrc/vecops.hip (``gmres_dots``, ``gmres_update``, ``gmres_next``) with a Lanczos small step that keeps the projected matrix
-(``hpcla_eigsh_update_f64``); the host enqueues a whole cycle in one library call (``hpcla_eigsh_steps_f64_*``) and reads back
+(``hpcla_eigsh_update_f64``); the host enqueues a whole cycle in one library call (``hpcla_eigsh_steps_f64_*``, csrc/solvers.hip) and reads back
 once per cycle; the restart compresses the basis in place in one pass (``hpcla_eigsh_rotate_f64``, csrc/eigsh.hip).
 
 Thick-restart Lanczos (Wu and Simon; for symmetric ``A`` it is Krylov-Schur).  ``m = ncv``, ``j`` counts columns inside a cycle,

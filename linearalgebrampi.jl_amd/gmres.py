@@ -7,7 +7,7 @@ with twice-applied classical Gram-Schmidt the step that orthogonalises against `
 and ``2c + 1`` host read-backs.  Here it is one SpMV and the fused HIP steps of csrc/vecops.hip (``gmres_dots``: all ``c`` sums
 with one read of the basis; ``gmres_update``: the whole running subtraction in one pass), whose scalars, Givens rotations,
 stop rule and breakdown test stay on the device; the host enqueues ``check_every`` inner steps per library call
-(``hpcla_gmres_iterations_f64_*``) and reads 16 bytes of state per chunk, exactly as the other two solvers do.
+(``hpcla_gmres_iterations_f64_*``, csrc/solvers.hip) and reads 16 bytes of state per chunk, exactly as the other two solvers do.
 
 Right-preconditioned, ``K`` = identity, ``dinv .*`` or the operator of ``hp.ilu0`` / ``hp.amg`` (ilu.py, amg.py; ``_gmres_operator`` enqueues the same
 steps with ``dinv == NULL`` one by one and applies ``K`` between them); gate order and rounding order (tests/_gmres_cases.py restates them):
@@ -29,8 +29,8 @@ from __future__ import annotations
 from typing import Optional, Tuple
 
 from . import _capi
-from .bicgstab import _AMGOperator, _bicgstab_dinv, _ilu_operator
-from .cg import CGInfo, _PairHistory, _residual_norms, _run_chunks, _solver_arguments, _stop_rule_or_done
+from .krylov import (CGInfo, _AMGOperator, _bicgstab_dinv, _ilu_operator, _PairHistory, _residual_norms, _run_chunks,
+                     _solver_arguments, _stop_rule_or_done)
 from .sparse import get_vector_plan, mul_
 from .vectors import HPCVector, current_stream_ptr, dptr, norm, rd16_vector
 

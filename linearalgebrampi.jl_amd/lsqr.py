@@ -6,7 +6,7 @@ has no such path (its ``A \\ b`` goes through MUMPS and needs a square matrix); 
 (src/sparse.jl:2096-2128), ``transpose(A)*u`` (src/sparse.jl:2136-2142), ``norm`` (src/vectors.jl:758-780) and broadcast
 updates (src/vectors.jl:1203-1226): two SpMVs, about ten launches and four host read-backs per iteration.  Here an iteration
 is the two SpMVs -- on ``A``'s plan and on the plan of the materialised, cached ``transpose(A)`` -- and three gated HIP steps
-(csrc/vecops.hip, ``hpcla_lsqr_iterations_f64_*``) whose scalars, stop rules and history stay on the device; the host
+(csrc/vecops.hip, chained by ``hpcla_lsqr_iterations_f64_*`` in csrc/solvers.hip) whose scalars, stop rules and history stay on the device; the host
 enqueues ``check_every`` iterations per library call and reads 16 bytes of state per chunk, exactly as ``hp.cg`` does.
 
 Paige and Saunders' Golub-Kahan recurrences with NO vector normalised in memory: uh and vh are kept unnormalised next to their
@@ -29,7 +29,7 @@ from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
 from . import _capi
-from .cg import _PairHistory, _run_chunks
+from .krylov import _PairHistory, _run_chunks
 from .partition import compute_partition_hash
 from .sparse import get_vector_plan, mul_
 from .transpose import TransposedHPCSparseMatrix

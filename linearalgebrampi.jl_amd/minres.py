@@ -5,7 +5,7 @@ reference (src/mumps_factorization.jl:247-259, MUMPS on the host).  ``hp.cg`` br
 iteration (``p.Ap <= 0``); ``hp.gmres`` solves them but ignores the symmetry.  A caller of the reference composes MINRES from
 ``A*v`` (src/sparse.jl:2096-2128), ``dot`` (src/vectors.jl:798-812) and broadcast updates (src/vectors.jl:1203-1226): about ten
 launches and three host read-backs per iteration.  Here an iteration is the SpMV with the partials of ``y . A y`` in its
-epilogue and two gated HIP steps (csrc/vecops.hip, ``hpcla_minres_iterations_f64_*``) whose scalars, stop rule and history stay
+epilogue and two gated HIP steps (csrc/vecops.hip, chained by ``hpcla_minres_iterations_f64_*`` in csrc/solvers.hip) whose scalars, stop rule and history stay
 on the device; the host enqueues ``check_every`` iterations per library call and reads 16 bytes of state per chunk, exactly as
 ``hp.cg`` does.
 
@@ -30,7 +30,7 @@ import math
 from typing import Optional, Tuple
 
 from . import _capi
-from .cg import CGInfo, _PairHistory, _residual_norms, _run_chunks, _solver_arguments, _STATUS
+from .krylov import _STATUS, CGInfo, _PairHistory, _residual_norms, _run_chunks, _solver_arguments
 from .partition import compute_partition_hash
 from .sparse import get_vector_plan, mul_
 from .vectors import HPCVector, current_stream_ptr, dot, dptr, maximum, minimum, norm, rd16_vector

@@ -426,7 +426,7 @@ class VectorPlan:
 
     def matrix_block(self, A: "HPCSparseMatrix", narrow: bool = True) -> tuple:
         """Matrix A as this plan multiplies it: the argument run of the ``*_iterations_*`` / ``*_steps_*`` entry points
-        (csrc/comm.hip builds one SpmvBlock from it).  The halo plan comes first -- an entry that takes ``comm`` second is
+        (csrc/solvers.hip builds one SpmvBlock from it).  The halo plan comes first -- an entry that takes ``comm`` second is
         passed ``blk[0], comm, *blk[1:]``; the 16-bit columns and the pattern table are present on Int32 plans only, and not
         at all with ``narrow=False`` (entries without the pair: hpcla_cg_iterations_*)."""
         pair = (dptr(self.cols16), self.patterns) if narrow and not self.is_i64 else ()

@@ -10,7 +10,7 @@ both sides the step that orthogonalises against ``c`` columns on each side is ``
 read-backs, and the restart is two dense products plus their copies back.  Here a step is two SpMVs -- on ``A``'s plan and on
 the plan of the materialised, cached ``transpose(A)``, as in ``hp.lsqr`` -- and, per side, the fused GMRES kernels of
 csrc/vecops.hip (``gmres_dots``, ``gmres_update``, ``gmres_next``) with a Golub-Kahan small step that keeps the projected
-matrix (``hpcla_svds_update_f64``); the host enqueues a whole cycle in one library call (``hpcla_svds_steps_f64_*``) and reads
+matrix (``hpcla_svds_update_f64``); the host enqueues a whole cycle in one library call (``hpcla_svds_steps_f64_*``, csrc/solvers.hip) and reads
 back once per cycle; the restart compresses each basis in place in one pass (``hpcla_eigsh_rotate_f64``, csrc/eigsh.hip).
 
 Thick-restart bidiagonalisation with full two-sided reorthogonalisation (Baglama and Reichel; SLEPc's TRLBD).  ``m = ncv``, ``j``

@@ -1,6 +1,6 @@
 """Shared cases of the BiCGStab solver (``hp.bicgstab``) and a numpy restatement of its loop.
 
-The restatement is plain arrays; it follows the device loop's gate order and rounding order literally (csrc/comm.hip,
+The restatement is plain arrays; it follows the device loop's gate order and rounding order literally (csrc/solvers.hip,
 ``bicgstab_iterations_impl``; the kernels in csrc/vecops.hip): every update is a separately rounded multiply and add in the
 order the kernels use, alpha / omega / beta are formed by the same expressions, and gates A, S, T, B, O are tested where the
 device tests them.  It is an independent statement of the algorithm, not of the device's summation order: ``dot`` can be

@@ -1,6 +1,6 @@
 """Shared cases of the eigensolver (``hp.eigsh``) and a numpy restatement of its loop.
 
-The restatement is plain arrays; it follows the device loop's gate order and rounding order literally (csrc/comm.hip,
+The restatement is plain arrays; it follows the device loop's gate order and rounding order literally (csrc/solvers.hip,
 ``eigsh_steps_impl``; the kernels in csrc/vecops.hip and csrc/eigsh.hip): the start is a division by ``sqrt(v0.v0)``, the running
 subtractions of the two Gram-Schmidt passes run over the basis columns in ascending order, ``T[i, j] = h1[i] + h2[i]``,
 ``beta[j] = sqrt(nn)``, gates N and I are tested where the device tests them, the host's cycle end (the assembly of T, ``eigh``,

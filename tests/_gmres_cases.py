@@ -1,6 +1,6 @@
 """Shared cases of the restarted GMRES solver (``hp.gmres``) and a numpy restatement of its loop.
 
-The restatement is plain arrays; it follows the device loop's gate order and rounding order literally (csrc/comm.hip,
+The restatement is plain arrays; it follows the device loop's gate order and rounding order literally (csrc/solvers.hip,
 ``gmres_iterations_impl``; the kernels in csrc/vecops.hip): every multiply, add, subtract, divide and sqrt is rounded separately
 in the order the kernels use, the running subtractions run over the basis columns in ascending order, the Givens rotations and
 the back substitution are the small step's own expressions, and gates R, D, C are tested where the device tests them.  It is an

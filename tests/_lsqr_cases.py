@@ -1,6 +1,6 @@
 """Shared cases of the least-squares solver (``hp.lsqr``) and a numpy restatement of its loop.
 
-The restatement is plain arrays; it follows the device loop's gate order and rounding order literally (csrc/comm.hip,
+The restatement is plain arrays; it follows the device loop's gate order and rounding order literally (csrc/solvers.hip,
 ``lsqr_iterations_impl``; the kernels in csrc/vecops.hip): uhat and vhat are kept unnormalised next to their norms beta and
 alpha, every update is a separately rounded divide / multiply / subtract in the order the kernels use, the scalars of the
 step are formed by the same expressions, and gate U and the three stop gates are tested where the device tests them.  It is

@@ -1,6 +1,6 @@
 """Shared cases of the MINRES solver (``hp.minres``) and a numpy restatement of its loop.
 
-The restatement is plain arrays; it follows the device loop's gate order and rounding order literally (csrc/comm.hip,
+The restatement is plain arrays; it follows the device loop's gate order and rounding order literally (csrc/solvers.hip,
 ``minres_iterations_impl``; the kernels in csrc/vecops.hip): the Lanczos vectors r1 and r2 are kept unnormalised next to their
 M-norms oldb and beta, every update is a separately rounded divide / multiply / subtract in the order the kernels use
 (``residual_update``, ``direction_update``), the scalars of the step are formed by the same expressions (``step``), and gates

@@ -1,6 +1,6 @@
 """Shared cases of the converging CG solver (``hp.cg``) and a numpy restatement of its loop.
 
-The restatement is plain arrays with ``np.dot``; it follows the device loop's gate order (csrc/comm.hip,
+The restatement is plain arrays with ``np.dot``; it follows the device loop's gate order (csrc/solvers.hip,
 ``pcg_iterations_impl``): Ap and pAp, gate A (breakdown), the residual update with both sums, gate B (the stop rule), then the
 deferred x update together with the direction update.  It is an independent statement of the algorithm, not of the device's
 summation order: histories are compared to ``CG_RTOL``, iteration counts to +-2 (tests/test_gpu_pcg.py has the basis).

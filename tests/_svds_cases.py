@@ -1,6 +1,6 @@
 """Shared cases of the truncated SVD (``hp.svds``) and a numpy restatement of its loop.
 
-The restatement is plain arrays; it follows the device loop's gate order and rounding order literally (csrc/comm.hip,
+The restatement is plain arrays; it follows the device loop's gate order and rounding order literally (csrc/solvers.hip,
 ``svds_steps_impl``; the kernels in csrc/vecops.hip and csrc/eigsh.hip): the start is a division by ``sqrt(v0.v0)``, the running
 subtractions of the two Gram-Schmidt passes of either half run over the basis columns in ascending order,
 ``B[i, j] = g1[i] + g2[i]``, ``B[j, j] = sqrt(aa)``, ``beta[j] = sqrt(bb)``, gates N, Z, N' and Z' are tested where the device
